@@ -52,6 +52,7 @@ WORKLOADS = {
 }
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured copy)
 EXIT_NEED_GPUS = 3
+DUMP_BYTES = 64_000_000  # --dump-outputs: every window when the arrays fit in this, else a fixed seeded sample of windows
 
 
 def synth_transcript(L, seed, kind="uniform"):
@@ -83,6 +84,8 @@ def relaunch_under_torchrun(args):
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__),
            "--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup)]
     cmd += ["--config", args.config, "--shuffle", args.shuffle or "", "--input", args.input]
+    if args.dump_outputs:
+        cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     if args.no_live_counters:
         cmd.append("--no-live-counters")
     if args.no_cpu_baseline:
@@ -364,6 +367,29 @@ def verify_sample(seq, W, step, r, kind, seed, lo, n_loc, en, db, cen, div, n_ch
     return len(idx), bad
 
 
+def dump_outputs(out_dir, computed, sample_seed=0):
+    """computed: name -> numpy array with one row per window, every window of the last timed step in window order.
+    Writes out_dir/<name>.npy (float64 stays float64, everything else becomes float32: int32 energies and the ASCII
+    codes of structure / centroid are exact in it) and out_dir/window_index.npy, the windows written.  That is every
+    window when they fit in DUMP_BYTES, else a sorted sample drawn with sample_seed: the same windows on every run of
+    the same workload.  Returns the number of windows written."""
+    import numpy as np
+    arrays = {k: np.asarray(v, dtype=np.float64 if np.asarray(v).dtype == np.float64 else np.float32)
+              for k, v in computed.items()}
+    n = len(next(iter(arrays.values())))
+    per_window = 8 + sum(a[:1].nbytes for a in arrays.values())  # + the float64 window index
+    n_keep = min(n, (DUMP_BYTES - 4096) // per_window)  # 4096: room for the .npy headers
+    if n_keep < n:
+        idx = np.sort(np.random.default_rng(sample_seed).choice(n, n_keep, replace=False))
+    else:
+        idx = np.arange(n)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "window_index.npy"), idx.astype(np.float64))
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a[idx]))
+    return int(n_keep)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -379,11 +405,16 @@ def main():
     ap.add_argument("--shuffle", default="", help="di (the north star's; default) or mono (SURVEY.md 8d's secondary run)")
     ap.add_argument("--input", choices=("uniform", "viral"), default="uniform",
                     help="uniform i.i.d. ACGU (default) or SURVEY.md 8d's viral-like input (60 %% AU + planted hairpins)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last one computed (energies, structure, centroid, ens_div, "
+                         "ens_dG per window) as DIR/<name>.npy, float32 / float64, at most 64 MB with DIR/window_index.npy")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 2 if args.config == "cfg3" else 1
     if args.warmup is None:
         args.warmup = 1 if args.config == "cfg3" else 0
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "RANK" not in os.environ:
         return relaunch_under_torchrun(args)
 
@@ -566,6 +597,13 @@ def main():
         else:
             checked, bad = verify_sample(seq, W, step, r, kind, wl["shuffle_seed"], lo, n_loc, en, db, cen, div, wl["verify"],
                                          engine=wl.get("verify_engine", "checker"))
+        if args.dump_outputs:
+            # one rank: its shard is every window; several: the gathered records of all shards
+            computed = merged if gather_check is not None else {
+                "energies": en[:n_loc].cpu().numpy(), "structure": db[:n_loc].cpu().numpy(),
+                "centroid": cen[:n_loc].cpu().numpy(), "ens_div": div[:n_loc].cpu().numpy(),
+                "ens_dG": dG[:n_loc].cpu().numpy()}
+            dump_outputs(args.dump_outputs, computed)
         algorithmic_bytes = folds_per_launch * bytes_per_fold
         out = {
             "metric": wl["metric"],

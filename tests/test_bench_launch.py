@@ -37,6 +37,49 @@ def test_world_size_mismatch_is_reported():
     assert out.returncode == 2 and "WORLD_SIZE=2" in out.stderr
 
 
+def test_steps_below_one_are_refused():
+    """ms_per_step divides by --steps: zero timed steps is a usage error, not a result line."""
+    for argv in (("--steps", "0"), ("--steps", "-1"), ("--warmup", "-1")):
+        out = run_bench("--gpus", "1", *argv)
+        assert out.returncode == 2 and "--steps must be at least 1" in out.stderr, argv
+        assert '"metric"' not in out.stdout
+
+
+def test_dump_outputs_writes_every_window_or_a_fixed_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: one float32 / float64 .npy per array of the last step plus window_index.npy; every window when
+    the files fit in DUMP_BYTES, else the same seeded sample of windows on every call, the files never above DUMP_BYTES."""
+    import numpy as np
+    import bench
+    rng = np.random.default_rng(0)
+    n, W, r = 500, 120, 100
+    computed = {"energies": rng.integers(-9000, 0, (n, r + 1)).astype(np.int32),
+                "structure": np.frombuffer(b"().", dtype=np.uint8)[rng.integers(0, 3, (n, W + 1))],
+                "ens_div": rng.random(n)}
+
+    def load(d):
+        return {f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)}
+
+    assert bench.dump_outputs(str(tmp_path / "all"), computed) == n
+    got = load(tmp_path / "all")
+    assert sorted(got) == ["energies", "ens_div", "structure", "window_index"]
+    assert got["energies"].dtype == np.float32 and got["structure"].dtype == np.float32
+    assert got["ens_div"].dtype == np.float64 and got["window_index"].dtype == np.float64
+    assert (got["window_index"] == np.arange(n)).all()
+    for k, v in computed.items():
+        assert (got[k] == v).all(), k
+
+    monkeypatch.setattr(bench, "DUMP_BYTES", 300_000)
+    k1 = bench.dump_outputs(str(tmp_path / "s1"), computed)
+    k2 = bench.dump_outputs(str(tmp_path / "s2"), computed)
+    assert 0 < k1 == k2 < n
+    a, b = load(tmp_path / "s1"), load(tmp_path / "s2")
+    assert sum(os.path.getsize(tmp_path / "s1" / f) for f in os.listdir(tmp_path / "s1")) <= 300_000
+    idx = a["window_index"].astype(np.int64)
+    assert (a["window_index"] == b["window_index"]).all() and len(idx) == k1 and (np.diff(idx) > 0).all()
+    for k, v in computed.items():
+        assert (a[k] == v[idx]).all() and (b[k] == a[k]).all(), k
+
+
 def test_calibrated_unit_fractions_from_the_committed_rates():
     """bench.py's roofline.secondary: instruction counts x the instruction costs measured on MI355X (profiles/r05/
     mfe_issue_rates.json: tools/micro/issue_rates.hip, valu_classes.hip; the kernel's vector mix from its round-5 ISA) / the launch

@@ -68,6 +68,32 @@ def test_bench_single_rank_over_rccl_cfg2():
     assert out["roofline"]["launches"] == 1 and out["roofline"]["folds_per_launch"] == 30659
 
 
+def test_bench_dump_outputs_are_what_the_timed_path_computed_cfg1(gpu_engine, oracle, tmp_path):
+    """bench.py --dump-outputs on one rank: the per-window arrays of the last of --steps timed steps, equal to what the engine
+    computes for the same workload through sf_scan, and to the oracle's whole per-window job on the same shuffles."""
+    d = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "0", "--no-live-counters",
+           "--no-cpu-baseline", "--config", "cfg1", "--dump-outputs", str(d)]
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
+    assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-3000:])
+    out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln][0])
+    assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["config"]["windows"] == 23
+    got = {f[:-4]: np.load(d / f) for f in os.listdir(d)}
+    assert sorted(got) == ["centroid", "energies", "ens_dG", "ens_div", "structure", "window_index"]
+    assert (got["window_index"] == np.arange(23)).all()
+    seq = synth_transcript(1000, 1)
+    ref = gpu_engine.scan(seq, 120, 40, 0, 23, 10, _lib.SHUFFLE_DI, 2026, raw=True)
+    for k, v in ref.items():
+        assert got[k].dtype == (np.float64 if v.dtype == np.float64 else np.float32), k
+        assert got[k].shape == v.shape and (got[k] == v).all(), k
+    orc = oracle.scan_windows(ascii_rows(oracle.shuffle_windows(seq, 120, 40, 0, 23, 10, _lib.SHUFFLE_DI, 2026)), 23, 10)
+    text = lambda a: [bytes(row[:120].astype(np.uint8)).decode() for row in a]
+    assert (got["energies"] == orc["energies"]).all()
+    assert text(got["structure"]) == orc["structure"] and text(got["centroid"]) == orc["centroid"]
+    assert np.abs(got["ens_div"] - orc["ens_div"]).max() < 1e-8
+
+
 def test_bench_two_ranks_on_gpu0_over_gloo_cfg2():
     """bench.py with world == 2 on REAL device tensors (the code the driver's multi-GPU run is the first to execute with
     world > 1): both ranks on GPU 0 — RCCL refuses two ranks on one device, so the collective runs over gloo, staged through
