@@ -1,0 +1,37 @@
+/*
+ * scanfold_hip_long.h — whole-record folds past the window limit (SF_MAX_W), an extension of include/scanfold_hip.h
+ * exported by the same library (libscanfold_hip.so).  Conventions as there: 0 or a negative sf_status, caller-owned host
+ * buffers, the resident parameter set and base-pair span (sf_params_load, sf_set_max_bp_span).
+ *
+ * Kept out of scanfold_hip.h on purpose: that header is the contract the CPU twin of the C ABI implements symbol for
+ * symbol, and the twin has no long fold.  Bind these symbols only where the loaded library exports them.
+ */
+#ifndef SCANFOLD_HIP_LONG_H
+#define SCANFOLD_HIP_LONG_H
+
+#include "scanfold_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define SF_MAX_LONG 32767 /* longest sequence sf_fold_long accepts (int16 bracket partners of the constraint model) */
+
+/* fc = RNA.fold_compound(seq, md); fc.hc_add_from_db(cons); fc.mfe() for one sequence of any length 1..SF_MAX_LONG
+ * (ScanFold.py:1520-1539, --global_refold).  seq: L bytes as in scanfold_hip.h.  cons: L characters with the meaning of
+ * sf_fold_constrained, or NULL.  db_out: L+1 bytes or NULL (energy only, no traceback).
+ * Structures are those of the window kernels and of the oracle's traceback, byte for byte, at every length.
+ * The DP tables live in device memory, allocated for the call and freed before it returns:
+ *   12 * L (L+1) / 2 + ~80 L bytes  (5.4 GB at L = 29 903).
+ * Not enough device memory: SF_ERR_HIP with the text in sf_last_hip_error().  Unbalanced brackets: SF_ERR_CONSTRAINT.
+ * L < 1, L > SF_MAX_LONG, seq NULL: SF_ERR_BAD_ARG. */
+int sf_fold_long(const uint8_t *seq, int L, const char *cons, int32_t *mfe_dcal_out, char *db_out);
+
+/* Device-event times (ms) of the phases of the last successful sf_fold_long: the fill of c / fML (one launch per
+ * diagonal), the exterior loop f5, and the traceback (0 when it was not asked for).  Any pointer may be NULL. */
+int sf_fold_long_times(double *fill_ms, double *f5_ms, double *trace_ms);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

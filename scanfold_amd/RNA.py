@@ -7,6 +7,9 @@ md.max_bp_span (ScanFold.py:214-215) is honoured (sf_set_max_bp_span).
 md.temperature other than 37 needs a parameter set with enthalpy tables (params.load_par of a real .par file).
 fc.hc_add_from_db and fc.sc_add_SHAPE_deigan (ScanFold-Scan.py:410; ScanFold.py:512,534) are provided through
 sf_fold_constrained.  Not provided: duplexfold, plotting, Zarringhalam soft constraints (upstream's call fails too).
+Sequences longer than SF_MAX_W (400 nt, the window kernels' limit) fold with fc.mfe() / RNA.fold through sf_fold_long
+(whole records up to 32 767 nt: ScanFold.py --global_refold, :1509-1547), hc_add_from_db included; their partition
+function, centroid and SHAPE term do not exist and raise NotImplementedError.
 """
 import numpy as np
 
@@ -84,8 +87,17 @@ class fold_compound:
             raise TypeError("sc_add_SHAPE_zarringhalam() missing required arguments: b, default_value, shape_conversion")
         raise NotImplementedError("Zarringhalam soft constraints are not implemented by the HIP engine")
 
+    def _long(self):
+        return len(self.sequence) > _lib.SF_MAX_W
+
     def mfe(self):
         self._eng = _check_md(self._model)
+        if self._long():
+            if self._sc is not None:
+                raise NotImplementedError("SHAPE soft constraints on a sequence longer than %d nt: the whole-record fold "
+                                          "(sf_fold_long) has no pseudo-energy term" % _lib.SF_MAX_W)
+            e, db = self._eng.fold_long(self.sequence, self._hc)
+            return db, _f32(e)
         if self._hc is not None or self._sc is not None:
             r = self._eng.fold_constrained([self.sequence], None if self._hc is None else [self._hc],
                                            None if self._sc is None else self._sc[None, :], pf=False)
@@ -97,6 +109,10 @@ class fold_compound:
         """-> (structure string, ensemble free energy).  The string is the centroid structure, not
         ViennaRNA's pair-propensity string (ScanFold discards it, ScanFold-Scan.py:383)."""
         self._eng = _check_md(self._model)
+        if self._long():
+            raise NotImplementedError("no partition function (and so no centroid / mean base-pair distance) for a sequence "
+                                      "longer than %d nt: only the MFE of a whole record is implemented (sf_fold_long)"
+                                      % _lib.SF_MAX_W)
         if self._sc is not None:
             raise NotImplementedError("partition function with SHAPE soft constraints (the reference calls fc.pf() "
                                       "before sc_add_SHAPE_*, ScanFold.py:525-539)")

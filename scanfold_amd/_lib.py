@@ -62,8 +62,31 @@ _EXPORTS = {
 EXPORTED_SYMBOLS = tuple(_EXPORTS)
 
 
+
+def _header_define(header, name):
+    """the integer value of `#define name` in include/<header>: the library's limits, read from the header it is compiled from"""
+    import re
+    path = os.path.join(os.path.dirname(_HERE), "include", header)
+    with open(path) as f:
+        m = re.search(r"^#define\s+%s\s+(\d+)\b" % name, f.read(), flags=re.M)
+    if m is None:
+        raise ScanFoldHipError("%s defines no %s" % (path, name))
+    return int(m.group(1))
+
+
+# include/scanfold_hip_long.h: bound only where the loaded library exports them (the CPU twin of the C ABI does not)
+_LONG_EXPORTS = {
+    "sf_fold_long": (ctypes.c_int, [_c_u8p, ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "sf_fold_long_times": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double)] * 3),
+}
+
+
 class ScanFoldHipError(RuntimeError):
     pass
+
+
+SF_MAX_W = _header_define("scanfold_hip.h", "SF_MAX_W")  # longest window of the window kernels
+SF_MAX_LONG = _header_define("scanfold_hip_long.h", "SF_MAX_LONG")  # longest sequence of sf_fold_long
 
 
 def _share_hip_runtime_with_torch():
@@ -99,6 +122,11 @@ def load_library(path=LIB_PATH):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
+    for name, (res, args) in _LONG_EXPORTS.items():
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.restype = res
+            fn.argtypes = args
     return lib
 
 
@@ -126,6 +154,7 @@ class Engine:
         self._check(self.lib.sf_init(int(device)))
         self.device = int(device)
         self.params = None
+        self.max_bp_span = 0  # what the last set_max_bp_span made resident (sf_init: no limit)
         self.load_params(paramset if paramset is not None else _params.default_params())
 
     # -- plumbing --
@@ -225,6 +254,38 @@ class Engine:
             out.update(dG=dG, mean_bp_dist=mbd, centroid=[bytes(r[:W]).decode() for r in cen], centroid_dist=cd)
         return out
 
+    def has_fold_long(self):
+        return getattr(self.lib, "sf_fold_long", None) is not None
+
+    def fold_long(self, seq, cons=None, structure=True):
+        """fc = RNA.fold_compound(seq, md); fc.hc_add_from_db(cons); fc.mfe() for ONE sequence of 1..SF_MAX_LONG nt
+        (ScanFold.py:1520-1539, --global_refold) -> (mfe_dcal, dot-bracket or None).  Raises ScanFoldHipError on a library
+        without the entry point (there is no fallback)."""
+        if not self.has_fold_long():
+            raise ScanFoldHipError("this library (%s) has no sf_fold_long: whole-record folds need libscanfold_hip.so"
+                                   % getattr(self.lib, "_name", "?"))
+        s = seq if isinstance(seq, (bytes, bytearray)) else str(seq).encode("ascii")
+        L = len(s)
+        c = None
+        if cons is not None:
+            c = cons if isinstance(cons, (bytes, bytearray)) else str(cons).encode("ascii")
+            if len(c) != L:
+                raise ValueError("constraint string and sequence differ in length")
+        arr = np.frombuffer(bytes(s), dtype=np.uint8) if L else np.zeros(1, dtype=np.uint8)
+        e = np.zeros(1, dtype=np.int32)
+        db = np.zeros(L + 1, dtype=np.uint8) if structure else None
+        self._check(self.lib.sf_fold_long(arr.ctypes.data, L, None if c is None else bytes(c), e.ctypes.data,
+                                          None if db is None else db.ctypes.data))
+        return int(e[0]), (bytes(db[:L]).decode() if structure else None)
+
+    def fold_long_times(self):
+        """-> (fill_ms, f5_ms, traceback_ms) of the last fold_long (device events)."""
+        if not self.has_fold_long():
+            raise ScanFoldHipError("this library has no sf_fold_long")
+        t = [ctypes.c_double() for _ in range(3)]
+        self._check(self.lib.sf_fold_long_times(*(ctypes.byref(x) for x in t)))
+        return tuple(x.value for x in t)
+
     def shuffle_windows(self, transcript, W, step, win_begin, n_win, r, kind, seed):
         tr = np.frombuffer(transcript.encode("ascii") if isinstance(transcript, str) else bytes(transcript),
                            dtype=np.uint8)
@@ -305,6 +366,7 @@ class Engine:
     def set_max_bp_span(self, span):
         """RNA.md().max_bp_span (ScanFold.py:214-215): pairs (i, j) with j - i + 1 > span do not exist; <= 0 = no limit."""
         self._check(self.lib.sf_set_max_bp_span(int(span or 0)))
+        self.max_bp_span = int(span or 0) if int(span or 0) > 0 else 0
 
     def prof_reset(self):
         self._check(self.lib.sf_prof_reset())

@@ -13,10 +13,12 @@
 #include <string>
 #include <vector>
 
+#include "../../include/scanfold_hip_long.h"
 #include "sf_launch.h"
 #include "sf_energy.h"
 #include "sf_mfe_full.hip.h"
 #include "sf_mfe_fast.hip.h"
+#include "sf_mfe_long.hip.h"
 #include "sf_pf.hip.h"
 #include "sf_pf_fast.hip.h"
 #include "sf_pf_lds.hip.h"
@@ -1017,6 +1019,146 @@ int sf_prof_get(double *ms, int64_t *launches, int64_t *folds) {
 int sf_prof_stop(void) {
   SF_ENTER();
   g.prof_on = false;
+  return SF_OK;
+}
+
+}  // extern "C"
+
+// ---------------- whole-record folds (include/scanfold_hip_long.h) ----------------
+namespace {
+double g_long_ms[3] = {0, 0, 0};  // fill, f5, traceback of the last sf_fold_long
+
+// Every device buffer of one long fold; all freed when it goes out of scope (after the stream has drained).
+struct LongBufs {
+  std::vector<void *> ptrs;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  ~LongBufs() {
+    hipStreamSynchronize(g.stream);
+    for (void *p : ptrs) hipFree(p);
+    for (hipEvent_t e : ev)
+      if (e) hipEventDestroy(e);
+  }
+  // hipMalloc that reports (and clears) an out-of-memory instead of leaving it for the next call's hipGetLastError
+  int alloc(void **p, size_t bytes, const char *what) {
+    *p = nullptr;
+    const hipError_t e = hipMalloc(p, bytes ? bytes : 1);
+    if (e != hipSuccess) {
+      hipGetLastError();
+      char b[512];
+      snprintf(b, sizeof b, "sf_fold_long: hipMalloc of %zu bytes (%s) failed: %s", bytes, what, hipGetErrorString(e));
+      g.last_hip_error = b;
+      *p = nullptr;
+      return SF_ERR_HIP;
+    }
+    ptrs.push_back(*p);
+    return SF_OK;
+  }
+};
+
+// lanes per cell of diagonal d: enough that no lane walks more than ~64 split terms, at most one wave
+int long_group(int d) {
+  int G = 1;
+  while (G < 64 && G * 64 < d) G *= 2;
+  return G;
+}
+}  // namespace
+
+extern "C" {
+
+int sf_fold_long(const uint8_t *seq, int L, const char *cons, int32_t *mfe_out, char *db_out) {
+  int rc = check_ready();
+  if (rc) return rc;
+  if (!seq || L < 1 || L > SF_MAX_LONG) return SF_ERR_BAD_ARG;
+  bool noncanonical = false;  // (a type-7 bracket pair needs nothing special here: the int32 tables carry it)
+  if (cons && (rc = scan_constraints(seq, cons, 1, L, &noncanonical))) return rc;
+  const sf_params_blob *P = (const sf_params_blob *)g.slot[g.cur].src.data();  // the resident set as it was handed in
+  std::vector<uint8_t> hS((size_t)L + 2, 0);
+  for (int x = 0; x < L; x++) hS[x + 1] = sf_encode_nt(seq[x]);
+  std::vector<int32_t> hhp((size_t)L + 1);
+  for (int s = 0; s <= L; s++) hhp[s] = (s <= 30) ? P->hairpin[s] : P->hairpin[30] + (int)(P->lxc * log(s / 30.));
+
+  int32_t e = 0;  // (outlives B: the copy into it is drained by B's destructor on an early return)
+  const size_t tri = SF_LONG_TRI(L);
+  LongBufs B;
+  SfLong F;
+  memset(&F, 0, sizeof F);
+  F.L = L;
+  void *p;
+  if ((rc = B.alloc(&p, tri * sizeof(int32_t), "c"))) return rc;
+  F.c = (int32_t *)p;
+  if ((rc = B.alloc(&p, tri * sizeof(int32_t), "fML"))) return rc;
+  F.fML = (int32_t *)p;
+  if ((rc = B.alloc(&p, tri * sizeof(int32_t), "fML transposed"))) return rc;
+  F.fMLt = (int32_t *)p;
+  if ((rc = B.alloc(&p, 3 * ((size_t)L + 2) * sizeof(int32_t), "DML ring"))) return rc;
+  F.dml = (int32_t *)p;
+  if ((rc = B.alloc(&p, ((size_t)L + 1) * sizeof(int32_t), "f5"))) return rc;
+  F.f5 = (int32_t *)p;
+  if ((rc = B.alloc(&p, SF_LONG_STACK_INTS(L) * sizeof(int32_t), "traceback stack"))) return rc;
+  F.stk = (int32_t *)p;
+  if ((rc = B.alloc(&p, (size_t)L + 1, "structure"))) return rc;
+  F.db = (char *)p;
+  if ((rc = B.alloc(&p, (size_t)L + 2, "sequence"))) return rc;
+  F.S = (const uint8_t *)p;
+  HIPCHK(hipMemcpyAsync(p, hS.data(), (size_t)L + 2, hipMemcpyHostToDevice, g.stream));
+  if ((rc = B.alloc(&p, ((size_t)L + 1) * sizeof(int32_t), "hairpin table"))) return rc;
+  F.hp = (const int32_t *)p;
+  HIPCHK(hipMemcpyAsync(p, hhp.data(), ((size_t)L + 1) * sizeof(int32_t), hipMemcpyHostToDevice, g.stream));
+  if ((rc = B.alloc(&p, sizeof(int32_t), "energy"))) return rc;
+  int32_t *d_mfe = (int32_t *)p;
+  F.status = (int *)g.status.p;
+  F.hc.c = nullptr;
+  if (cons) {
+    void *src, *hc, *part, *encl, *stack;
+    if ((rc = B.alloc(&src, (size_t)L, "constraint"))) return rc;
+    if ((rc = B.alloc(&hc, (size_t)L + 2, "constraint"))) return rc;
+    if ((rc = B.alloc(&part, ((size_t)L + 2) * sizeof(int16_t), "bracket partners"))) return rc;
+    if ((rc = B.alloc(&encl, ((size_t)L + 2) * sizeof(int16_t), "enclosing pairs"))) return rc;
+    if ((rc = B.alloc(&stack, ((size_t)L + 2) * sizeof(int16_t), "bracket stack"))) return rc;
+    HIPCHK(hipMemcpyAsync(src, cons, (size_t)L, hipMemcpyHostToDevice, g.stream));
+    SF_LAUNCH(sf_long_hc_kernel, 1, 64, 0, g.stream, (const char *)src, L, (char *)hc, (int16_t *)part, (int16_t *)encl,
+              (int16_t *)stack, (int *)g.status.p);
+    HIPCHK(hipGetLastError());
+    F.hc.c = (const char *)hc;
+    F.hc.partner = (const int16_t *)part;
+    F.hc.encl = (const int16_t *)encl;
+  }
+  for (auto &e : B.ev) HIPCHK(hipEventCreate(&e));
+  const SfDevParams *D = (const SfDevParams *)g.dP;
+  const int threads = 256;
+  HIPCHK(hipEventRecord(B.ev[0], g.stream));
+  for (int d = 0; d < L; d++) {
+    const int G = long_group(d);
+    const size_t total = (size_t)(L - d) * (size_t)G;
+    const int grid = (int)((total + threads - 1) / threads);
+    SF_LAUNCH(sf_long_fill_kernel, grid, threads, 0, g.stream, F, d, G, D);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(B.ev[1], g.stream));
+  SF_LAUNCH(sf_long_f5_kernel, 1, threads, 0, g.stream, F, D, d_mfe);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(B.ev[2], g.stream));
+  if (db_out) {
+    SF_LAUNCH(sf_long_trace_kernel, 1, threads, 0, g.stream, F, D);
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipEventRecord(B.ev[3], g.stream));
+  HIPCHK(hipMemcpyAsync(&e, d_mfe, sizeof e, hipMemcpyDeviceToHost, g.stream));
+  if (db_out) HIPCHK(hipMemcpyAsync(db_out, F.db, (size_t)L + 1, hipMemcpyDeviceToHost, g.stream));
+  if ((rc = read_status(g.stream, false))) return rc;
+  if (mfe_out) *mfe_out = e;
+  float ms[3] = {0, 0, 0};
+  for (int k = 0; k < 3; k++) HIPCHK(hipEventElapsedTime(&ms[k], B.ev[k], B.ev[k + 1]));
+  for (int k = 0; k < 3; k++) g_long_ms[k] = ms[k];
+  if (!db_out) g_long_ms[2] = 0.0;
+  return SF_OK;
+}
+
+int sf_fold_long_times(double *fill_ms, double *f5_ms, double *trace_ms) {
+  SF_ENTER();
+  if (fill_ms) *fill_ms = g_long_ms[0];
+  if (f5_ms) *f5_ms = g_long_ms[1];
+  if (trace_ms) *trace_ms = g_long_ms[2];
   return SF_OK;
 }
 

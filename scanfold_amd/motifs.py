@@ -17,8 +17,9 @@ Reproduced as they are upstream:
  * '<' counts as a start where the nesting depth is 1 and '>' as an end where it is 0;
  * the motif's z-score uses the UNCONSTRAINED energy of the motif and the run's shuffle type (upstream defines
    sub_shuffle = "mono" and never uses it).
-Not reproduced: the PostScript plot (RNA.PS_rna_plot_a) and the full-length "global refold" of the input sequence
-(ScanFold.py:1510-1549: one O(L^3) fold of the whole transcript — a different kernel from the window scan).
+Not reproduced: the PostScript plot (RNA.PS_rna_plot_a).  The full-length "global refold" of the input sequence
+(ScanFold.py:1510-1549: one O(L^3) fold of the whole transcript, a different kernel from the window scan) is
+scanfold_amd.scanfold.global_refold over sf_fold_long.
 """
 from . import RNA
 from . import functions as sff

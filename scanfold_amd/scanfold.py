@@ -10,7 +10,10 @@ and then feeds the windows straight into the Fold stage (scanfold_amd.fold; Scan
 TSV round trip; the pair tabulation of that stage runs on the GPU (sf_tabulate_pairs).  Output: `<name>.win_W.stp_S.rnd_R.shfl_T.out` (the scan table, ScanFold.py:381,685) and the Fold
 stage's files with the prefix `<that>.ScanFold.`, then the dot-bracket files (makedbn) and the motif extraction /
 refolds of ScanFold.py:1582-1776 (scanfold_amd.motifs: `<that>.ExtractedStructures.gff3`, `<that>_motif_<n>.dbn/.ct`).
-ScanFold.py's per-record directories, IGV wig exports and the full-length global refold are not reproduced.
+--global_refold folds the whole record three times after the dbn files are written (ScanFold.py:1509-1547): unconstrained,
+then with the -1 and the -2 filter's dot-bracket lines as hard constraints, through the RNA facade (whole-record folds,
+sf_fold_long), into `<that>.<--dbn_file_path>` and `<that>.AllDBN.txt`.  ScanFold.py's per-record directories and IGV
+wig exports are not reproduced.
 """
 import argparse
 import os
@@ -144,6 +147,57 @@ def read_reactivities(path):
     return vec
 
 
+def global_refold(seq, name, outname, temperature, dbn_file_path="AllDBN-global_refold.txt"):
+    """ScanFold.py:1509-1547 (--global_refold): a fresh RNA.md() at md.temperature = int(-t) — no --span, exactly as
+    upstream — folds the whole record unconstrained and with line 3 of `<outname>.ScanFold.-1.dbn` / `.-2.dbn` as
+    hc_add_from_db constraint, and writes the three records to `<outname>.<dbn_file_path>`; `<outname>.AllDBN.txt` is the
+    three dbn files concatenated (upstream's `cat`).  Upstream hands the constraint line over with its trailing newline;
+    what ViennaRNA makes of that extra character could not be checked against ViennaRNA itself, so it is stripped here
+    (the constraint is exactly as long as the record).  The dbn files cover the scanned stretch only, positions 1 .. the
+    last window's end; when the windows stop short of the record's end the line is padded with '.' (no ScanFold pair
+    there, so no constraint) to the record's length.
+    The engine's model (base-pair span, temperature, and the RNA facade's record of the span) is put back exactly as it
+    was, also when a fold raises: the stages after this one, and the next records, fold as they would without the flag."""
+    from . import RNA
+    md = RNA.md()
+    md.temperature = int(temperature)
+    cons = []
+    for tag in ("-1", "-2"):
+        with open(outname + ".ScanFold." + tag + ".dbn") as f:
+            line = f.readlines()[2].rstrip("\r\n")
+        cons.append(line + "." * max(0, len(seq) - len(line)))
+    eng = _lib.get_engine()
+    span0, params0 = eng.max_bp_span, eng.params
+    had_facade_span, facade_span0 = hasattr(eng, "_span"), getattr(eng, "_span", 0)
+    try:
+        eng.set_max_bp_span(0)  # (the scan's --span is engine state; the fresh md has none)
+        eng._span = 0
+        fc = RNA.fold_compound(seq, md)
+        fc.hc_add_from_db(cons[0])
+        s1, e1 = fc.mfe()
+        fc = RNA.fold_compound(seq, md)
+        fc.hc_add_from_db(cons[1])
+        s2, e2 = fc.mfe()
+        s0, e0 = RNA.fold_compound(seq, md).mfe()
+    finally:
+        if eng.params is not params0:
+            eng._load(params0)
+            eng.params = params0
+        eng.set_max_bp_span(span0)
+        if had_facade_span:
+            eng._span = facade_span0
+        else:
+            del eng._span
+    with open(outname + "." + dbn_file_path, "w") as w:
+        w.write(">" + str(name) + "\tGlobal Full MFE=" + str(e0) + "\n" + seq + "\n" + s0 + "\n")
+        w.write(">" + str(name) + "\tRefolded with -1 constraints MFE=" + str(e1) + "\n" + seq + "\n" + s1 + "\n")
+        w.write(">" + str(name) + "\tRefolded with -2 constraints MFE=" + str(e2) + "\n" + seq + "\n" + s2 + "\n")
+    with open(outname + ".AllDBN.txt", "w") as w:
+        for tag in ("no_filter", "-1", "-2"):
+            with open(outname + ".ScanFold." + tag + ".dbn") as f:
+                w.write(f.read())
+
+
 def build_parser():
     p = argparse.ArgumentParser(description="ScanFold (scan + fold) on the MI355X HIP engine")
     p.add_argument('filename', type=str, help='input fasta')
@@ -165,6 +219,10 @@ def build_parser():
     p.add_argument('--algo', type=str, default='rnafold')
     p.add_argument('--constraints', type=str, help='optional | input constraint file')
     p.add_argument('--span', type=int, help='Max bp span')
+    p.add_argument('--global_refold', action='store_true',
+                   help='Global refold option. Refold full sequence using Zavg <-1 and <-2 base pairs')
+    p.add_argument('--dbn_file_path', type=str, default="AllDBN-global_refold.txt",
+                   help='file name (after the output prefix) of the global refold records')
     p.add_argument('--dont_fold', action='store_true', help='scan only')
     p.add_argument('--dont_extract', action='store_true', help='no motif extraction / refolds after the Fold stage')
     p.add_argument('--seed', type=int, default=0)
@@ -179,6 +237,9 @@ def main(argv=None):
         raise NameError("name 'RNAstructure' is not defined")  # upstream's rnastructure backend is never imported (ScanFold.py:40,439)
     if args.c not in (0, 1):
         raise ValueError("-c must be 1 (no competition allowed) or 0 (competition allowed)")
+    if args.global_refold and (args.c == 0 or args.dont_fold):
+        # upstream scans first and then fails on the dbn files those modes never write
+        raise ValueError("--global_refold refolds with the -1 / -2 dbn files of the Fold stage: not with -c 0 or --dont_fold")
     from . import params as _params
     eng = _lib.get_engine()
     eng.set_max_bp_span(args.span or 0)
@@ -228,6 +289,9 @@ def main(argv=None):
             writers.write_wig(zlist, step, args.name, outname + ".scan-zscores.wig")
             writers.write_wig(table.pvalues, step, args.name, outname + ".scan-pvalue.wig")
             writers.write_wig(table.ed.tolist(), step, args.name, outname + ".scan-ED.wig")
+            if args.global_refold:
+                print("Refolding full sequence using ScanFold results as constraints...")
+                global_refold(seq, args.name, outname, args.t, args.dbn_file_path)
             if args.c == 1 and not args.dont_extract:
                 with open(outname + ".ScanFold.-2.dbn") as f:
                     line = f.readlines()[2]
