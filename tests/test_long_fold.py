@@ -1,6 +1,7 @@
 """Whole-record folds past the window limit (sf_fold_long, include/scanfold_hip_long.h): the kernel source compiled for the
 CPU against the oracle, the RNA facade's routing of long sequences, and the combined driver's --global_refold
 (ScanFold.py:1509-1547)."""
+import contextlib
 import ctypes
 import os
 import random
@@ -11,6 +12,8 @@ import pytest
 from scanfold_amd import _lib, params
 from scanfold_amd import RNA
 from scanfold_amd import scanfold as sfd
+from long_util import (PAIRS, formed_type7, hairpin_record, multiloop_rich, rand_seq, separated_record, short_hairpin_params,
+                       with_oracle_constraint)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -23,23 +26,11 @@ def emul():
     return e
 
 
-def rand_seq(rng, L):
-    return "".join("ACGU"[k] for k in rng.integers(0, 4, L))
-
-
 def planted_stem(rng, L, n_stem=12, loop_at=None):
     """a random sequence whose first and last n_stem bases form a perfect helix around the rest"""
     s = rand_seq(rng, n_stem)
     comp = s[::-1].translate(str.maketrans("ACGU", "UGCA"))
     return s + rand_seq(rng, L - 2 * n_stem) + comp
-
-
-def with_oracle_constraint(oracle, cons, fn):
-    oracle.set_constraint(cons)
-    try:
-        return fn()
-    finally:
-        oracle.set_constraint(None)
 
 
 @pytest.mark.parametrize("L", [1, 4, 57, 401, 433])
@@ -62,10 +53,9 @@ def constraint_string(s, rng):
     c = ["."] * L
     for k in rng.choice(L, max(4, L // 10), replace=False):
         c[k] = "<>x"[k % 3]
-    pairs = {("A", "U"), ("U", "A"), ("G", "C"), ("C", "G"), ("G", "U"), ("U", "G")}
-    a = next(i for i in range(2, L // 4) if (s[i], s[L - 1 - i]) not in pairs)  # type 7
+    a = next(i for i in range(2, L // 4) if (s[i], s[L - 1 - i]) not in PAIRS)  # type 7
     c[a], c[L - 1 - a] = "(", ")"
-    b, j = next((i, j) for i in range(a + 3, L // 2) for j in range(i + 10, min(i + 40, L - 2 - a)) if (s[i], s[j]) in pairs)
+    b, j = next((i, j) for i in range(a + 3, L // 2) for j in range(i + 10, min(i + 40, L - 2 - a)) if (s[i], s[j]) in PAIRS)
     c[b], c[j] = "(", ")"
     return "".join(c)
 
@@ -92,6 +82,72 @@ def test_span_equals_oracle(emul, oracle):
     finally:
         emul.set_max_bp_span(0)
         oracle.set_max_bp_span(0)
+
+
+@contextlib.contextmanager
+def params_in(oracle, engine, p):
+    oracle.set_params(p)
+    engine.load_params(p)
+    try:
+        yield
+    finally:
+        oracle.set_params(params.default_params())
+        engine.load_params(params.default_params())
+
+
+@pytest.mark.parametrize("kind", ["N", "x"])
+@pytest.mark.parametrize("short_hairpins", [False, True])
+def test_separated_blocks_fold_as_the_whole_record(oracle, kind, short_hairpins):
+    """The premise of long_util.separated_record, proved on every run: the oracle's fold of the whole record equals the sum
+    of its block folds in energy and their join in structure, for both separator kinds, with bracket pairs (one of them
+    type 7), '<' / '>' / 'x' marks inside blocks and, for 'x' separators, the bracket pair (1, L) the span forbids; with the
+    default set and with multiloop-rich blocks under short_hairpin_params."""
+    S = 60
+    cons_blocks, outer = ((1, 4), False) if kind == "N" else ((0, 2, 4), True)
+    if short_hairpins:
+        oracle.set_params(short_hairpin_params())
+    try:
+        seq, cons, e, db = separated_record(oracle, [180, 250, 200, 190, 230], kind, S, 41, cons_blocks=cons_blocks,
+                                            outer_pair=outer, fill=multiloop_rich if short_hairpins else rand_seq)
+        assert len(seq) == 1290 and cons and set("()<>x") <= set(cons)
+        assert formed_type7(seq, cons, db)
+        oracle.set_max_bp_span(S)
+        try:
+            assert with_oracle_constraint(oracle, cons, lambda: oracle.mfe(seq)) == (db, e)
+        finally:
+            oracle.set_max_bp_span(0)
+    finally:
+        oracle.set_params(params.default_params())
+
+
+def test_separated_record_on_the_emulated_kernel(emul, oracle):
+    """sf_fold_long (CPU build) on separated records of 410 nt: three blocks, span 40, N separators without a constraint and
+    'x' separators with bracket pairs, marks and the forbidden pair (1, L).  The blocks are multiloop_rich under
+    short_hairpin_params, so the multiloop splits need their first and last k."""
+    S = 40
+    emul.set_max_bp_span(S)
+    try:
+        with params_in(oracle, emul, short_hairpin_params()):
+            seq, cons, e, db = separated_record(oracle, [110, 120, 100], "N", S, 3, fill=multiloop_rich)
+            assert cons is None and "N" * S in seq
+            assert emul.fold_long(seq) == (e, db)
+            seq, cons, e, db = separated_record(oracle, [110, 120, 100], "x", S, 4, cons_blocks=(0, 2), outer_pair=True,
+                                                fill=multiloop_rich)
+            assert formed_type7(seq, cons, db)
+            assert emul.fold_long(seq, cons) == (e, db)
+    finally:
+        emul.set_max_bp_span(0)
+
+
+@pytest.mark.parametrize("s", [401, 402, 403])
+def test_hairpin_at_the_end_of_the_window_table(emul, oracle, s):
+    """A hairpin of size s closed by a bracketed G-C stem: 401 is the last size of the resident model's table (hp_init), 402
+    the first one the kernel reads from the host-built table of the call."""
+    seq, cons, db = hairpin_record(np.random.default_rng(s), s, flank=5)
+    assert len(seq) <= 433
+    odb, e = with_oracle_constraint(oracle, cons, lambda: oracle.mfe(seq))
+    assert odb == db
+    assert emul.fold_long(seq, cons) == (e, db)
 
 
 def test_bad_arguments(emul):
