@@ -10,12 +10,15 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.path.join(_HERE, "libsf_oracle.so")
+_LIB_LONG = os.path.join(_HERE, "libsf_oracle_long.so")  # sf_oracle.c with long double accumulators (SF_ORACLE_LONG)
 _lib = None
+_lib_long = None
 
 
 def build(force=False):
     srcs = [os.path.join(_HERE, f) for f in os.listdir(_HERE) if f.endswith(".c")]  # sf_cpu_twin.c is #included by sf_oracle.c
-    if force or not os.path.exists(_LIB) or os.path.getmtime(_LIB) < max(os.path.getmtime(f) for f in srcs):
+    newest = max(os.path.getmtime(f) for f in srcs)
+    if force or any(not os.path.exists(x) or os.path.getmtime(x) < newest for x in (_LIB, _LIB_LONG)):
         subprocess.check_call(["make", "-C", _HERE, "-s"])
 
 
@@ -79,7 +82,26 @@ def lib():
     return _lib
 
 
-def _bind(L):
+def lib_long():
+    """The high-precision reference: the oracle's recurrences on long double, unscaled (its own parameter tables: call
+    set_params(p, L=lib_long())).  Only the single-sequence entry points (pf, brute, constraints) are used from it."""
+    global _lib_long
+    if _lib_long is None:
+        if not os.path.exists(_LIB_LONG):
+            build()
+        _lib_long = _bind_common(ctypes.CDLL(_LIB_LONG))
+    return _lib_long
+
+
+def _lib_for(precision):
+    if precision == "double":
+        return lib()
+    if precision == "long":
+        return lib_long()
+    raise ValueError("precision must be 'double' or 'long', not %r" % (precision,))
+
+
+def _bind_common(L):
     L.sfo_set_params.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
     L.sfo_set_params_exact.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_char_p]
     L.sfo_mfe.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_char_p]
@@ -90,11 +112,18 @@ def _bind(L):
                             ctypes.POINTER(ctypes.c_longlong)]
     L.sfo_pf.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_void_p,
                          ctypes.c_char_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
+    L.sfo_brute_dG.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_void_p]
+    L.sfo_pf_unscaled.argtypes = [ctypes.c_char_p, ctypes.c_int] + [ctypes.POINTER(ctypes.c_double)] * 4
+    L.sfo_set_constraint.argtypes = [ctypes.c_char_p, ctypes.c_void_p]
+    return L
+
+
+def _bind(L):
+    _bind_common(L)
     L.sfo_scan_windows.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
     L.sfo_twin_scan_windows.argtypes = L.sfo_scan_windows.argtypes
     L.sfo_twin_mfe_batch.argtypes = L.sfo_mfe_batch.argtypes
-    L.sfo_set_constraint.argtypes = [ctypes.c_char_p, ctypes.c_void_p]
     L.sfo_shuffle_windows.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                       ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_void_p]
     return L
@@ -115,16 +144,17 @@ def set_max_bp_span(span):
     lib().sfo_set_max_bp_span(int(span or 0))
 
 
-_keep = []
+_keep = {}
 
 
-def set_constraint(cons=None, sc_stack_dcal=None):
+def set_constraint(cons=None, sc_stack_dcal=None, precision="double"):
     """fc.hc_add_from_db(cons) / fc.sc_add_SHAPE_deigan pseudo-energies (int dcal per nucleotide, stacks only) for the
-    following single-sequence calls (mfe, eval_structure, brute, pf); None, None clears.  See sf_oracle.c."""
+    following single-sequence calls (mfe, eval_structure, brute, pf) of that precision's library; None, None clears.
+    See sf_oracle.c."""
     c = cons.encode() if isinstance(cons, str) else cons
     s = None if sc_stack_dcal is None else np.ascontiguousarray(sc_stack_dcal, dtype=np.int32)
-    _keep[:] = [c, s]  # the C side keeps the pointers
-    lib().sfo_set_constraint(c, None if s is None else s.ctypes.data)
+    _keep[precision] = [c, s]  # the C side keeps the pointers
+    _lib_for(precision).sfo_set_constraint(c, None if s is None else s.ctypes.data)
 
 
 def mfe(seq, structure=True):
@@ -159,8 +189,17 @@ def eval_structure(seq, db):
     return e.value
 
 
-def brute(seq, want_bpp=False):
+def brute(seq, want_bpp=False, precision="double"):
+    """-> (mfe dcal, Z, bpp, count) in double; precision="long" -> dict(dG, bpp) from the long-double sum (its Z
+    would not fit a double)"""
     n = len(seq)
+    if precision != "double":
+        dG = ctypes.c_double()
+        bpp = np.zeros((n + 1, n + 1)) if want_bpp else None
+        rc = _lib_for(precision).sfo_brute_dG(seq.encode(), n, ctypes.byref(dG), bpp.ctypes.data if want_bpp else None)
+        if rc:
+            raise RuntimeError("sfo_brute_dG rc=%d" % rc)
+        return dict(dG=dG.value, bpp=bpp)
     e = ctypes.c_int()
     Z = ctypes.c_double()
     cnt = ctypes.c_longlong()
@@ -172,19 +211,29 @@ def brute(seq, want_bpp=False):
     return e.value, Z.value, bpp, cnt.value
 
 
-def pf(seq, want_bpp=False):
-    """-> dict(dG, centroid, centroid_dist, mean_bp_dist, bpp)"""
+def pf(seq, want_bpp=False, precision="double"):
+    """-> dict(dG, centroid, centroid_dist, mean_bp_dist, bpp).  precision="double": the FP64 oracle, scaled per
+    nucleotide where the fold needs it; "long": the unscaled long-double reference (lib_long)."""
     n = len(seq)
     dG = ctypes.c_double()
     cd = ctypes.c_double()
     mbd = ctypes.c_double()
     cen = ctypes.create_string_buffer(n + 1)
     bpp = np.zeros((n + 1, n + 1)) if want_bpp else None
-    rc = lib().sfo_pf(seq.encode(), n, ctypes.byref(dG), bpp.ctypes.data if want_bpp else None, cen,
+    rc = _lib_for(precision).sfo_pf(seq.encode(), n, ctypes.byref(dG), bpp.ctypes.data if want_bpp else None, cen,
                       ctypes.byref(cd), ctypes.byref(mbd))
     if rc:
         raise RuntimeError("sfo_pf rc=%d" % rc)
     return dict(dG=dG.value, centroid=cen.value.decode(), centroid_dist=cd.value, mean_bp_dist=mbd.value, bpp=bpp)
+
+
+def pf_unscaled(seq, precision="double"):
+    """The fold with scale 1, whatever its range: -> dict(dG, centroid_dist, mean_bp_dist, lnZ)"""
+    v = [ctypes.c_double() for _ in range(4)]
+    rc = _lib_for(precision).sfo_pf_unscaled(seq.encode(), len(seq), *[ctypes.byref(x) for x in v])
+    if rc:
+        raise RuntimeError("sfo_pf_unscaled rc=%d" % rc)
+    return dict(dG=v[0].value, centroid_dist=v[1].value, mean_bp_dist=v[2].value, lnZ=v[3].value)
 
 
 def scan_windows(rows, n_win, r, nthreads=0):

@@ -24,7 +24,7 @@ typedef struct {
   int cap; /* sequence length the buffers are sized for */
   int *c, *ci, *fML, *fMLT, *DML, *f5;
   unsigned char *pt;
-  double *qb, *qm, *qm1, *ob, *obw, *a0, *a1, *q5, *q3, *mlb;
+  double *qb, *qm, *qm1, *ob, *obw, *a0, *a1, *q5, *q3, *mlb, *sc;
 } twin_ws;
 
 static _Thread_local twin_ws TW = {0};
@@ -33,7 +33,7 @@ static void twin_reserve(int n) {
   if (TW.cap >= n) return;
   free(TW.c); free(TW.ci); free(TW.fML); free(TW.fMLT); free(TW.DML); free(TW.f5); free(TW.pt);
   free(TW.qb); free(TW.qm); free(TW.qm1); free(TW.ob); free(TW.obw); free(TW.a0); free(TW.a1);
-  free(TW.q5); free(TW.q3); free(TW.mlb);
+  free(TW.q5); free(TW.q3); free(TW.mlb); free(TW.sc);
   const size_t sz = (size_t)(n + 2) * (size_t)(n + 2);
   TW.c = (int *)malloc(sz * sizeof(int)); TW.ci = (int *)malloc(sz * sizeof(int)); TW.fML = (int *)malloc(sz * sizeof(int));
   TW.fMLT = (int *)malloc(sz * sizeof(int)); TW.DML = (int *)malloc(sz * sizeof(int));
@@ -44,7 +44,7 @@ static void twin_reserve(int n) {
   TW.obw = (double *)malloc(sz * sizeof(double)); TW.a0 = (double *)malloc(sz * sizeof(double));
   TW.a1 = (double *)malloc(sz * sizeof(double));
   TW.q5 = (double *)malloc((size_t)(n + 3) * sizeof(double)); TW.q3 = (double *)malloc((size_t)(n + 3) * sizeof(double));
-  TW.mlb = (double *)malloc((size_t)(n + 3) * sizeof(double));
+  TW.mlb = (double *)malloc((size_t)(n + 3) * sizeof(double)); TW.sc = (double *)malloc((size_t)(n + 3) * sizeof(double));
   TW.cap = n;
 }
 
@@ -169,26 +169,28 @@ static int twin_traceback(const seq_t *q, char *db) {
   return mfe_traceback(q, &t, db);
 }
 
-/* McCaskill inside / outside -> centroid, mean bp distance, ensemble free energy */
-static void twin_pf(const seq_t *q, char *centroid, double *mean_bp_dist, double *ens_dG) {
+/* McCaskill inside / outside -> centroid, mean bp distance, ensemble free energy; scaled by e^lns per nucleotide as
+ * sfo_pf is (sc[k] = s^-k on every weight that covers k new nucleotides).  Returns ln Z_s. */
+static double twin_pf_run(const seq_t *q, double lns, char *centroid, double *mean_bp_dist, double *ens_dG) {
   const int n = q->n;
   const int *S = q->S;
   const unsigned char *pt = TW.pt;
   double *qb = TW.qb, *qm = TW.qm, *qm1 = TW.qm1, *ob = TW.ob, *obw = TW.obw, *A0 = TW.a0, *A1 = TW.a1;
-  double *q5 = TW.q5, *q3 = TW.q3, *mlb = TW.mlb;
+  double *q5 = TW.q5, *q3 = TW.q3, *mlb = TW.mlb, *sc = TW.sc;
   const size_t sz = (size_t)(n + 2) * (size_t)(n + 2);
   memset(qb, 0, sz * sizeof(double)); memset(qm, 0, sz * sizeof(double)); memset(qm1, 0, sz * sizeof(double));
   memset(ob, 0, sz * sizeof(double)); memset(obw, 0, sz * sizeof(double));
   memset(A0, 0, sz * sizeof(double)); memset(A1, 0, sz * sizeof(double));
+  for (int k = 0; k <= n + 1; k++) sc[k] = exp(-lns * k);
   mlb[0] = 1.0;
-  for (int k = 1; k <= n + 1; k++) mlb[k] = mlb[k - 1] * XP->MLbase;
+  for (int k = 1; k <= n + 1; k++) mlb[k] = mlb[k - 1] * XP->MLbase * sc[1];
   for (int d = TURN + 1; d < n; d++) {
     for (int i = 1; i + d <= n; i++) {
       const int j = i + d;
       const int type = pt[TX(i, j)];
       double qbij = 0.0;
       if (type) {
-        double z = X_hairpin(d - 1, type, S[i + 1], S[j - 1], q->str + i - 1);
+        double z = X_hairpin(d - 1, type, S[i + 1], S[j - 1], q->str + i - 1) * sc[d + 1];
         const int si1 = S[i + 1], sj1 = S[j - 1];
         const int pmax = MIN2(j - 2 - TURN, i + MAXLOOP + 1);
         for (int p = i + 1; p <= pmax; p++) {
@@ -200,16 +202,16 @@ static void twin_pf(const seq_t *q, char *centroid, double *mean_bp_dist, double
           for (int qq = j - 1; qq >= minq; qq--) {
             const int t2 = ptp[qq];
             if (!t2) continue;
-            z += X_intloop(u1, j - qq - 1, type, rtype[t2], si1, sj1, sp1, S[qq + 1]) * qbp[qq];
+            z += X_intloop(u1, j - qq - 1, type, rtype[t2], si1, sj1, sp1, S[qq + 1]) * qbp[qq] * sc[u1 + j - qq + 1];
           }
         }
         double ml = 0.0;
         for (int u = i + 2 + TURN; u <= j - 1 - TURN - 1; u++) ml += qm[TX(i + 1, u - 1)] * qm1[TX(u, j - 1)];
-        z += ml * XP->MLclosing * X_mlstem(rtype[type], sj1, si1);
+        z += ml * XP->MLclosing * X_mlstem(rtype[type], sj1, si1) * sc[2];
         qbij = z;
       }
       qb[TX(i, j)] = qbij;
-      double m1 = qm1[TX(i, j - 1)] * XP->MLbase;
+      double m1 = qm1[TX(i, j - 1)] * XP->MLbase * sc[1];
       if (type) m1 += qbij * X_mlstem(type, ml_nb5(q, i), ml_nb3(q, j));
       qm1[TX(i, j)] = m1;
       double m = m1; /* u == i */
@@ -219,7 +221,7 @@ static void twin_pf(const seq_t *q, char *centroid, double *mean_bp_dist, double
   }
   q5[0] = 1.0;
   for (int j = 1; j <= n; j++) {
-    double z = q5[j - 1];
+    double z = q5[j - 1] * sc[1];
     for (int i = 1; i + TURN + 1 <= j; i++) {
       const int type = pt[TX(i, j)];
       if (type) z += q5[i - 1] * qb[TX(i, j)] * X_extloop(type, ml_nb5(q, i), ml_nb3(q, j));
@@ -228,7 +230,7 @@ static void twin_pf(const seq_t *q, char *centroid, double *mean_bp_dist, double
   }
   q3[n + 1] = 1.0;
   for (int i = n; i >= 1; i--) {
-    double z = q3[i + 1];
+    double z = q3[i + 1] * sc[1];
     for (int j = i + TURN + 1; j <= n; j++) {
       const int type = pt[TX(i, j)];
       if (type) z += qb[TX(i, j)] * X_extloop(type, ml_nb5(q, i), ml_nb3(q, j)) * q3[j + 1];
@@ -236,14 +238,14 @@ static void twin_pf(const seq_t *q, char *centroid, double *mean_bp_dist, double
     q3[i] = z;
   }
   const double Z = q5[n];
-  if (ens_dG) *ens_dG = -log(Z) * XP->kT / 1000.0;
+  if (ens_dG) *ens_dG = -(log(Z) + lns * n) * XP->kT / 1000.0;
   /* outside, widest pairs first; A0 / A1 are indexed by the cell (i, l): sums over closers (k, l), k < i */
   for (int d = n - 1; d >= TURN + 1; d--) {
     for (int i = 1; i + d <= n; i++) {
       const int j = i + d;
       double a0 = 0.0, a1 = 0.0;
       if (i > 1) {
-        a0 = A0[TX(i - 1, j)] * XP->MLbase + obw[TX(i - 1, j)];
+        a0 = A0[TX(i - 1, j)] * XP->MLbase * sc[1] + obw[TX(i - 1, j)];
         for (int k = 1; k <= i - 2 - TURN - 1; k++) a1 += obw[TX(k, j)] * qm[TX(k + 1, i - 1)];
       }
       A0[TX(i, j)] = a0;
@@ -261,7 +263,7 @@ static void twin_pf(const seq_t *q, char *centroid, double *mean_bp_dist, double
           for (int l = j + 1; l <= n && (l - j - 1) + u1 <= MAXLOOP; l++) {
             const int tk = ptk[l];
             if (!tk || obk[l] == 0.0) continue;
-            o += obk[l] * X_intloop(u1, l - j - 1, tk, rt, S[k + 1], S[l - 1], sp1, sq1);
+            o += obk[l] * X_intloop(u1, l - j - 1, tk, rt, S[k + 1], S[l - 1], sp1, sq1) * sc[u1 + l - j + 1];
           }
         }
         double mlsum = 0.0;
@@ -272,7 +274,7 @@ static void twin_pf(const seq_t *q, char *centroid, double *mean_bp_dist, double
         o += mlsum * X_mlstem(type, sp1, sq1);
       }
       ob[TX(i, j)] = o;
-      obw[TX(i, j)] = o * XP->MLclosing * X_mlstem(rtype[type], S[j - 1], S[i + 1]);
+      obw[TX(i, j)] = o * XP->MLclosing * X_mlstem(rtype[type], S[j - 1], S[i + 1]) * sc[2];
     }
   }
   double mbd = 0.0;
@@ -287,8 +289,19 @@ static void twin_pf(const seq_t *q, char *centroid, double *mean_bp_dist, double
       if (p > 0.5 && centroid) { centroid[i - 1] = '('; centroid[j - 1] = ')'; }
     }
   if (mean_bp_dist) *mean_bp_dist = 2.0 * mbd;
+  return log(Z);
 }
 #undef TX
+
+/* rescaled as sfo_pf: ln Z past SF_PF_LNZ_MAX redoes the fold with lns raised by ln Z_s / n (700 / n where not finite) */
+static void twin_pf(const seq_t *q, char *centroid, double *mean_bp_dist, double *ens_dG) {
+  double lns = 0.0;
+  for (int attempt = 0; attempt < 40; attempt++) {
+    const double lz = twin_pf_run(q, lns, centroid, mean_bp_dist, ens_dG);
+    if (lz <= SF_PF_LNZ_MAX) break;
+    lns += (isfinite(lz) ? lz : 700.0) / q->n;
+  }
+}
 
 /* Same contract as sfo_scan_windows: rows = n_win * (r+1) sequences of W characters; native row: MFE + traceback +
  * partition function, shuffle rows: MFE only.  One OpenMP thread per window. */

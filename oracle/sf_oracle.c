@@ -37,6 +37,27 @@
 #include "../include/sf_params_blob.h"
 
 #define INF SF_INF
+
+/* Accumulator type of the Boltzmann weights.  The default build is FP64, like the kernels, and scales a fold whose
+ * partition function passes SF_PF_LNZ_MAX (sfo_pf).  Built with -DSF_ORACLE_LONG (libsf_oracle_long.so) the same
+ * recurrences run on x87 long double (ln of its largest value ~11356) without any scaling: the high-precision
+ * reference the scaled FP64 folds are tested against. */
+#ifdef SF_ORACLE_LONG
+typedef long double sf_real;
+#define SF_EXP expl
+#define SF_LOG logl
+#define SF_POW powl
+#define SF_PF_RESCALE 0
+#else
+typedef double sf_real;
+#define SF_EXP exp
+#define SF_LOG log
+#define SF_POW pow
+#define SF_PF_RESCALE 1
+#endif
+/* ln Z above which a fold is redone with a per-nucleotide scale (the kernels flag Z > e^600 the same way): the outside
+ * pass overflows FP64 well before Z itself does */
+#define SF_PF_LNZ_MAX 600.0
 #define TURN SF_TURN
 #define MAXLOOP SF_MAXLOOP
 #define MIN2(a, b) ((a) < (b) ? (a) : (b))
@@ -52,15 +73,15 @@ static int pair_tab[5][5];
 
 /* Boltzmann-weight tables derived from P at P.temperature */
 typedef struct {
-  double kT; /* cal/mol */
-  double stack[8][8], hairpin[31], bulge[31], internal_loop[31];
-  double mismatchI[8][5][5], mismatchH[8][5][5], mismatchM[8][5][5], mismatch1nI[8][5][5],
+  sf_real kT; /* cal/mol */
+  sf_real stack[8][8], hairpin[31], bulge[31], internal_loop[31];
+  sf_real mismatchI[8][5][5], mismatchH[8][5][5], mismatchM[8][5][5], mismatch1nI[8][5][5],
       mismatch23I[8][5][5], mismatchExt[8][5][5];
-  double dangle5[8][5], dangle3[8][5];
-  double int11[8][8][5][5], int21[8][8][5][5][5], int22[8][8][5][5][5][5];
-  double ninio[MAXLOOP + 1];
-  double MLbase, MLclosing, MLintern[8], TermAU;
-  double tetra[SF_MAX_SPECIAL], tri[SF_MAX_SPECIAL], hexa[SF_MAX_SPECIAL];
+  sf_real dangle5[8][5], dangle3[8][5];
+  sf_real int11[8][8][5][5], int21[8][8][5][5][5], int22[8][8][5][5][5][5];
+  sf_real ninio[MAXLOOP + 1];
+  sf_real MLbase, MLclosing, MLintern[8], TermAU;
+  sf_real tetra[SF_MAX_SPECIAL], tri[SF_MAX_SPECIAL], hexa[SF_MAX_SPECIAL];
 } exp_params;
 static exp_params *XP = NULL;
 
@@ -92,10 +113,10 @@ static void build_exp_params(void) {
   if (!XP) XP = (exp_params *)malloc(sizeof(exp_params));
   exp_params *x = XP;
   x->kT = (P.temperature + K0) * GASCONST;
-  const double kT = x->kT;
+  const sf_real kT = x->kT;
 #define EX(f) exact_energy(&(f))
-#define BW(e) exp(-(double)(e)*10.0 / kT)
-#define BWS(e) exp(smooth(-(double)(e)) * 10.0 / kT)
+#define BW(e) SF_EXP(-(sf_real)(e)*10 / kT)
+#define BWS(e) SF_EXP((sf_real)smooth(-(double)(e)) * 10 / kT)
   for (int a = 0; a < 8; a++)
     for (int b = 0; b < 8; b++) x->stack[a][b] = BW(EX(P.stack[a][b]));
   for (int i = 0; i <= 30; i++) {
@@ -377,8 +398,8 @@ static int E_extloop(int type, int si1, int sj1) {
 }
 
 /* Boltzmann-weight twins */
-static double X_hairpin(int size, int type, int si1, int sj1, const char *loop) {
-  double q = (size <= 30) ? XP->hairpin[size] : XP->hairpin[30] * exp(-(P.lxc * log(size / 30.)) * 10. / XP->kT);
+static sf_real X_hairpin(int size, int type, int si1, int sj1, const char *loop) {
+  sf_real q = (size <= 30) ? XP->hairpin[size] : XP->hairpin[30] * SF_EXP(-(sf_real)(P.lxc * log(size / 30.)) * 10 / XP->kT);
   if (size < 3) return q;
   if (size == 4) {
     int k = special_lookup(P.tetra_seq, P.n_tetra, loop, 6);
@@ -393,12 +414,12 @@ static double X_hairpin(int size, int type, int si1, int sj1, const char *loop) 
   }
   return q * XP->mismatchH[type][si1][sj1];
 }
-static double X_intloop(int n1, int n2, int type, int type_2, int si1, int sj1, int sp1, int sq1) {
+static sf_real X_intloop(int n1, int n2, int type, int type_2, int si1, int sj1, int sp1, int sq1) {
   int nl, ns;
   if (n1 > n2) { nl = n1; ns = n2; } else { nl = n2; ns = n1; }
   if (nl == 0) return XP->stack[type][type_2];
   if (ns == 0) {
-    double z = XP->bulge[nl];
+    sf_real z = XP->bulge[nl];
     if (nl == 1) z *= XP->stack[type][type_2];
     else {
       if (type > 2) z *= XP->TermAU;
@@ -424,16 +445,16 @@ static double X_intloop(int n1, int n2, int type, int type_2, int si1, int sj1, 
   return XP->internal_loop[nl + ns] * XP->ninio[nl - ns] * XP->mismatchI[type][si1][sj1] *
          XP->mismatchI[type_2][sq1][sp1];
 }
-static double X_mlstem(int type, int si1, int sj1) {
-  double z = 1.0;
+static sf_real X_mlstem(int type, int si1, int sj1) {
+  sf_real z = 1.0;
   if (si1 >= 0 && sj1 >= 0) z = XP->mismatchM[type][si1][sj1];
   else if (si1 >= 0) z = XP->dangle5[type][si1];
   else if (sj1 >= 0) z = XP->dangle3[type][sj1];
   if (type > 2) z *= XP->TermAU;
   return z * XP->MLintern[type];
 }
-static double X_extloop(int type, int si1, int sj1) {
-  double z = 1.0;
+static sf_real X_extloop(int type, int si1, int sj1) {
+  sf_real z = 1.0;
   if (si1 >= 0 && sj1 >= 0) z = XP->mismatchExt[type][si1][sj1];
   else if (si1 >= 0) z = XP->dangle5[type][si1];
   else if (sj1 >= 0) z = XP->dangle3[type][sj1];
@@ -752,11 +773,11 @@ int sfo_eval(const char *seq, const char *structure, int n, int *energy) {
 }
 
 /* Boltzmann weight of a structure under the partition-function model (smoothed dangles) */
-static double weight_loop(const seq_t *q, const int *pt, int i, int j) {
+static sf_real weight_loop(const seq_t *q, const int *pt, int i, int j) {
   const int *S = q->S;
   int type = ptype(q, i, j);
   int p = i + 1, nstems = 0, p1 = 0, q1 = 0, unp = 0;
-  double w = 1.0;
+  sf_real w = 1;
   while (p < j) {
     if (pt[p] == 0) { unp++; p++; continue; }
     int qq = pt[p];
@@ -768,11 +789,11 @@ static double weight_loop(const seq_t *q, const int *pt, int i, int j) {
   if (nstems == 0) return X_hairpin(j - i - 1, type, S[i + 1], S[j - 1], q->str + i - 1);
   if (nstems == 1)
     return X_intloop(p1 - i - 1, j - q1 - 1, type, rtype[ptype(q, p1, q1)], S[i + 1], S[j - 1], S[p1 - 1], S[q1 + 1]);
-  return XP->MLclosing * X_mlstem(rtype[type], S[j - 1], S[i + 1]) * w * pow(XP->MLbase, unp);
+  return XP->MLclosing * X_mlstem(rtype[type], S[j - 1], S[i + 1]) * w * SF_POW(XP->MLbase, unp);
 }
-static double weight_pt(const seq_t *q, const int *pt) {
+static sf_real weight_pt(const seq_t *q, const int *pt) {
   int n = q->n;
-  double w = 1.0;
+  sf_real w = 1;
   int i = 1;
   while (i <= n) {
     if (pt[i] == 0) { i++; continue; }
@@ -790,8 +811,8 @@ typedef struct {
   const seq_t *q;
   int *pt;
   int best;
-  double Z;
-  double *bpp; /* (n+1)*(n+1) accumulators or NULL */
+  sf_real Z;
+  sf_real *bpp; /* (n+1)*(n+1) accumulators or NULL */
   long long count;
 } brute_ctx;
 
@@ -830,7 +851,7 @@ static void brute_enum(brute_ctx *b, seg *segs, int nseg) {
       int e = eval_pt(q, b->pt, &bad);
       b->count++;
       if (e < b->best) b->best = e;
-      double w = weight_pt(q, b->pt);
+      sf_real w = weight_pt(q, b->pt);
       b->Z += w;
       if (b->bpp)
         for (int i = 1; i <= n; i++)
@@ -859,61 +880,74 @@ static void brute_enum(brute_ctx *b, seg *segs, int nseg) {
   segs[nseg] = above;
 }
 
-int sfo_brute(const char *seq, int n, int *mfe_dcal, double *Z, double *bpp, long long *count) {
+/* *Z: the Boltzmann sum in sf_real, returned as double (inf where it passes the double range); *dG: -kT ln Z in
+ * kcal/mol, finite in the long-double build; bpp normalised in sf_real */
+static int brute_impl(const char *seq, int n, int *mfe_dcal, double *Z, double *dG, double *bpp, long long *count) {
   if (!have_params) return -10;
   if (n > 26) return -3;
   seq_t q;
   seq_init(&q, seq, n);
   if (q.cons_bad) { seq_free(&q); return -3; }
+  const size_t nb = (size_t)(n + 1) * (size_t)(n + 1);
   brute_ctx b;
   b.q = &q;
   b.pt = (int *)calloc((size_t)n + 2, sizeof(int));
   b.best = INF;
-  b.Z = 0.0;
-  b.bpp = bpp;
+  b.Z = 0;
+  b.bpp = bpp ? (sf_real *)calloc(nb, sizeof(sf_real)) : NULL;
   b.count = 0;
-  if (bpp) memset(bpp, 0, sizeof(double) * (size_t)(n + 1) * (size_t)(n + 1));
   seg *segs = (seg *)calloc((size_t)(n + 4), sizeof(seg));
   segs[0] = (seg){1, n};
   brute_enum(&b, segs, 1);
   if (bpp)
-    for (size_t k = 0; k < (size_t)(n + 1) * (size_t)(n + 1); k++) bpp[k] /= b.Z;
+    for (size_t k = 0; k < nb; k++) bpp[k] = (double)(b.bpp[k] / b.Z);
   if (mfe_dcal) *mfe_dcal = b.best;
-  if (Z) *Z = b.Z;
+  if (Z) *Z = (double)b.Z;
+  if (dG) *dG = (double)(-SF_LOG(b.Z) * XP->kT / 1000);
   if (count) *count = b.count;
+  free(b.bpp);
   free(segs);
   free(b.pt);
   seq_free(&q);
   return 0;
 }
+int sfo_brute(const char *seq, int n, int *mfe_dcal, double *Z, double *bpp, long long *count) {
+  return brute_impl(seq, n, mfe_dcal, Z, NULL, bpp, count);
+}
+int sfo_brute_dG(const char *seq, int n, double *ensemble_dG, double *bpp) {
+  return brute_impl(seq, n, NULL, NULL, ensemble_dG, bpp, NULL);
+}
 
 /* =================================== partition function =================================== */
 /* Inside: qb, qm, qm1 (unambiguous McCaskill decomposition, dangles=2), q5/q3 exterior.
- * Outside: direct O(n^4) summation over enclosing pairs (an oracle, not a fast path). */
-int sfo_pf(const char *seq, int n, double *ensemble_dG, double *bpp_out, char *centroid, double *centroid_dist,
-           double *mean_bp_dist) {
-  if (!have_params) return -10;
-  seq_t q;
-  seq_init(&q, seq, n);
-  if (q.cons_bad) { seq_free(&q); return -3; }
+ * Outside: direct O(n^4) summation over enclosing pairs (an oracle, not a fast path).
+ * Scaled by s = e^lns per nucleotide: every weight that covers k nucleotides not yet covered by the tables it
+ * multiplies carries sc[k] = s^-k, so each table entry holds its weight times s^-(nucleotides it spans) and
+ * Z_s = Z s^-n.  lns = 0 multiplies by exactly 1.  Returns ln Z_s. */
+static double pf_run(const seq_t *qs, sf_real lns, double *ensemble_dG, double *bpp_out, char *centroid,
+                     double *centroid_dist, double *mean_bp_dist) {
+  const seq_t q = *qs;
+  const int n = q.n;
   const int *S = q.S;
   size_t sz = (size_t)(n + 2) * (size_t)(n + 2);
-  double *qb = (double *)calloc(sz, sizeof(double));
-  double *qm = (double *)calloc(sz, sizeof(double));
-  double *qm1 = (double *)calloc(sz, sizeof(double));
-  double *ob = (double *)calloc(sz, sizeof(double));
-  double *q5 = (double *)calloc((size_t)n + 2, sizeof(double));
-  double *q3 = (double *)calloc((size_t)n + 3, sizeof(double));
-  double *mlb = (double *)malloc(sizeof(double) * (size_t)(n + 2)); /* expMLbase^k */
-  mlb[0] = 1.0;
-  for (int k = 1; k <= n + 1; k++) mlb[k] = mlb[k - 1] * XP->MLbase;
+  sf_real *qb = (sf_real *)calloc(sz, sizeof(sf_real));
+  sf_real *qm = (sf_real *)calloc(sz, sizeof(sf_real));
+  sf_real *qm1 = (sf_real *)calloc(sz, sizeof(sf_real));
+  sf_real *ob = (sf_real *)calloc(sz, sizeof(sf_real));
+  sf_real *q5 = (sf_real *)calloc((size_t)n + 2, sizeof(sf_real));
+  sf_real *q3 = (sf_real *)calloc((size_t)n + 3, sizeof(sf_real));
+  sf_real *mlb = (sf_real *)malloc(sizeof(sf_real) * (size_t)(n + 2)); /* (expMLbase / s)^k */
+  sf_real *sc = (sf_real *)malloc(sizeof(sf_real) * (size_t)(n + 2));  /* s^-k */
+  for (int k = 0; k <= n + 1; k++) sc[k] = SF_EXP(-lns * k);
+  mlb[0] = 1;
+  for (int k = 1; k <= n + 1; k++) mlb[k] = mlb[k - 1] * XP->MLbase * sc[1];
 
   for (int d = TURN + 1; d < n; d++) {
     for (int i = 1; i + d <= n; i++) {
       int j = i + d;
       int type = ptype(&q, i, j);
       if (type) {
-        double z = X_hairpin(d - 1, type, S[i + 1], S[j - 1], q.str + i - 1);
+        sf_real z = X_hairpin(d - 1, type, S[i + 1], S[j - 1], q.str + i - 1) * sc[d + 1];
         int pmax = MIN2(j - 2 - TURN, i + MAXLOOP + 1);
         for (int p = i + 1; p <= pmax; p++) {
           int minq = j - i + p - MAXLOOP - 2;
@@ -922,81 +956,81 @@ int sfo_pf(const char *seq, int n, double *ensemble_dG, double *bpp_out, char *c
             int t2 = ptype(&q, p, qq);
             if (!t2) continue;
             z += X_intloop(p - i - 1, j - qq - 1, type, rtype[t2], S[i + 1], S[j - 1], S[p - 1], S[qq + 1]) *
-                 qb[IX(p, qq)];
+                 qb[IX(p, qq)] * sc[(p - i) + (j - qq)];
           }
         }
-        double ml = 0.0;
+        sf_real ml = 0;
         for (int u = i + 2 + TURN; u <= j - 1 - TURN - 1; u++) ml += qm[IX(i + 1, u - 1)] * qm1[IX(u, j - 1)];
-        z += ml * XP->MLclosing * X_mlstem(rtype[type], S[j - 1], S[i + 1]);
+        z += ml * XP->MLclosing * X_mlstem(rtype[type], S[j - 1], S[i + 1]) * sc[2];
         qb[IX(i, j)] = z;
       }
       /* qm1[i][j] = sum_l qb[i][l] * stem(i,l) * MLbase^(j-l) */
-      double m1 = 0.0;
+      sf_real m1 = 0;
       for (int l = i + TURN + 1; l <= j; l++) {
         int t2 = ptype(&q, i, l);
-        if (t2 && qb[IX(i, l)] != 0.0) m1 += qb[IX(i, l)] * X_mlstem(t2, ml_nb5(&q, i), ml_nb3(&q, l)) * mlb[j - l];
+        if (t2 && qb[IX(i, l)] != 0) m1 += qb[IX(i, l)] * X_mlstem(t2, ml_nb5(&q, i), ml_nb3(&q, l)) * mlb[j - l];
       }
       qm1[IX(i, j)] = m1;
       /* qm[i][j] = sum_u (MLbase^(u-i) + qm[i][u-1]) * qm1[u][j] */
-      double m = 0.0;
+      sf_real m = 0;
       for (int u = i; u + TURN + 1 <= j; u++) {
-        double left = mlb[u - i] + ((u - 1 >= i) ? qm[IX(i, u - 1)] : 0.0);
+        sf_real left = mlb[u - i] + ((u - 1 >= i) ? qm[IX(i, u - 1)] : 0);
         m += left * qm1[IX(u, j)];
       }
       qm[IX(i, j)] = m;
     }
   }
   /* exterior */
-  q5[0] = 1.0;
+  q5[0] = 1;
   for (int j = 1; j <= n; j++) {
-    double z = q5[j - 1];
+    sf_real z = q5[j - 1] * sc[1];
     for (int i = 1; i + TURN + 1 <= j; i++) {
       int type = ptype(&q, i, j);
       if (type) z += q5[i - 1] * qb[IX(i, j)] * X_extloop(type, ml_nb5(&q, i), ml_nb3(&q, j));
     }
     q5[j] = z;
   }
-  q3[n + 1] = 1.0;
+  q3[n + 1] = 1;
   for (int i = n; i >= 1; i--) {
-    double z = q3[i + 1];
+    sf_real z = q3[i + 1] * sc[1];
     for (int j = i + TURN + 1; j <= n; j++) {
       int type = ptype(&q, i, j);
       if (type) z += qb[IX(i, j)] * X_extloop(type, ml_nb5(&q, i), ml_nb3(&q, j)) * q3[j + 1];
     }
     q3[i] = z;
   }
-  double Z = q5[n];
-  if (ensemble_dG) *ensemble_dG = -log(Z) * XP->kT / 1000.0;
+  sf_real Z = q5[n];
+  if (ensemble_dG) *ensemble_dG = (double)(-(SF_LOG(Z) + lns * n) * XP->kT / 1000);
 
   /* outside of pairs, widest first */
   for (int d = n - 1; d >= TURN + 1; d--) {
     for (int i = 1; i + d <= n; i++) {
       int j = i + d;
       int type = ptype(&q, i, j);
-      if (!type || qb[IX(i, j)] == 0.0) continue;
-      double o = q5[i - 1] * q3[j + 1] * X_extloop(type, ml_nb5(&q, i), ml_nb3(&q, j));
+      if (!type || qb[IX(i, j)] == 0) continue;
+      sf_real o = q5[i - 1] * q3[j + 1] * X_extloop(type, ml_nb5(&q, i), ml_nb3(&q, j));
       for (int k = MAX2(1, i - MAXLOOP - 1); k < i; k++) {
         int u1 = i - k - 1;
         for (int l = j + 1; l <= n && (l - j - 1) + u1 <= MAXLOOP; l++) {
           int tk = ptype(&q, k, l);
-          if (!tk || ob[IX(k, l)] == 0.0) continue;
+          if (!tk || ob[IX(k, l)] == 0) continue;
           o += ob[IX(k, l)] *
-               X_intloop(u1, l - j - 1, tk, rtype[type], S[k + 1], S[l - 1], S[i - 1], S[j + 1]);
+               X_intloop(u1, l - j - 1, tk, rtype[type], S[k + 1], S[l - 1], S[i - 1], S[j + 1]) * sc[(i - k) + (l - j)];
         }
       }
       /* (i,j) as a stem of a multiloop closed by (k,l) */
-      double mlsum = 0.0;
+      sf_real mlsum = 0;
       if (i > 1 && j < n) {
-        double stem = X_mlstem(type, S[i - 1], S[j + 1]);
+        sf_real stem = X_mlstem(type, S[i - 1], S[j + 1]);
         for (int k = 1; k < i; k++)
           for (int l = j + 1; l <= n; l++) {
             int tk = ptype(&q, k, l);
-            if (!tk || ob[IX(k, l)] == 0.0) continue;
-            double left_q = (i - 1 >= k + 1) ? qm[IX(k + 1, i - 1)] : 0.0;
-            double right_q = (l - 1 >= j + 1) ? qm[IX(j + 1, l - 1)] : 0.0;
-            double ctx = left_q * mlb[l - 1 - j] + mlb[i - k - 1] * right_q + left_q * right_q;
-            if (ctx == 0.0) continue;
-            mlsum += ob[IX(k, l)] * XP->MLclosing * X_mlstem(rtype[tk], S[l - 1], S[k + 1]) * ctx;
+            if (!tk || ob[IX(k, l)] == 0) continue;
+            sf_real left_q = (i - 1 >= k + 1) ? qm[IX(k + 1, i - 1)] : 0;
+            sf_real right_q = (l - 1 >= j + 1) ? qm[IX(j + 1, l - 1)] : 0;
+            sf_real ctx = left_q * mlb[l - 1 - j] + mlb[i - k - 1] * right_q + left_q * right_q;
+            if (ctx == 0) continue;
+            mlsum += ob[IX(k, l)] * XP->MLclosing * X_mlstem(rtype[tk], S[l - 1], S[k + 1]) * ctx * sc[2];
           }
         mlsum *= stem;
       }
@@ -1004,7 +1038,7 @@ int sfo_pf(const char *seq, int n, double *ensemble_dG, double *bpp_out, char *c
       ob[IX(i, j)] = o;
     }
   }
-  double mbd = 0.0, cdist = 0.0;
+  sf_real mbd = 0, cdist = 0;
   if (bpp_out) memset(bpp_out, 0, sizeof(double) * (size_t)(n + 1) * (size_t)(n + 1));
   if (centroid) {
     for (int k = 0; k < n; k++) centroid[k] = '.';
@@ -1012,20 +1046,52 @@ int sfo_pf(const char *seq, int n, double *ensemble_dG, double *bpp_out, char *c
   }
   for (int i = 1; i <= n; i++)
     for (int j = i + TURN + 1; j <= n; j++) {
-      double p = ob[IX(i, j)] * qb[IX(i, j)] / Z;
-      if (bpp_out) bpp_out[(size_t)i * (n + 1) + j] = p;
-      mbd += p * (1.0 - p);
+      sf_real p = ob[IX(i, j)] * qb[IX(i, j)] / Z;
+      if (bpp_out) bpp_out[(size_t)i * (n + 1) + j] = (double)p;
+      mbd += p * (1 - p);
       if (p > 0.5) {
         if (centroid) { centroid[i - 1] = '('; centroid[j - 1] = ')'; }
-        cdist += 1.0 - p;
+        cdist += 1 - p;
       } else cdist += p;
     }
-  if (mean_bp_dist) *mean_bp_dist = 2.0 * mbd;
-  if (centroid_dist) *centroid_dist = cdist;
-  free(qb); free(qm); free(qm1); free(ob); free(q5); free(q3); free(mlb);
+  if (mean_bp_dist) *mean_bp_dist = (double)(2 * mbd);
+  if (centroid_dist) *centroid_dist = (double)cdist;
+  free(qb); free(qm); free(qm1); free(ob); free(q5); free(q3); free(mlb); free(sc);
+  return (double)SF_LOG(Z);
+}
+
+/* A fold whose ln Z passes SF_PF_LNZ_MAX (or is not finite) is redone scaled: by its own ln Z_s / n where that is finite,
+ * which brings ln Z_s to ~0, else by 700 / n more, which lowers ln Z_s (> 709 before) by exactly 700. */
+int sfo_pf(const char *seq, int n, double *ensemble_dG, double *bpp_out, char *centroid, double *centroid_dist,
+           double *mean_bp_dist) {
+  if (!have_params) return -10;
+  seq_t q;
+  seq_init(&q, seq, n);
+  if (q.cons_bad) { seq_free(&q); return -3; }
+  sf_real lns = 0;
+  for (int attempt = 0; attempt < 40; attempt++) {
+    const double lz = pf_run(&q, lns, ensemble_dG, bpp_out, centroid, centroid_dist, mean_bp_dist);
+    if (!SF_PF_RESCALE || lz <= SF_PF_LNZ_MAX) break;
+    lns += (isfinite(lz) ? lz : 700.0) / n;
+  }
+  seq_free(&q);
+  return 0;
+}
+
+/* the scale-free FP64 fold (lns = 0) with its ln Z, for the tests that show where it leaves the range */
+int sfo_pf_unscaled(const char *seq, int n, double *ensemble_dG, double *centroid_dist, double *mean_bp_dist,
+                    double *ln_z) {
+  if (!have_params) return -10;
+  seq_t q;
+  seq_init(&q, seq, n);
+  if (q.cons_bad) { seq_free(&q); return -3; }
+  const double lz = pf_run(&q, 0, ensemble_dG, NULL, NULL, centroid_dist, mean_bp_dist);
+  if (ln_z) *ln_z = lz;
   seq_free(&q);
   return 0;
 }
 
 /* =================================== fast CPU twin (baseline only) =================================== */
+#ifndef SF_ORACLE_LONG /* the twin is FP64 by design */
 #include "sf_cpu_twin.c"
+#endif

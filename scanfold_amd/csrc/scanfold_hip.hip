@@ -60,7 +60,7 @@ struct Ctx {
   uint64_t loads = 0;
   int cur = 0;
   double temperature = 37.0;
-  DevBuf full_scratch, pf_scratch, pf_share, fast_scratch, seqs, energies, db, cen, dbl, status, transcript, ovf, cons, sc;
+  DevBuf full_scratch, pf_scratch, pf_share, fast_scratch, seqs, energies, db, cen, dbl, status, transcript, ovf, cons, sc, pf_flag;
   // the rolling-row offsets (SfFastRows, 8.7 kB) of every width that has been launched: one device table per width, written
   // once and never again, so launches of different widths on different caller streams (sf_mfe_device) cannot see each other's
   std::map<int, SfFastRows *> fast_rows;
@@ -242,13 +242,42 @@ int launch_full(const uint8_t *d_seqs, const int *d_idx, const int *d_count, int
   return SF_OK;
 }
 
+// Partition functions past FP64's range (sf_pf.hip.h): every PF launch clears a flag per row, the kernel flags the folds
+// whose ln Z passes SF_PF_LNZ_MAX, and sf_pf_kernel<true> redoes those — on the device, so that the _dev paths stay
+// free of host round trips (as the int16 -> int32 MFE list does).  pf_begin sizes the scratch of both launches up front
+// (the redo reuses g.pf_scratch behind the first launch on the same stream).
+static int pf_begin(int n, int W, size_t scratch_bytes, hipStream_t st) {
+  const size_t redo = (size_t)(n < SF_PF_REDO_GRID ? n : SF_PF_REDO_GRID) * SF_PF_SCRATCH_DOUBLES(W) * sizeof(double);
+  int rc = ensure(g.pf_scratch, scratch_bytes > redo ? scratch_bytes : redo);
+  if (!rc) rc = ensure(g.pf_flag, (size_t)n * sizeof(int));
+  if (rc) return rc;
+  HIPCHK(hipMemsetAsync(g.pf_flag.p, 0, (size_t)n * sizeof(int), st));
+  return SF_OK;
+}
+static int pf_redo_flagged(const uint8_t *d_seqs, int n, int row_stride, int W, double *d_dG, double *d_mbd, char *d_cen,
+                           double *d_cd, const char *d_cons, hipStream_t st) {
+  HIPCHK(hipGetLastError());
+  const int grid = n < SF_PF_REDO_GRID ? n : SF_PF_REDO_GRID;
+  SF_LAUNCH((sf_pf_kernel<true>), grid, block_threads(W), 0, st, d_seqs, n, row_stride, W, (const SfDevParams *)g.dP,
+            (const SfDevParamsPF *)g.dX, (double *)g.pf_scratch.p, d_dG, d_mbd, d_cen, d_cd, d_cons, (int *)nullptr,
+            (int *)g.pf_flag.p);
+  HIPCHK(hipGetLastError());
+  return SF_OK;
+}
+
 // d_tr != null: the n rows are the native windows of transcript d_tr (length L) that start at win0, win0+1, ...
-// (sf_scan with step 1): consecutive windows share their inside tables (sf_pf_lds.hip.h).
+// (sf_scan with step 1): consecutive windows share their inside tables (sf_pf_lds.hip.h).  A flagged window keeps its
+// place in the run: the tables it hands on hold the same (unscaled) values as its neighbours' own folds would, and only
+// its own outputs are redone.
 int launch_pf(const uint8_t *d_seqs, int n, int row_stride, int W, double *d_dG, double *d_mbd, char *d_cen,
               double *d_cd, hipStream_t st, const uint8_t *d_tr = nullptr, int L = 0, int win0 = 0, int step = 1) {
   if (n <= 0) return SF_OK;
   int grid = n < max_resident_blocks() ? n : max_resident_blocks();
+  int *d_flag = nullptr;
   if (sf_pfl_supported(W) && !g.force_full && g.pf_kernel == 0) {
+    int rc = pf_begin(n, W, 0, st);
+    if (rc) return rc;
+    d_flag = (int *)g.pf_flag.p;
     // every table of a fold in the LDS of one CU: one workgroup per CU
     grid = n < g.n_cu ? n : g.n_cu;
     int run_len = 1;
@@ -271,23 +300,24 @@ int launch_pf(const uint8_t *d_seqs, int n, int row_stride, int W, double *d_dG,
       }
     }
     sf_pf_lds_launch(grid, W, share != nullptr, st, d_seqs, n, row_stride, W, (const SfDevParams *)g.dP, (const SfDevParamsPF *)g.dX,
-                     d_dG, d_mbd, d_cen, d_cd, d_tr, L, win0, step, run_len, share, (const char *)nullptr, (int *)nullptr);
+                     d_dG, d_mbd, d_cen, d_cd, d_tr, L, win0, step, run_len, share, (const char *)nullptr, (int *)nullptr, d_flag);
   } else if (W >= 16 && W <= SF_PFF_MAXW && !g.force_full) {
     const int pf_blocks = g.n_cu * pf_fast_blocks_per_cu(W);
     grid = n < pf_blocks ? n : pf_blocks;
-    int rc = ensure(g.pf_scratch, (size_t)grid * SF_PFF_SCRATCH_DOUBLES(W) * sizeof(double));
+    int rc = pf_begin(n, W, (size_t)grid * SF_PFF_SCRATCH_DOUBLES(W) * sizeof(double), st);
     if (rc) return rc;
-    sf_pf_fast_launch(grid, W, st, d_seqs, n, row_stride, W, (const SfDevParams *)g.dP, (const SfDevParamsPF *)g.dX,
+    d_flag = (int *)g.pf_flag.p;
+    sf_pf_fast_launch(grid, W, st, d_flag, d_seqs, n, row_stride, W, (const SfDevParams *)g.dP, (const SfDevParamsPF *)g.dX,
                       (double *)g.pf_scratch.p, d_dG, d_mbd, d_cen, d_cd);
   } else {
-    int rc = ensure(g.pf_scratch, (size_t)grid * SF_PF_SCRATCH_DOUBLES(W) * sizeof(double));
+    int rc = pf_begin(n, W, (size_t)grid * SF_PF_SCRATCH_DOUBLES(W) * sizeof(double), st);
     if (rc) return rc;
-    SF_LAUNCH(sf_pf_kernel, grid, block_threads(W), 0, st, d_seqs, n, row_stride, W, (const SfDevParams *)g.dP,
+    d_flag = (int *)g.pf_flag.p;
+    SF_LAUNCH((sf_pf_kernel<false>), grid, block_threads(W), 0, st, d_seqs, n, row_stride, W, (const SfDevParams *)g.dP,
               (const SfDevParamsPF *)g.dX, (double *)g.pf_scratch.p, d_dG, d_mbd, d_cen, d_cd, (const char *)nullptr,
-              (int *)nullptr);
+              (int *)nullptr, d_flag);
   }
-  HIPCHK(hipGetLastError());
-  return SF_OK;
+  return pf_redo_flagged(d_seqs, n, row_stride, W, d_dG, d_mbd, d_cen, d_cd, (const char *)nullptr, st);
 }
 
 // energies of n rows: LDS-resident int16 kernel, then the exact int32 kernel on the rows it flagged.
@@ -499,7 +529,7 @@ int sf_init(int device_ordinal) {
 int sf_shutdown(void) {
   if (!g.init) return SF_OK;
   hipDeviceSynchronize();
-  DevBuf *bufs[] = {&g.full_scratch, &g.pf_scratch, &g.pf_share, &g.fast_scratch, &g.seqs, &g.energies, &g.db, &g.cen,
+  DevBuf *bufs[] = {&g.pf_flag, &g.full_scratch, &g.pf_scratch, &g.pf_share, &g.fast_scratch, &g.seqs, &g.energies, &g.db, &g.cen,
                     &g.dbl, &g.status, &g.transcript, &g.ovf, &g.cons, &g.sc, &g.tab_in, &g.tab_partner, &g.tab_counts,
                     &g.tab_out};
   for (DevBuf *b : bufs) {
@@ -743,22 +773,26 @@ int sf_fold_constrained(const uint8_t *seqs, int n, int W, const char *cons, con
     } else if (!noncanonical && !g.force_full && g.pf_kernel == 0 && sf_pfl_supported(W) &&
                sf_pfl_lds_bytes(W, true) <= SF_PFL_LDS_LIMIT) {
       grid = n < g.n_cu ? n : g.n_cu;  // every table of a fold in the LDS of one CU
+      if ((rc = pf_begin(n, W, 0, g.stream))) return rc;
       sf_pf_lds_launch_hc(grid, W, g.stream, (const uint8_t *)g.seqs.p, n, 1, W, (const SfDevParams *)g.dP,
                           (const SfDevParamsPF *)g.dX, d_dG, d_mbd, (char *)g.cen.p, d_cd, (const uint8_t *)nullptr, 0, 0, 1, 1,
-                          (double *)nullptr, d_cons, (int *)g.status.p);
+                          (double *)nullptr, d_cons, (int *)g.status.p, (int *)g.pf_flag.p);
+      if ((rc = pf_redo_flagged((const uint8_t *)g.seqs.p, n, 1, W, d_dG, d_mbd, (char *)g.cen.p, d_cd, d_cons, g.stream))) return rc;
     } else if (!noncanonical && !g.force_full && W >= 16 && W <= SF_PFF_HC_MAXW) {
       // the constrained instantiation of the device-table kernel (120 < W <= 250, or SCANFOLD_PF_KERNEL=global)
       const int pf_blocks = g.n_cu * pf_fast_blocks_per_cu(W);
       grid = n < pf_blocks ? n : pf_blocks;
-      if ((rc = ensure(g.pf_scratch, (size_t)grid * SF_PFF_SCRATCH_DOUBLES(W) * sizeof(double)))) return rc;
+      if ((rc = pf_begin(n, W, (size_t)grid * SF_PFF_SCRATCH_DOUBLES(W) * sizeof(double), g.stream))) return rc;
       sf_pf_fast_launch_hc(grid, W, g.stream, (const uint8_t *)g.seqs.p, n, 1, W, (const SfDevParams *)g.dP,
                            (const SfDevParamsPF *)g.dX, (double *)g.pf_scratch.p, d_dG, d_mbd, (char *)g.cen.p, d_cd, d_cons,
-                           (int *)g.status.p);
+                           (int *)g.status.p, (int *)g.pf_flag.p);
+      if ((rc = pf_redo_flagged((const uint8_t *)g.seqs.p, n, 1, W, d_dG, d_mbd, (char *)g.cen.p, d_cd, d_cons, g.stream))) return rc;
     } else {
-      if ((rc = ensure(g.pf_scratch, (size_t)grid * SF_PF_SCRATCH_DOUBLES(W) * sizeof(double)))) return rc;
-      SF_LAUNCH(sf_pf_kernel, grid, block_threads(W), 0, g.stream, (const uint8_t *)g.seqs.p, n, 1, W,
+      if ((rc = pf_begin(n, W, (size_t)grid * SF_PF_SCRATCH_DOUBLES(W) * sizeof(double), g.stream))) return rc;
+      SF_LAUNCH((sf_pf_kernel<false>), grid, block_threads(W), 0, g.stream, (const uint8_t *)g.seqs.p, n, 1, W,
                 (const SfDevParams *)g.dP, (const SfDevParamsPF *)g.dX, (double *)g.pf_scratch.p, d_dG, d_mbd,
-                (char *)g.cen.p, d_cd, d_cons, (int *)g.status.p);
+                (char *)g.cen.p, d_cd, d_cons, (int *)g.status.p, (int *)g.pf_flag.p);
+      if ((rc = pf_redo_flagged((const uint8_t *)g.seqs.p, n, 1, W, d_dG, d_mbd, (char *)g.cen.p, d_cd, d_cons, g.stream))) return rc;
     }
     HIPCHK(hipGetLastError());
     if (ens_dG) HIPCHK(hipMemcpyAsync(ens_dG, d_dG, n * sizeof(double), hipMemcpyDeviceToHost, g.stream));

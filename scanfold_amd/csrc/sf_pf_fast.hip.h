@@ -54,7 +54,8 @@ __global__ __launch_bounds__(NT, 2) void sf_pf_fast_kernel(const uint8_t *__rest
                                                         double *__restrict__ scratch, double *__restrict__ ens_dG,
                                                         double *__restrict__ mean_bp_dist, char *__restrict__ centroid,
                                                         double *__restrict__ centroid_dist,
-                                                        const char *__restrict__ cons_rows, int *__restrict__ status) {
+                                                        const char *__restrict__ cons_rows, int *__restrict__ status,
+                                                        int *__restrict__ pf_flag) {
   __shared__ uint8_t S[SF_PFF_MAXW + 2];
   __shared__ char hcC[HC ? SF_PFF_MAXW + 2 : 1];
   __shared__ uint8_t hcP[HC ? SF_PFF_MAXW + 2 : 1], hcE[HC ? SF_PFF_MAXW + 2 : 1];
@@ -463,6 +464,7 @@ __global__ __launch_bounds__(NT, 2) void sf_pf_fast_kernel(const uint8_t *__rest
       if (ens_dG) ens_dG[k] = -log(Z) * X->kT / 1000.0;
       if (mean_bp_dist) mean_bp_dist[k] = 2.0 * mbd;
       if (centroid_dist) centroid_dist[k] = cd;
+      if (pf_flag) pf_flag[k] = sf_pf_out_of_range(Z);  // redone scaled by sf_pf_kernel<true>
     }
   }
 #undef PT
@@ -470,11 +472,11 @@ __global__ __launch_bounds__(NT, 2) void sf_pf_fast_kernel(const uint8_t *__rest
 }
 
 template <typename... A>
-static inline void sf_pf_fast_launch(int grid, int W, hipStream_t st, A... args) {
-  if (W == 120) SF_LAUNCH((sf_pf_fast_kernel<128, 120>), grid, 128, 0, st, args..., (const char *)nullptr, (int *)nullptr);
-  else if (W <= 128) SF_LAUNCH((sf_pf_fast_kernel<128, 0>), grid, 128, 0, st, args..., (const char *)nullptr, (int *)nullptr);
-  else if (W == 200) SF_LAUNCH((sf_pf_fast_kernel<256, 200>), grid, 256, 0, st, args..., (const char *)nullptr, (int *)nullptr);
-  else SF_LAUNCH((sf_pf_fast_kernel<256, 0>), grid, 256, 0, st, args..., (const char *)nullptr, (int *)nullptr);
+static inline void sf_pf_fast_launch(int grid, int W, hipStream_t st, int *pf_flag, A... args) {
+  if (W == 120) SF_LAUNCH((sf_pf_fast_kernel<128, 120>), grid, 128, 0, st, args..., (const char *)nullptr, (int *)nullptr, pf_flag);
+  else if (W <= 128) SF_LAUNCH((sf_pf_fast_kernel<128, 0>), grid, 128, 0, st, args..., (const char *)nullptr, (int *)nullptr, pf_flag);
+  else if (W == 200) SF_LAUNCH((sf_pf_fast_kernel<256, 200>), grid, 256, 0, st, args..., (const char *)nullptr, (int *)nullptr, pf_flag);
+  else SF_LAUNCH((sf_pf_fast_kernel<256, 0>), grid, 256, 0, st, args..., (const char *)nullptr, (int *)nullptr, pf_flag);
 }
 // constrained folds (a constraint row per fold); W <= 250
 #define SF_PFF_HC_MAXW 250

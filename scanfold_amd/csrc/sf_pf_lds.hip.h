@@ -161,7 +161,7 @@ __global__ __launch_bounds__(SF_PFL_NT) void sf_pf_lds_kernel(const uint8_t *__r
                                                               const uint8_t *__restrict__ tr, int L, int win0,
                                                               int step, int run_len, double *__restrict__ share,
                                                               const char *__restrict__ cons_rows,
-                                                              int *__restrict__ status) {
+                                                              int *__restrict__ status, int *__restrict__ pf_flag) {
   // SH (native windows of one transcript, `step` nucleotides apart, sf_scan): a workgroup takes RUNS of run_len
   // consecutive windows.  The inside tables of window w+1 are those of window w shifted by `step` rows and columns
   // plus `step` new columns — provided the ends of a window are treated like any other position
@@ -221,6 +221,7 @@ __global__ __launch_bounds__(SF_PFL_NT) void sf_pf_lds_kernel(const uint8_t *__r
   // read back by the same workgroup one window later; 32 workgroups per XCD x 102 kB = 3.3 MB stay in that XCD's 4-MB L2)
   double *sv = SH ? share + (size_t)((blockIdx.x & 7u) * ((gridDim.x + 7u) >> 3) + (blockIdx.x >> 3)) * SF_PFL_SHARE_DOUBLES(W) : nullptr;
   if (!shared) run_len = 1;
+  bool dirty = false;  // the previous fold of this workgroup left values past FP64's range in QB / QM
   for (int fold0 = blockIdx.x * run_len; fold0 < n; fold0 += gridDim.x * run_len)
   for (int fold = fold0; fold < fold0 + run_len && fold < n; fold++) {
     const bool resume = SH && fold > fold0;                          // the previous window's state is in sv
@@ -229,6 +230,10 @@ __global__ __launch_bounds__(SF_PFL_NT) void sf_pf_lds_kernel(const uint8_t *__r
     const int pos = (win0 + fold) * step;  // window start in the transcript
     const bool nbL = SH && pos > 0, nbR = SH && pos + W < L;
     __syncthreads();
+    if (dirty && !resume) {  // the speculative reads must find finite values (see above): inf * 0 would poison this fold
+      for (int x = tid; x < 2 * NC; x += SF_PFL_NT) QB[x] = 0.0;
+      __syncthreads();
+    }
     for (int x = tid; x < W; x += SF_PFL_NT) S[x + 1] = sf_encode_nt(src[x]);
     if (tid == 0) { S[0] = nbL ? sf_encode_nt(tr[pos - 1]) : 0; S[W + 1] = nbR ? sf_encode_nt(tr[pos + W]) : 0; }
     if (HC && cons_rows) {
@@ -1054,7 +1059,9 @@ __global__ __launch_bounds__(SF_PFL_NT) void sf_pf_lds_kernel(const uint8_t *__r
       if (ens_dG) ens_dG[fold] = -log(Z) * X->kT / 1000.0;
       if (mean_bp_dist) mean_bp_dist[fold] = 2.0 * mbd;
       if (centroid_dist) centroid_dist[fold] = cd;
+      if (pf_flag) pf_flag[fold] = sf_pf_out_of_range(Z);  // redone scaled by sf_pf_kernel<true>
     }
+    dirty = sf_pf_out_of_range(Z);  // (Z: q5[W] in LDS, the same for every lane)
   }
 #undef COFF
 #undef DOFF

@@ -105,12 +105,12 @@ PFSTAMP_PATCHES = [
     (PFL, "          } else cd += p;\n        }\n      }\n      SF_LANE_TABLE_PIN(tpk);\n      SF_LANE_TABLE_PIN(tcol);\n      __syncthreads();\n    }\n",
      "          } else cd += p;\n        }\n      }\n      SF_LANE_TABLE_PIN(tpk);\n      SF_LANE_TABLE_PIN(tcol);\n      if (SFL) atomicAdd(SFB + 3, (unsigned long long)(clock64() - SFT0));\n      __syncthreads();\n"
      "      if (SFL) { atomicAdd(SFB + 4, (unsigned long long)(clock64() - SFT0)); atomicAdd(SFB + 5, 1ull); }\n    }\n    SF_PH(43)\n"),
-    (PFL, "      if (centroid_dist) centroid_dist[fold] = cd;\n    }\n",
-     "      if (centroid_dist) centroid_dist[fold] = cd;\n    }\n    SF_PH(44)\n    if (SFL0) atomicAdd(SFP + 45, 1ull);\n"),
+    (PFL, "      if (pf_flag) pf_flag[fold] = sf_pf_out_of_range(Z);  // redone scaled by sf_pf_kernel<true>\n    }\n",
+     "      if (pf_flag) pf_flag[fold] = sf_pf_out_of_range(Z);  // redone scaled by sf_pf_kernel<true>\n    }\n    SF_PH(44)\n    if (SFL0) atomicAdd(SFP + 45, 1ull);\n"),
     (HOST, "    int rc = ensure(g.status, sizeof(int));\n    if (rc) return rc;\n    HIPCHK(hipMemset(g.status.p, 0, sizeof(int)));",
      "    int rc = ensure(g.status, 65536);\n    if (rc) return rc;\n    HIPCHK(hipMemset(g.status.p, 0, 65536));"),
-    (HOST, "                     d_dG, d_mbd, d_cen, d_cd, d_tr, L, win0, step, run_len, share, (const char *)nullptr, (int *)nullptr);\n",
-     "                     d_dG, d_mbd, d_cen, d_cd, d_tr, L, win0, step, run_len, share, (const char *)nullptr, (int *)g.status.p);\n"
+    (HOST, "                     d_dG, d_mbd, d_cen, d_cd, d_tr, L, win0, step, run_len, share, (const char *)nullptr, (int *)nullptr, d_flag);\n",
+     "                     d_dG, d_mbd, d_cen, d_cd, d_tr, L, win0, step, run_len, share, (const char *)nullptr, (int *)g.status.p, d_flag);\n"
      "    if (const char *so = getenv(\"SF_STAMP_OUT\")) {\n      static unsigned long long hb[8 * 64];\n      HIPCHK(hipStreamSynchronize(st));\n"
      "      HIPCHK(hipMemcpy(hb, (char *)g.status.p + 32768, sizeof hb, hipMemcpyDeviceToHost));\n"
      "      HIPCHK(hipMemset((char *)g.status.p + 32768, 0, sizeof hb));\n      if (FILE *f = fopen(so, \"a\")) {\n"

@@ -14,4 +14,4 @@
 #endif
 template __global__ void sf_pf_lds_kernel<PF_WT, PF_SH, false>(const uint8_t *, int, int, int, const SfDevParams *, const SfDevParamsPF *,
                                                                double *, double *, char *, double *, const uint8_t *, int, int, int, int,
-                                                               double *, const char *, int *);
+                                                               double *, const char *, int *, int *);
