@@ -169,6 +169,10 @@ static inline void sf_fast_build_params(const SfDevParams &D, SfFastParams &F) {
   upd(&P.TerminalAU, 1); upd(P.tetra_E, SF_NSPECIAL); upd(P.tri_E, SF_NSPECIAL); upd(P.hexa_E, SF_NSPECIAL);
   for (int s = 0; s <= SF_FAST_MAXW; s++) upd(&D.hp_init[s], 1);
   F.fast_ok = (mx <= SF_FAST_MAXPARAM) ? 1 : 0;
+  // this kernel adds ONE multiloop-stem term, MLintern[1] (SfFastCtx::MLintern), whatever the pair type: a set whose MLintern
+  // differs by type (possible through sf_params_load's blob; a .par file has a single value) goes to the int32 kernel
+  for (int t = 2; t < 8; t++)
+    if (P.MLintern[t] != P.MLintern[1]) F.fast_ok = 0;
   auto clamp16 = [](int v) { return (int16_t)(v > 32000 ? 32000 : (v < -32000 ? -32000 : v)); };
   for (int t = 0; t < 8; t++) {
     for (int a = 0; a < 5; a++) {

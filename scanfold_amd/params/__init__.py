@@ -349,10 +349,13 @@ def default_params():
 def random_params(seed, scale=200):
     """A randomised but symmetry-respecting set for index-order tests (oracle vs HIP vs evaluator).
 
-    Keeps loop-initiation arrays / constants of the default set and replaces every sequence-dependent
-    table by random integers, honouring stack[a][b]==stack[b][a],
+    Replaces every sequence-dependent table (stack, the six mismatch tables, dangles, int11 / int21 / int22, the
+    special-hairpin ENERGIES) by random integers, honouring stack[a][b]==stack[b][a],
     int11[a][b][x][y]==int11[b][a][y][x], int22[a][b][w][x][y][z]==int22[b][a][y][z][w][x]
-     — the symmetries a loop read from either strand relies on.
+     — the symmetries a loop read from either strand relies on.  Leaves alone, at the default set's
+    values: the loop-size tables hairpin / bulge / internal_loop, lxc, ninio / max_ninio, DuplexInit, the special-hairpin
+    sequences and their counts.  MLintern is ONE random value copied to every pair type, MLbase is 0, 10 or 20,
+    TerminalAU and MLclosing are positive.  (tests/par_util.py's random_params_full randomises all of those too.)
     """
     rng = np.random.default_rng(seed)
     p = default_params()

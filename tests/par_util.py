@@ -1,7 +1,8 @@
 """Test helper: write a parameter set as a ViennaRNA "RNAfold parameter file v2.0" in the PUBLISHED file's layout —
 free-energy section, then its `_enthalpies` twin, block comments before and after rows, dG / dH column pairs in
 NINIO / ML_params / Misc and in the special-loop lists.  (The real rna_turner2004.par is absent from this machine;
-this reproduces its format, not its numbers.)"""
+this reproduces its format, not its numbers.)  Also: fully randomised parameter sets for the kernel tests
+(random_params_full, boundary_params, random_enthalpies) and sequences with their special hairpins planted in them."""
 import numpy as np
 
 PAIRS = ["CG", "GC", "GU", "UG", "AU", "UA", "NS"]
@@ -100,6 +101,125 @@ def par_text(rec, dH=None, def_fields=None):
         out.append("")
     out += ["#END", ""]
     return "\n".join(out)
+
+
+SF_FAST_MAXPARAM = 2500  # sf_mfe_fast.hip.h: a set with a finite entry beyond this goes to the int32 kernel at every width
+SPECIAL_COUNTS = (0, 1, 7, 8, 9, 40)  # the MFE kernel scans special-hairpin keys in blocks of eight
+_CANON = ("CG", "GC", "GU", "UG", "AU", "UA")
+_MM = ("mismatchI", "mismatchH", "mismatchM", "mismatch1nI", "mismatch23I", "mismatchExt")
+_SPECIALS = (("tetra_seq", "tetra_E", "n_tetra", 6), ("tri_seq", "tri_E", "n_tri", 5), ("hexa_seq", "hexa_E", "n_hexa", 8))
+
+
+def _special_seqs(rng, n, length, taken):
+    """n distinct loop strings of `length` letters closed by a canonical pair, none of them in `taken`."""
+    out = []
+    while len(out) < n:
+        cp = _CANON[rng.integers(0, 6)]
+        s = cp[0] + "".join("ACGU"[k] for k in rng.integers(0, 4, length - 2)) + cp[1]
+        if s not in taken:
+            taken.add(s)
+            out.append(s)
+    return out
+
+
+def random_params_full(seed, counts=None):
+    """params.random_params(seed) with EVERY field the model reads randomised as well: hairpin[3..30], bulge[1..30],
+    internal_loop[2..30], lxc, ninio / max_ninio, MLintern per pair type, MLbase and TerminalAU of either sign, MLclosing,
+    the dangles, the six mismatch tables and the special hairpins — energies and sequences, each closed by a canonical pair,
+    all 40 slots filled (a reader past n_* finds plausible keys there), n_tetra / n_tri / n_hexa drawn from SPECIAL_COUNTS
+    unless `counts` = (n_tetra, n_tri, n_hexa) is given.  Keeps the symmetries of random_params; its stacks are halved.  Every finite entry, the
+    hairpin initiation extrapolated to 256 nt included, stays within SF_FAST_MAXPARAM, so W <= 256 runs on the int16 kernel."""
+    from scanfold_amd import params
+    p = params.random_params(seed)
+    r = p.rec
+    rng = np.random.default_rng([seed, 0x7ab1e5])
+    r["stack"] = r["stack"] // 2  # (random_params' stacks alone fold 256-mers below the int16 kernel's range)
+    r["hairpin"][3:31] = rng.integers(150, 800, 28)
+    r["bulge"][1:31] = rng.integers(0, 700, 30)
+    r["internal_loop"][2:31] = rng.integers(0, 700, 29)
+    r["lxc"] = float(rng.uniform(40.0, 160.0))
+    r["ninio"] = int(rng.integers(0, 120))
+    r["max_ninio"] = int(rng.integers(0, 500))
+    ml = rng.integers(-250, 60, 8)
+    if (ml[1:8] == ml[1]).all():
+        ml[2] += 37
+    r["MLintern"] = ml
+    r["MLbase"] = int(rng.integers(-40, 50))
+    r["TerminalAU"] = int(rng.integers(-80, 120))
+    r["MLclosing"] = int(rng.integers(-300, 1000))
+    r["dangle5"] = rng.integers(-100, 30, (8, 5))
+    r["dangle3"] = rng.integers(-100, 30, (8, 5))
+    for f in _MM:
+        r[f] = rng.integers(-150, 60, (8, 5, 5))
+    if counts is None:
+        counts = [SPECIAL_COUNTS[k] for k in rng.integers(0, len(SPECIAL_COUNTS), 3)]
+    taken = set()
+    for (fseq, fe, fn, ln), n in zip(_SPECIALS, counts):
+        r[fseq] = [s.encode() for s in _special_seqs(rng, params.MAX_SPECIAL, ln, taken)]
+        r[fe] = rng.integers(-500, 500, params.MAX_SPECIAL)
+        r[fn] = int(n)
+    p.source = "random_params_full(%d)" % seed
+    return p
+
+
+def boundary_params(seed, top=SF_FAST_MAXPARAM):
+    """random_params_full(seed) with one MLintern for every pair type (the int16 kernel's condition besides magnitude) and
+    its largest entries at +SF_FAST_MAXPARAM: ninio and max_ninio, every third internal_loop size, every fourth mismatchI
+    entry, the odd hairpin sizes 3..29.  top > SF_FAST_MAXPARAM puts that value on ONE entry, internal_loop[17]: the set then
+    goes to the int32 kernel at every width."""
+    p = random_params_full(seed)
+    r = p.rec
+    r["MLintern"] = r["MLintern"][1]
+    M = SF_FAST_MAXPARAM
+    r["ninio"] = M
+    r["max_ninio"] = M
+    r["internal_loop"][4:31:3] = M
+    mi = r["mismatchI"].copy()
+    mi.reshape(-1)[::4] = M
+    r["mismatchI"] = mi
+    r["hairpin"][3:30:2] = M
+    r["internal_loop"][17] = top
+    p.source = "boundary_params(%d, %d)" % (seed, top)
+    return p
+
+
+def max_finite_entry(rec, W=256):
+    """Largest |entry| below INF that the int16 kernel's magnitude check sees (sf_fast_build_params), with the hairpin
+    initiation extrapolated to W nucleotides."""
+    fields = ("stack", "hairpin", "bulge", "internal_loop", "dangle5", "dangle3", "int11", "int21", "int22", "ninio",
+              "max_ninio", "MLbase", "MLclosing", "MLintern", "TerminalAU", "tetra_E", "tri_E", "hexa_E") + _MM
+    v = np.concatenate([np.abs(np.asarray(rec[f], dtype=np.int64)).reshape(-1) for f in fields])
+    ext = int(rec["hairpin"][30]) + int(float(rec["lxc"]) * np.log(W / 30.0))
+    return max(int(v[v < INF].max()), abs(ext))
+
+
+def plant_specials(rng, arr, p, per_row=3):
+    """A copy of `arr` (uint8 ASCII, (n, W)) with special-hairpin strings of `p` written over each row at random places:
+    mostly entries in use (slot < n_*), some from the unused slots behind them (they must NOT count)."""
+    used, unused = [], []
+    for fseq, _, fn, _ in _SPECIALS:
+        n = int(p.rec[fn])
+        for k, s in enumerate(p.rec[fseq]):
+            (used if k < n else unused).append(bytes(s))
+    out = np.array(arr, dtype=np.uint8, copy=True)
+    W = out.shape[1]
+    for row in out:
+        for _ in range(per_row):
+            pool = used if used and (not unused or rng.random() < 0.8) else unused
+            s = pool[int(rng.integers(0, len(pool)))]
+            at = int(rng.integers(0, W - len(s) + 1))
+            row[at:at + len(s)] = np.frombuffer(s, dtype=np.uint8)
+    return out
+
+
+def random_enthalpies(rec, seed):
+    """synthetic_enthalpies with the scalar fields random too (MLintern per pair type): for ParamSet.at_temperature."""
+    rng = np.random.default_rng([seed, 0xe47])
+    dH = synthetic_enthalpies(rec, seed)
+    for f in ("ninio", "MLbase", "MLclosing", "TerminalAU", "DuplexInit"):
+        dH[f] = 3 * int(rec[f]) - int(rng.integers(0, 40)) * 10
+    dH["MLintern"] = 3 * rec["MLintern"].astype(np.int64) - rng.integers(0, 40, 8) * 10
+    return dH
 
 
 def synthetic_enthalpies(rec, seed=0):
