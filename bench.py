@@ -15,8 +15,15 @@ process (never exec), relays the child's JSON line and exits with its code.
 Workload at N=1: BASELINE.json configs[2] ("30 kb, W=120, step=1, 100 shuffles on 1 MI355X") — the configuration
 the metric is quoted on; it fits one GPU.
 
-After the timed region rank 0 checks 64 windows of the last step against the oracle ("verified_windows"), and at
-N=1 adds an "e2e" block (the CLI's whole path: H2D, kernels, D2H, z/p-scores, TSV rows) and the CPU baseline.
+A plain run does what the headline figure needs and no more: set-up, warm-up, the timed steps, --dump-outputs when asked,
+the result line.  Its roofline block costs no run of its own: HIP events around the MFE launches of the timed steps and the
+counters committed under profiles/.
+
+With --full rank 0 goes on after the timed region: it checks 64 windows of the last step against the oracle
+("verified_windows"; with several ranks on the gathered records, "gather_check"), at N=1 takes the roofline's traffic and
+unit counters live (rocprofv3 --pmc child runs of ONE scan of the same workload) and adds an "e2e" block (the CLI's whole
+path: H2D, kernels, D2H, z/p-scores, TSV rows) and the CPU baseline.  The timed region and the headline fields (metric,
+value, unit, higher_is_better, dtype, ms_per_step) are the same either way; "full" in the line says which run it was.
 
 Prints ONE JSON line on rank 0.
 """
@@ -86,6 +93,8 @@ def relaunch_under_torchrun(args):
     cmd += ["--config", args.config, "--shuffle", args.shuffle or "", "--input", args.input]
     if args.dump_outputs:
         cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
+    if args.full:
+        cmd.append("--full")
     if args.no_live_counters:
         cmd.append("--no-live-counters")
     if args.no_cpu_baseline:
@@ -395,10 +404,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: the check of the last step "
+                         "against the oracle (of the gathered records with several ranks), live rocprofv3 --pmc counter passes "
+                         "for the roofline block, the end-to-end runs and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--no-live-counters", action="store_true",
-                    help="take roofline.traffic from the committed profiles/ file instead of two live rocprofv3 --pmc child "
-                         "runs (use when bench.py itself runs under rocprofv3)")
+                    help="with --full: take roofline.traffic from the committed profiles/ file, as a plain run does, instead of "
+                         "live rocprofv3 --pmc child runs (use when bench.py itself runs under rocprofv3)")
     ap.add_argument("--config", choices=sorted(WORKLOADS), default="cfg3",
                     help="cfg3 (default, the metric's own configuration), cfg5 (W=200, r=1000, partition function), or the "
                          "small parity shapes cfg1 / cfg2")
@@ -546,7 +559,7 @@ def main():
             secondary.update(calibrated_unit_fractions(secondary, W, folds_per_launch, avg_ms, eng))
         traffic_src = counters_src and (counters_src + " (rocprofv3 --pmc passes of an earlier run, committed)")
         secondary_src = counters_src and (counters_src + " (SQ counter passes of an earlier run, committed)")
-        if world == 1 and not args.no_live_counters:
+        if args.full and world == 1 and not args.no_live_counters:
             # cfg5's step is half a minute: its counters are taken on the first 2 000 windows of the same scan
             live, why = live_counters_per_fold(args.config, args.shuffle, args.input,
                                                ["FETCH_SIZE", "WRITE_SIZE", "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_LDS_IDX_ACTIVE",
@@ -568,11 +581,13 @@ def main():
                 secondary.update(calibrated_unit_fractions(secondary, W, folds_per_launch, avg_ms, eng))
             else:
                 traffic_src = (traffic_src or "none") + "; live measurement failed: " + why
-        gather_check = None
-        if use_dist and gathered is not None:
-            # what the RCCL all-gather delivered, un-padded and put back into window order, against (i) this rank's own
-            # device tensors for its shard and (ii) the oracle on windows spread over EVERY rank's shard (below)
+        gather_check, merged, checked, bad = None, None, 0, 0
+        if use_dist and gathered is not None and (args.full or args.dump_outputs):
+            # what the RCCL all-gather delivered, un-padded and put back into window order
             merged = sdist.merge_shards(gathered, n_win, world, W, r)
+        if args.full and merged is not None:
+            # the gathered records against (i) this rank's own device tensors for its shard and (ii) the oracle on windows
+            # spread over EVERY rank's shard (below)
             mine = slice(lo, hi)
             same = bool((merged["energies"][mine] == en[:n_loc].cpu().numpy()).all()
                         and (merged["structure"][mine] == db[:n_loc].cpu().numpy()).all()
@@ -594,12 +609,12 @@ def main():
                                                           for a, b in gather_check["shard_ranges"]]
             if not same:
                 bad += 1
-        else:
+        elif args.full:
             checked, bad = verify_sample(seq, W, step, r, kind, wl["shuffle_seed"], lo, n_loc, en, db, cen, div, wl["verify"],
                                          engine=wl.get("verify_engine", "checker"))
         if args.dump_outputs:
             # one rank: its shard is every window; several: the gathered records of all shards
-            computed = merged if gather_check is not None else {
+            computed = merged if merged is not None else {
                 "energies": en[:n_loc].cpu().numpy(), "structure": db[:n_loc].cpu().numpy(),
                 "centroid": cen[:n_loc].cpu().numpy(), "ens_div": div[:n_loc].cpu().numpy(),
                 "ens_dG": dG[:n_loc].cpu().numpy()}
@@ -610,7 +625,7 @@ def main():
             "value": value, "unit": "windows/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "strong",
             "vs_baseline": None, "dtype": "int32 (int16 LDS storage) energies; f64 partition function",
-            "data": "synthetic",
+            "data": "synthetic", "full": args.full,
             "config": {"workload": wl["name"], "L": wl["L"], "W": W, "step": step, "shuffles": r,
                        "shuffle_type": wl["shuffle"], "windows": n_win, "mfe_folds_per_step": n_win * (r + 1),
                        "parallelism": "windows sharded over %d rank(s), one all-gather per step" % world},
@@ -627,19 +642,21 @@ def main():
                                  "the kernel is in `secondary`",
                          "secondary": secondary,
                          "mfe_kernel_share_of_step": (kern_ms * 1e-3) / elapsed},
-            "verified_windows": checked, "verified_mismatches": bad, "device_status": dev_status,
-            "gather_check": gather_check,
-            "verified_against": "oracle (%s + sf_shuffle_oracle.c): all %d energies, structure, centroid, "
-                                "ensemble diversity of %d windows of the last timed step%s"
-                                % ("sf_cpu_twin.c, the CPU engine tests/test_oracle.py holds equal to the checker sf_oracle.c,"
-                                   if wl.get("verify_engine") == "twin" else "sf_oracle.c",
-                                   r + 1, checked, " (taken from the gathered records of all ranks)" if gather_check else ""),
+            "device_status": dev_status,
             "params": eng.params.source and os.path.basename(eng.params.source),
             "device": eng.device_name(),
         }
+        if args.full:
+            out.update({
+                "verified_windows": checked, "verified_mismatches": bad, "gather_check": gather_check,
+                "verified_against": "oracle (%s + sf_shuffle_oracle.c): all %d energies, structure, centroid, "
+                                    "ensemble diversity of %d windows of the last timed step%s"
+                                    % ("sf_cpu_twin.c, the CPU engine tests/test_oracle.py holds equal to the checker sf_oracle.c,"
+                                       if wl.get("verify_engine") == "twin" else "sf_oracle.c",
+                                       r + 1, checked, " (taken from the gathered records of all ranks)" if gather_check else "")})
         if bad or dev_status:
             rc = 4
-        if world == 1:
+        if args.full and world == 1:
             from scanfold_amd import scan as scanmod
             times, nbytes = [], 0
             n_e2e = 5 if args.config == "cfg3" else 1

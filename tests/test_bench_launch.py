@@ -32,6 +32,33 @@ def test_gpus_2_spawns_two_ranks_and_fails_only_at_device_selection():
     assert '"metric"' not in out.stdout
 
 
+def test_full_is_an_option_and_reaches_the_ranks(monkeypatch):
+    """--full (what a plain run leaves out: oracle check, live counters, end-to-end runs, CPU baseline) parses, is off by
+    default, and the ranks that `--gpus 2` starts are given it: they stop at device selection, not at their command line."""
+    import bench
+    import torch
+    out = run_bench("--gpus", "1", "--full", "--steps", "0")
+    assert out.returncode == 2 and "--steps must be at least 1" in out.stderr and "unrecognized" not in out.stderr
+    helptext = run_bench("--help").stdout
+    assert "--full" in helptext
+    seen = {}
+
+    def fake_run(cmd, **kw):
+        seen["cmd"] = cmd
+        return subprocess.CompletedProcess(cmd, 0, stdout='{"metric": "m"}\n')
+    with monkeypatch.context() as m:
+        m.setattr(bench.subprocess, "run", fake_run)
+        for full in (False, True):
+            args = bench.argparse.Namespace(gpus=2, steps=1, warmup=0, config="cfg2", shuffle="", input="uniform",
+                                            dump_outputs="", full=full, no_live_counters=False, no_cpu_baseline=True)
+            assert bench.relaunch_under_torchrun(args) == 0
+            assert ("--full" in seen["cmd"]) is full
+    if torch.cuda.device_count() < 2:
+        out = run_bench("--gpus", "2", "--full", "--steps", "1", "--warmup", "0")
+        assert out.returncode != 0 and "unrecognized" not in out.stderr
+        assert "rank 0: --gpus 2 needs 2 GPUs" in out.stderr, out.stderr[-3000:]
+
+
 def test_world_size_mismatch_is_reported():
     out = run_bench("--gpus", "1", env={"RANK": "0", "WORLD_SIZE": "2", "LOCAL_RANK": "0"})
     assert out.returncode == 2 and "WORLD_SIZE=2" in out.stderr

@@ -45,14 +45,14 @@ def expected_rows(oracle, seq, W, step, r, kind, seed):
 
 
 def test_bench_single_rank_over_rccl_cfg2():
-    """bench.py --config cfg2 as one rank under torch.distributed.run: init_process_group("nccl"), pack_records on the device,
-    all_gather_into_tensor, merge_shards — and 64 windows of what the gather delivered == oracle."""
+    """bench.py --full --config cfg2 as one rank under torch.distributed.run: init_process_group("nccl"), pack_records on the
+    device, all_gather_into_tensor, merge_shards — and 64 windows of what the gather delivered == oracle."""
     with socket.socket() as so:
         so.bind(("127.0.0.1", 0))
         port = so.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0",
-           "--no-live-counters", "--no-cpu-baseline", "--config", "cfg2"]
+           "--full", "--no-live-counters", "--no-cpu-baseline", "--config", "cfg2"]
     env = dict(os.environ, SCANFOLD_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-3000:])
@@ -60,6 +60,7 @@ def test_bench_single_rank_over_rccl_cfg2():
     assert len(lines) == 1, p.stdout[-2000:]
     out = json.loads(lines[0])
     assert out["n_gpus"] == 1 and out["config"]["windows"] == 989 and out["config"]["mfe_folds_per_step"] == 30659
+    assert out["full"] is True and out["e2e"]["runs"] == 1 and out["e2e"]["windows_per_s"] > 0
     gc = out["gather_check"]
     assert gc is not None and gc["backend"] == "nccl" and gc["ranks"] == 1 and gc["windows"] == 989
     assert gc["rank0_shard_equals_its_device_tensors"] is True
@@ -70,7 +71,8 @@ def test_bench_single_rank_over_rccl_cfg2():
 
 def test_bench_dump_outputs_are_what_the_timed_path_computed_cfg1(gpu_engine, oracle, tmp_path):
     """bench.py --dump-outputs on one rank: the per-window arrays of the last of --steps timed steps, equal to what the engine
-    computes for the same workload through sf_scan, and to the oracle's whole per-window job on the same shuffles."""
+    computes for the same workload through sf_scan, and to the oracle's whole per-window job on the same shuffles.  The run is
+    a plain one (no --full): its line carries the headline and nothing that the steps did not measure."""
     d = tmp_path / "dump"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "0", "--no-live-counters",
            "--no-cpu-baseline", "--config", "cfg1", "--dump-outputs", str(d)]
@@ -79,6 +81,10 @@ def test_bench_dump_outputs_are_what_the_timed_path_computed_cfg1(gpu_engine, or
     assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-3000:])
     out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln][0])
     assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["config"]["windows"] == 23
+    assert abs(out["value"] - 23 / (out["ms_per_step"] * 1e-3)) < 1e-6 * out["value"] and out["unit"] == "windows/s"
+    assert out["full"] is False and out["device_status"] == 0
+    assert not {"verified_windows", "verified_mismatches", "gather_check", "e2e", "cpu_baseline"} & set(out)
+    assert "live" not in (out["roofline"]["traffic_source"] or "") and out["roofline"]["launches"] == 3
     got = {f[:-4]: np.load(d / f) for f in os.listdir(d)}
     assert sorted(got) == ["centroid", "energies", "ens_dG", "ens_div", "structure", "window_index"]
     assert (got["window_index"] == np.arange(23)).all()
@@ -95,7 +101,7 @@ def test_bench_dump_outputs_are_what_the_timed_path_computed_cfg1(gpu_engine, or
 
 
 def test_bench_two_ranks_on_gpu0_over_gloo_cfg2():
-    """bench.py with world == 2 on REAL device tensors (the code the driver's multi-GPU run is the first to execute with
+    """bench.py --full with world == 2 on REAL device tensors (the code the driver's multi-GPU run is the first to execute with
     world > 1): both ranks on GPU 0 — RCCL refuses two ranks on one device, so the collective runs over gloo, staged through
     the host for the exchange only (SCANFOLD_DIST_BACKEND=gloo, dist.gather_records) — `pack_records` on the device, one
     all-gather, `merge_shards`; the verified windows come from BOTH shards of the gathered tensor and the elapsed time in the
@@ -105,7 +111,7 @@ def test_bench_two_ranks_on_gpu0_over_gloo_cfg2():
         port = so.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--no-live-counters", "--no-cpu-baseline", "--config", "cfg2"]
+           "--full", "--no-live-counters", "--no-cpu-baseline", "--config", "cfg2"]
     env = dict(os.environ, SCANFOLD_DIST_BACKEND="gloo", SCANFOLD_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("SCANFOLD_BENCH_FORCE_DIST", None)
     p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)

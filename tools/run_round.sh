@@ -2,7 +2,7 @@
 # One round's measurement set, parameterised by the round tag (replaces r02_run.sh / r03_run.sh / r03_cfg5.sh / r04_run.sh /
 # r04_final.sh / r04_collect.sh / final_run.sh).  Run on the GPU box through gpurun; `collect` runs in the build container.
 #
-#   bash tools/run_round.sh measure RR cfg3|cfg5 [extra bench flags]   bench.py --config C (live counters on), the same under
+#   bash tools/run_round.sh measure RR cfg3|cfg5 [extra bench flags]   bench.py --full --config C (live counters on), the same under
 #        rocprofv3 --kernel-trace --stats, and six counter passes of tools/gpu_scan_only.py C — ONE scan of the timed workload, no
 #        warm-up launch, so that the counters are the timed kernel's — summarised in gpurun_out/RR_final/C/[C_]mfe_counters.json
 #   bash tools/run_round.sh final RR       the GPU test suite, `measure` for cfg3 and cfg5, the secondary workloads of SURVEY 8d
@@ -23,8 +23,8 @@ measure() {
   [ "$C" = cfg5 ] && WIN="--windows 2000"
   cd /tmp && export TMPDIR=/tmp
   mkdir -p $O
-  python3 $R/bench.py --config $C "$@" > $O/${P}bench.json 2> $O/${P}bench.err
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 $R/bench.py --config $C --no-cpu-baseline --no-live-counters "$@" > $O/${P}bench_under_rocprof.json 2>/dev/null
+  python3 $R/bench.py --full --config $C "$@" > $O/${P}bench.json 2> $O/${P}bench.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 $R/bench.py --full --config $C --no-cpu-baseline --no-live-counters "$@" > $O/${P}bench_under_rocprof.json 2>/dev/null
   local k=0
   for c in "FETCH_SIZE" "WRITE_SIZE" "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_LDS_IDX_ACTIVE" "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY" "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_THREAD_CYCLES_VALU SQ_LDS_BANK_CONFLICT" "GRBM_GUI_ACTIVE SQ_BUSY_CYCLES"; do
     k=$((k+1))
@@ -82,8 +82,8 @@ final() {
   measure cfg3 > $S/cfg3.log 2>&1
   measure cfg5 > $S/cfg5.log 2>&1
   cd $R
-  python3 bench.py --shuffle mono --no-cpu-baseline > $S/bench_mono.json 2> $S/bench_mono.err
-  python3 bench.py --input viral --no-cpu-baseline > $S/bench_viral.json 2> $S/bench_viral.err
+  python3 bench.py --full --shuffle mono --no-cpu-baseline > $S/bench_mono.json 2> $S/bench_mono.err
+  python3 bench.py --full --input viral --no-cpu-baseline > $S/bench_viral.json 2> $S/bench_viral.err
   python3 tools/gpu_shard_step.py cfg3 > $S/shard_step_cfg3.txt 2>&1
   python3 tools/gpu_shard_step.py cfg5 --windows 4096 --reps 1 > $S/shard_step_cfg5_first_4096_windows.txt 2>&1
   for f in cfg3/bench.json cfg5/cfg5_bench.json bench_mono.json bench_viral.json; do python3 -c "
