@@ -6,7 +6,8 @@ RNA.fold(seq) :245.  Energies come back as ViennaRNA returns them: (float)dcal /
 md.max_bp_span (ScanFold.py:214-215) is honoured (sf_set_max_bp_span).
 md.temperature other than 37 needs a parameter set with enthalpy tables (params.load_par of a real .par file).
 fc.hc_add_from_db and fc.sc_add_SHAPE_deigan (ScanFold-Scan.py:410; ScanFold.py:512,534) are provided through
-sf_fold_constrained.  Not provided: duplexfold, plotting, Zarringhalam soft constraints (upstream's call fails too).
+sf_fold_constrained.  RNA.duplexfold(s1, s2) (ScanFold.py:785; ScanFoldFunctions.py:824) folds through sf_duplex_batch.
+Not provided: plotting, Zarringhalam soft constraints (upstream's call fails too).
 Sequences longer than SF_MAX_W (400 nt, the window kernels' limit) fold with fc.mfe() / RNA.fold through sf_fold_long
 (whole records up to 32 767 nt: ScanFold.py --global_refold, :1509-1547), hc_add_from_db included; their partition
 function, centroid and SHAPE term do not exist and raise NotImplementedError.
@@ -140,3 +141,24 @@ def fold(sequence):
 
 def pf_fold(sequence):
     return fold_compound(sequence).pf()
+
+
+class duplexT:
+    """What RNA.duplexfold returns: .energy (kcal/mol), .structure ("((.&.))"), .i (3' end of the strand-1 part, 1-based),
+    .j (5' end of the strand-2 part).  Two strands that cannot form a pair: ViennaRNA leaves its minimum at INF, so .energy
+    is (float)INF / 100 = 100000.0, with structure "&" and i = j = 0 here."""
+
+    def __init__(self, energy, structure, i, j):
+        self.energy, self.structure, self.i, self.j = energy, structure, i, j
+
+    def __repr__(self):
+        return "duplexT(energy=%r, structure=%r, i=%r, j=%r)" % (self.energy, self.structure, self.i, self.j)
+
+
+def duplexfold(s1, s2):
+    """RNA.duplexfold(s1, s2): the minimum-energy duplex of two strands of at most SF_DUPLEX_MAX_LEN nucleotides (only
+    inter-strand pairs), at the engine's resident model (37 C unless a fold_compound with another md was made before)."""
+    eng = _lib.get_engine()
+    r = eng.duplex_batch([str(s1)], [str(s2)])
+    e = int(r["energy"][0])
+    return duplexT(_f32(10000000 if e == _lib.SF_DUPLEX_NONE else e), r["structure"][0], int(r["i"][0]), int(r["j"][0]))

@@ -81,12 +81,46 @@ _LONG_EXPORTS = {
 }
 
 
+# include/scanfold_hip_duplex.h: likewise optional (duplex folds and the LRI scan)
+_DUPLEX_EXPORTS = {
+    "sf_duplex_batch": (ctypes.c_int, [_c_u8p, _c_u8p, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 6),
+    "sf_lri_grid": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int32),
+                                   ctypes.POINTER(ctypes.c_int32)]),
+    "sf_lri_scan": (ctypes.c_int, [_c_u8p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int32, ctypes.c_int64,
+                                   ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p, ctypes.c_void_p,
+                                   ctypes.c_void_p]),
+    "sf_lri_scan_time": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]),
+    "sf_lri_background": (ctypes.c_int, [_c_u8p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_void_p,
+                                         ctypes.c_void_p, ctypes.c_void_p]),
+}
+# one compacted hit of sf_lri_scan (struct sf_lri_hit)
+LRI_HIT_DTYPE = np.dtype([("j_win", np.int32), ("k_win", np.int32), ("energy", np.int32), ("i", np.int32),
+                          ("j", np.int32)])
+
+
+def _header_value(header, name):
+    """like _header_define for a `#define name` whose value is signed or a parenthesised integer expression"""
+    import re
+    path = os.path.join(os.path.dirname(_HERE), "include", header)
+    with open(path) as f:
+        m = re.search(r"^#define\s+%s\s+([-+0-9() ]+?)\s*(?:/\*|$)" % name, f.read(), flags=re.M)
+    if m is None:
+        raise ScanFoldHipError("%s defines no integer %s" % (path, name))
+    return int(eval(m.group(1), {"__builtins__": {}}))
+
+
 class ScanFoldHipError(RuntimeError):
     pass
 
 
 SF_MAX_W = _header_define("scanfold_hip.h", "SF_MAX_W")  # longest window of the window kernels
 SF_MAX_LONG = _header_define("scanfold_hip_long.h", "SF_MAX_LONG")  # longest sequence of sf_fold_long
+SF_DUPLEX_MAX_LEN = _header_define("scanfold_hip_duplex.h", "SF_DUPLEX_MAX_LEN")  # longest strand of a duplex
+SF_DUPLEX_STRUCT_LEN = _header_define("scanfold_hip_duplex.h", "SF_DUPLEX_STRUCT_LEN")
+SF_DUPLEX_NONE = _header_define("scanfold_hip_duplex.h", "SF_DUPLEX_NONE")  # "energy" of strands that cannot pair
+SF_DUPLEX_SKIPPED = _header_value("scanfold_hip_duplex.h", "SF_DUPLEX_SKIPPED")  # dense scan: left out by the distance test
+SF_ERR_DUPLEX_HITS = _header_value("scanfold_hip_duplex.h", "SF_ERR_DUPLEX_HITS")
 
 
 def _share_hip_runtime_with_torch():
@@ -122,7 +156,7 @@ def load_library(path=LIB_PATH):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
-    for name, (res, args) in _LONG_EXPORTS.items():
+    for name, (res, args) in list(_LONG_EXPORTS.items()) + list(_DUPLEX_EXPORTS.items()):
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype = res
@@ -285,6 +319,99 @@ class Engine:
         t = [ctypes.c_double() for _ in range(3)]
         self._check(self.lib.sf_fold_long_times(*(ctypes.byref(x) for x in t)))
         return tuple(x.value for x in t)
+
+    # -- duplex folds and the LRI scan (include/scanfold_hip_duplex.h) --
+    def has_duplex(self):
+        return all(getattr(self.lib, name, None) is not None for name in _DUPLEX_EXPORTS)
+
+    def _need_duplex(self):
+        if not self.has_duplex():
+            raise ScanFoldHipError("this library (%s) has no duplex entry points (sf_duplex_batch, sf_lri_scan, "
+                                   "sf_lri_background): duplex folds and --lri need libscanfold_hip.so"
+                                   % getattr(self.lib, "_name", "?"))
+
+    def duplex_batch(self, s1, s2, structure=True):
+        """RNA.duplexfold(s1[p], s2[p]) for every p (ScanFold.py:785) -> dict(energy int32 dcal/mol or SF_DUPLEX_NONE,
+        i, j int32 (duplexT's .i / .j), structure [str] or None).  Strands of 0..SF_DUPLEX_MAX_LEN nucleotides, mixed freely."""
+        self._need_duplex()
+        a = [s if isinstance(s, (bytes, bytearray)) else str(s).encode("ascii") for s in s1]
+        b = [s if isinstance(s, (bytes, bytearray)) else str(s).encode("ascii") for s in s2]
+        if len(a) != len(b):
+            raise ValueError("one strand 2 per strand 1")
+        n = len(a)
+        ld = max([1] + [len(s) for s in a] + [len(s) for s in b])
+        if ld > SF_DUPLEX_MAX_LEN:
+            raise ValueError("a duplex strand is at most %d nucleotides" % SF_DUPLEX_MAX_LEN)
+        m1 = np.zeros((n, ld), dtype=np.uint8)
+        m2 = np.zeros((n, ld), dtype=np.uint8)
+        for p in range(n):
+            m1[p, :len(a[p])] = np.frombuffer(bytes(a[p]), dtype=np.uint8)
+            m2[p, :len(b[p])] = np.frombuffer(bytes(b[p]), dtype=np.uint8)
+        l1 = np.array([len(s) for s in a], dtype=np.int32)
+        l2 = np.array([len(s) for s in b], dtype=np.int32)
+        e, ri, rj = (np.zeros(n, dtype=np.int32) for _ in range(3))
+        st = np.zeros((n, SF_DUPLEX_STRUCT_LEN), dtype=np.uint8) if structure else None
+        self._check(self.lib.sf_duplex_batch(m1.ctypes.data, m2.ctypes.data, n, ld, l1.ctypes.data, l2.ctypes.data,
+                                             e.ctypes.data, ri.ctypes.data, rj.ctypes.data,
+                                             None if st is None else st.ctypes.data))
+        return dict(energy=e, i=ri, j=rj,
+                    structure=None if st is None else [bytes(r).split(b"\0")[0].decode() for r in st])
+
+    def lri_grid(self, L, kmer, step):
+        """-> (n_j, n_k): j_win = jx * step, k_win = kx * step of the reference's two loops (ScanFold.py:774,780)"""
+        self._need_duplex()
+        nj, nk = ctypes.c_int32(), ctypes.c_int32()
+        self._check(self.lib.sf_lri_grid(int(L), int(kmer), int(step), ctypes.byref(nj), ctypes.byref(nk)))
+        return nj.value, nk.value
+
+    def lri_scan(self, seq, kmer, step, cutoff_dcal, max_hits=1 << 20, dense=False):
+        """The all-pairs k-mer duplex scan (ScanFold.py:773-812).  Compacted (default): the pairs with Emin < cutoff_dcal as
+        a LRI_HIT_DTYPE array sorted by (j_win, k_win); more than max_hits raises ScanFoldHipError.  dense=True: dict(energy,
+        i, j) of int32 (n_j, n_k) arrays, SF_DUPLEX_SKIPPED where the distance test fails (small records: tests)."""
+        self._need_duplex()
+        s = np.frombuffer(seq.encode("ascii") if isinstance(seq, str) else bytes(seq), dtype=np.uint8)
+        if dense:
+            nj, nk = self.lri_grid(len(s), kmer, step)
+            e, ri, rj = (np.zeros((nj, nk), dtype=np.int32) for _ in range(3))
+            if nj and nk:
+                self._check(self.lib.sf_lri_scan(s.ctypes.data, len(s), kmer, step, int(cutoff_dcal), 0, None, None,
+                                                 e.ctypes.data, ri.ctypes.data, rj.ctypes.data))
+            return dict(energy=e, i=ri, j=rj)
+        hits = np.zeros(max(int(max_hits), 1), dtype=LRI_HIT_DTYPE)
+        n = ctypes.c_int64(0)
+        rc = self.lib.sf_lri_scan(s.ctypes.data, len(s), kmer, step, int(cutoff_dcal), int(max_hits), hits.ctypes.data,
+                                  ctypes.byref(n), None, None, None)
+        if rc == SF_ERR_DUPLEX_HITS:
+            raise ScanFoldHipError("%s: %d pairs are below the cutoff, max_hits is %d"
+                                   % (self.lib.sf_strerror(rc).decode(), n.value, max_hits))
+        self._check(rc)
+        return hits[:n.value].copy()
+
+    def lri_scan_time(self):
+        """-> (ms of the scan kernels of the last lri_scan by device events, duplexes they folded)"""
+        self._need_duplex()
+        ms, nd = ctypes.c_double(), ctypes.c_int64()
+        self._check(self.lib.sf_lri_scan_time(ctypes.byref(ms), ctypes.byref(nd)))
+        return ms.value, nd.value
+
+    def lri_background(self, seq, kmer, j_win, k_win, r, kind, seed, rows=False):
+        """cofold_energies(frag, [dup_frag] + scramble(dup_frag, r, type)) for every hit (ScanFold.py:813-817) -> int32
+        (n_hits, r+1) energies; rows=True: (energies, rows1, rows2), the folded strands as uint8 codes (n_hits, r+1, kmer)."""
+        self._need_duplex()
+        s = np.frombuffer(seq.encode("ascii") if isinstance(seq, str) else bytes(seq), dtype=np.uint8)
+        jw = np.ascontiguousarray(j_win, dtype=np.int32)
+        kw = np.ascontiguousarray(k_win, dtype=np.int32)
+        if jw.shape != kw.shape or jw.ndim != 1:
+            raise ValueError("one k_win per j_win")
+        n = len(jw)
+        en = np.zeros((n, r + 1), dtype=np.int32)
+        r1 = np.zeros((n, r + 1, kmer), dtype=np.uint8) if rows else None
+        r2 = np.zeros((n, r + 1, kmer), dtype=np.uint8) if rows else None
+        self._check(self.lib.sf_lri_background(s.ctypes.data, len(s), int(kmer), jw.ctypes.data, kw.ctypes.data, n, int(r),
+                                               int(kind), ctypes.c_uint64(seed), en.ctypes.data,
+                                               None if r1 is None else r1.ctypes.data,
+                                               None if r2 is None else r2.ctypes.data))
+        return (en, r1, r2) if rows else en
 
     def shuffle_windows(self, transcript, W, step, win_begin, n_win, r, kind, seed):
         tr = np.frombuffer(transcript.encode("ascii") if isinstance(transcript, str) else bytes(transcript),

@@ -9,6 +9,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <map>
 #include <string>
 #include <vector>
@@ -24,6 +25,7 @@
 #include "sf_pf_lds.hip.h"
 #include "sf_shuffle.hip.h"
 #include "sf_tabulate.hip.h"
+#include "sf_duplex.hip.h"
 
 namespace {
 
@@ -481,6 +483,7 @@ const char *sf_strerror(int status) {
     case SF_ERR_INTERNAL: return "internal error: traceback found no decomposition";
     case SF_ERR_TABLE: return "scan table: unbalanced structure string, or window starts not ascending";
     case SF_ERR_CONSTRAINT: return "unbalanced brackets in a window's constraint string";
+    case SF_ERR_DUPLEX_HITS: return "LRI scan: more hits than max_hits (raise the capacity or lower the cutoff)";
     default: return "unknown status";
   }
 }
@@ -1194,6 +1197,284 @@ int sf_fold_long_times(double *fill_ms, double *f5_ms, double *trace_ms) {
   if (f5_ms) *f5_ms = g_long_ms[1];
   if (trace_ms) *trace_ms = g_long_ms[2];
   return SF_OK;
+}
+
+}  // extern "C"
+
+// ---------------- duplex folds and the LRI scan (include/scanfold_hip_duplex.h) ----------------
+namespace {
+double g_lri_ms = 0.0;
+int64_t g_lri_duplexes = 0;
+
+// device buffers of one duplex call; freed when it goes out of scope (after the stream has drained)
+struct DupBufs {
+  std::vector<void *> ptrs;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  ~DupBufs() {
+    hipStreamSynchronize(g.stream);
+    for (void *p : ptrs) hipFree(p);
+    for (hipEvent_t e : ev)
+      if (e) hipEventDestroy(e);
+  }
+  int alloc(void **p, size_t bytes) {
+    *p = nullptr;
+    const hipError_t e = hipMalloc(p, bytes ? bytes : 1);
+    if (e != hipSuccess) {
+      hipGetLastError();
+      char b[256];
+      snprintf(b, sizeof b, "duplex: hipMalloc of %zu bytes failed: %s", bytes, hipGetErrorString(e));
+      g.last_hip_error = b;
+      *p = nullptr;
+      return SF_ERR_HIP;
+    }
+    ptrs.push_back(*p);
+    return SF_OK;
+  }
+  template <class T>
+  int upload(T **d, const T *h, size_t count) {
+    void *p;
+    int rc = alloc(&p, count * sizeof(T));
+    if (rc) return rc;
+    *d = (T *)p;
+    if (count) HIPCHK(hipMemcpyAsync(p, h, count * sizeof(T), hipMemcpyHostToDevice, g.stream));
+    return SF_OK;
+  }
+};
+
+int dup_grid(long long tasks) {  // workgroups of a grid-stride launch: enough for every CU's LDS, bounded scratch
+  const long long cap = (long long)(g.n_cu > 0 ? g.n_cu : 1) * 8;
+  return (int)(tasks < cap ? (tasks < 1 ? 1 : tasks) : cap);
+}
+
+// n pairs that are already on the device as codes -> energies (and records) on the device
+int launch_duplex_batch(DupBufs &B, SfDupBatch A, int max1, int max2) {
+  if (A.n <= 0) return SF_OK;
+  const int grid = dup_grid(((long long)A.n + SF_DUP_BLOCK - 1) / SF_DUP_BLOCK);
+  void *scr;
+  int rc = B.alloc(&scr, (size_t)(max1 > 0 ? max1 : 1) * (max2 > 0 ? max2 : 1) * grid * SF_DUP_BLOCK * sizeof(int16_t));
+  if (rc) return rc;
+  A.scratch = (int16_t *)scr;
+  A.max2 = max2 > 0 ? max2 : 1;
+  A.status = (int *)g.status.p;
+  SF_LAUNCH(sf_duplex_batch_kernel, grid, SF_DUP_BLOCK, 0, g.stream, A, (const SfDevParams *)g.dP);
+  HIPCHK(hipGetLastError());
+  return SF_OK;
+}
+
+void lri_grid(int L, int kmer, int step, int *n_j, int *n_k) {
+  // j_win = 0, step, ... while j_win == 0 or j_win <= L - kmer + 1;  k_win likewise up to L - kmer (ScanFold.py:774,780).
+  // L < kmer: the single (0, 0) iteration never passes the distance test.
+  if (L < kmer) { *n_j = 0; *n_k = 0; return; }
+  *n_j = (L - kmer + 1) / step + 1;
+  *n_k = (L - kmer) / step + 1;
+}
+}  // namespace
+
+extern "C" {
+
+int sf_duplex_batch(const uint8_t *s1, const uint8_t *s2, int n, int ld, const int32_t *len1, const int32_t *len2,
+                    int32_t *energy_out, int32_t *i_out, int32_t *j_out, char *structure_out) {
+  int rc = check_ready();
+  if (rc) return rc;
+  if (n < 0 || ld < 1 || (n > 0 && (!s1 || !s2 || !len1 || !len2 || !energy_out))) return SF_ERR_BAD_ARG;
+  if (n == 0) return SF_OK;
+  int max1 = 0, max2 = 0;
+  for (int p = 0; p < n; p++) {
+    if (len1[p] < 0 || len2[p] < 0 || len1[p] > SF_DUPLEX_MAX_LEN || len2[p] > SF_DUPLEX_MAX_LEN || len1[p] > ld || len2[p] > ld)
+      return SF_ERR_BAD_ARG;
+    if (len1[p] > max1) max1 = len1[p];
+    if (len2[p] > max2) max2 = len2[p];
+  }
+  std::vector<uint8_t> c1((size_t)n * ld), c2((size_t)n * ld);
+  for (size_t x = 0; x < c1.size(); x++) { c1[x] = sf_encode_nt(s1[x]); c2[x] = sf_encode_nt(s2[x]); }
+  DupBufs B;
+  SfDupBatch A;
+  memset(&A, 0, sizeof A);
+  uint8_t *d1, *d2;
+  int32_t *dl1, *dl2;
+  if ((rc = B.upload(&d1, c1.data(), c1.size())) || (rc = B.upload(&d2, c2.data(), c2.size())) ||
+      (rc = B.upload(&dl1, len1, (size_t)n)) || (rc = B.upload(&dl2, len2, (size_t)n)))
+    return rc;
+  void *de, *di, *dj, *ds = nullptr;
+  if ((rc = B.alloc(&de, n * sizeof(int32_t))) || (rc = B.alloc(&di, n * sizeof(int32_t))) || (rc = B.alloc(&dj, n * sizeof(int32_t))))
+    return rc;
+  if (structure_out && (rc = B.alloc(&ds, (size_t)n * SF_DUPLEX_STRUCT_LEN))) return rc;
+  A.s1 = d1; A.s2 = d2; A.len1 = dl1; A.len2 = dl2; A.n = n; A.ld = ld;
+  A.e = (int32_t *)de; A.i = (int32_t *)di; A.j = (int32_t *)dj; A.structure = (char *)ds;
+  if ((rc = launch_duplex_batch(B, A, max1, max2))) return rc;
+  HIPCHK(hipMemcpyAsync(energy_out, de, n * sizeof(int32_t), hipMemcpyDeviceToHost, g.stream));
+  if (i_out) HIPCHK(hipMemcpyAsync(i_out, di, n * sizeof(int32_t), hipMemcpyDeviceToHost, g.stream));
+  if (j_out) HIPCHK(hipMemcpyAsync(j_out, dj, n * sizeof(int32_t), hipMemcpyDeviceToHost, g.stream));
+  if (structure_out) HIPCHK(hipMemcpyAsync(structure_out, ds, (size_t)n * SF_DUPLEX_STRUCT_LEN, hipMemcpyDeviceToHost, g.stream));
+  return read_status(g.stream, false);
+}
+
+int sf_lri_grid(int L, int kmer, int step, int32_t *n_j, int32_t *n_k) {
+  if (L < 0 || kmer < 2 || step < 1 || !n_j || !n_k) return SF_ERR_BAD_ARG;
+  int a, b;
+  lri_grid(L, kmer, step, &a, &b);
+  *n_j = a; *n_k = b;
+  return SF_OK;
+}
+
+int sf_lri_scan(const uint8_t *seq, int L, int kmer, int step, int32_t cutoff_dcal, int64_t max_hits, sf_lri_hit *hits_out,
+                int64_t *n_hits_out, int32_t *dense_e, int32_t *dense_i, int32_t *dense_j) {
+  int rc = check_ready();
+  if (rc) return rc;
+  const bool dense = dense_e != nullptr;
+  if (!seq || L < 1 || kmer < 2 || kmer > SF_DUPLEX_MAX_LEN || step < 1 || max_hits < 0 || max_hits > 0x7fffffffLL)
+    return SF_ERR_BAD_ARG;
+  if (dense ? (!dense_i || !dense_j) : (!n_hits_out || (max_hits > 0 && !hits_out))) return SF_ERR_BAD_ARG;
+  if (n_hits_out) *n_hits_out = 0;
+  int n_j, n_k;
+  lri_grid(L, kmer, step, &n_j, &n_k);
+  g_lri_ms = 0.0;
+  g_lri_duplexes = 0;
+  if (n_j == 0 || n_k == 0) return SF_OK;
+  if (dense && (long long)n_j * n_k > 0x7fffffffLL / 4) return SF_ERR_BAD_ARG;
+
+  std::vector<uint8_t> codes((size_t)L);
+  for (int x = 0; x < L; x++) codes[x] = sf_encode_nt(seq[x]);
+  DupBufs B;
+  SfLriScan A;
+  memset(&A, 0, sizeof A);
+  uint8_t *dcodes;
+  if ((rc = B.upload(&dcodes, codes.data(), codes.size()))) return rc;
+  A.codes = dcodes; A.L = L; A.kmer = kmer; A.step = step; A.n_j = n_j; A.n_k = n_k;
+  A.n_chunk = (n_k + SF_DUP_BLOCK - 1) / SF_DUP_BLOCK;
+  A.cutoff = cutoff_dcal;
+  A.max_hits = (unsigned)max_hits;
+  void *p;
+  const size_t nd = (size_t)n_j * n_k;
+  if (dense) {
+    if ((rc = B.alloc(&p, nd * sizeof(int32_t)))) return rc;
+    A.dense_e = (int32_t *)p;
+    if ((rc = B.alloc(&p, nd * sizeof(int32_t)))) return rc;
+    A.dense_i = (int32_t *)p;
+    if ((rc = B.alloc(&p, nd * sizeof(int32_t)))) return rc;
+    A.dense_j = (int32_t *)p;
+  } else {
+    if ((rc = B.alloc(&p, (size_t)max_hits * sizeof(sf_lri_hit)))) return rc;
+    A.hits = (sf_lri_hit *)p;
+  }
+  if ((rc = B.alloc(&p, sizeof(unsigned)))) return rc;
+  A.n_hits = (unsigned *)p;
+  HIPCHK(hipMemsetAsync(p, 0, sizeof(unsigned), g.stream));
+
+  const long long tasks = (long long)n_j * A.n_chunk;
+  const int grid = dup_grid(tasks);
+  const size_t strands = (size_t)kmer * SF_DUP_BLOCK + (size_t)kmer;
+  const size_t ctab = (size_t)kmer * kmer * SF_DUP_BLOCK * sizeof(int16_t);
+  const bool ldsc = ctab + strands <= SF_DUP_LDS_BUDGET;
+  const size_t lds = ldsc ? ctab + strands : strands;
+  if (strands > SF_DUP_LDS_BUDGET) return SF_ERR_BAD_ARG;
+  if (ldsc) {
+    HIPCHK(hipFuncSetAttribute((const void *)sf_lri_scan_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  } else {
+    if ((rc = B.alloc(&p, ctab * grid))) return rc;
+    A.scratch = (int16_t *)p;
+  }
+  // Bound the TIME of one launch, not its task count: the work of a duplex grows with kmer^4 (measured: 3.7e6 duplexes/s at
+  // k = 20, 4.6e5 at k = 40), so a launch takes 8e6 * (20 / kmer)^4 duplexes — one to two seconds — and never fewer tasks
+  // than the grid has workgroups.
+  long long per_launch = (long long)(8.0e6 * (20.0 / kmer) * (20.0 / kmer) * (20.0 / kmer) * (20.0 / kmer)) / SF_DUP_BLOCK;
+  if (per_launch < grid) per_launch = grid;
+  for (auto &e : B.ev) HIPCHK(hipEventCreate(&e));
+  HIPCHK(hipEventRecord(B.ev[0], g.stream));
+  for (long long t0 = 0; t0 < tasks; t0 += per_launch) {
+    const long long t1 = t0 + per_launch < tasks ? t0 + per_launch : tasks;
+    if (ldsc)
+      SF_LAUNCH(sf_lri_scan_kernel<true>, grid, SF_DUP_BLOCK, lds, g.stream, A, t0, t1, (const SfDevParams *)g.dP);
+    else
+      SF_LAUNCH(sf_lri_scan_kernel<false>, grid, SF_DUP_BLOCK, lds, g.stream, A, t0, t1, (const SfDevParams *)g.dP);
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipEventRecord(B.ev[1], g.stream));
+  unsigned count = 0;
+  HIPCHK(hipMemcpyAsync(&count, A.n_hits, sizeof count, hipMemcpyDeviceToHost, g.stream));
+  HIPCHK(hipStreamSynchronize(g.stream));
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, B.ev[0], B.ev[1]));
+  g_lri_ms = ms;
+  {  // the pairs the distance test lets through
+    long long nd2 = 0;
+    for (int jx = 0; jx < n_j; jx++) {
+      const long long jw = (long long)jx * step;
+      // k_win + 3 < j_win - kmer  <=>  k_win <= j_win - kmer - 4;   k_win > j_win + kmer + 3
+      const long long lo = jw - kmer - 4;
+      long long below = lo < 0 ? 0 : lo / step + 1;
+      if (below > n_k) below = n_k;
+      long long above = n_k - ((jw + kmer + 3) / step + 1);
+      if (above < 0) above = 0;
+      nd2 += below + above;
+    }
+    g_lri_duplexes = nd2;
+  }
+  if (dense) {
+    HIPCHK(hipMemcpy(dense_e, A.dense_e, nd * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(dense_i, A.dense_i, nd * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(dense_j, A.dense_j, nd * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return SF_OK;
+  }
+  *n_hits_out = (int64_t)count;
+  if ((int64_t)count > max_hits) return SF_ERR_DUPLEX_HITS;
+  if (count) {
+    std::vector<sf_lri_hit> h(count);
+    HIPCHK(hipMemcpy(h.data(), A.hits, (size_t)count * sizeof(sf_lri_hit), hipMemcpyDeviceToHost));
+    std::sort(h.begin(), h.end(), [](const sf_lri_hit &a, const sf_lri_hit &b) {
+      return a.j_win != b.j_win ? a.j_win < b.j_win : a.k_win < b.k_win;
+    });
+    memcpy(hits_out, h.data(), (size_t)count * sizeof(sf_lri_hit));
+  }
+  return SF_OK;
+}
+
+int sf_lri_scan_time(double *ms, int64_t *duplexes) {
+  SF_ENTER();
+  if (ms) *ms = g_lri_ms;
+  if (duplexes) *duplexes = g_lri_duplexes;
+  return SF_OK;
+}
+
+int sf_lri_background(const uint8_t *seq, int L, int kmer, const int32_t *j_win, const int32_t *k_win, int n_hits, int r,
+                      int kind, uint64_t seed, int32_t *energies_out, uint8_t *rows1_out, uint8_t *rows2_out) {
+  int rc = check_ready();
+  if (rc) return rc;
+  if (!seq || L < 1 || kmer < 2 || kmer > SF_DUPLEX_MAX_LEN || n_hits < 0 || r < 0 || r > 0x3fffffff) return SF_ERR_BAD_ARG;
+  if (kind != SF_SHUFFLE_MONO && kind != SF_SHUFFLE_DI) return SF_ERR_BAD_ARG;
+  if (n_hits == 0) return SF_OK;
+  if (!j_win || !k_win || !energies_out) return SF_ERR_BAD_ARG;
+  const long long rows = (long long)n_hits * (r + 1);
+  if (rows > 0x7fffffffLL / SF_DUPLEX_MAX_LEN) return SF_ERR_BAD_ARG;
+  for (int h = 0; h < n_hits; h++)
+    if (j_win[h] < 0 || j_win[h] > L - kmer + 1 || k_win[h] < 0 || k_win[h] > L - kmer) return SF_ERR_BAD_ARG;
+  std::vector<uint8_t> codes((size_t)L);
+  for (int x = 0; x < L; x++) codes[x] = sf_encode_nt(seq[x]);
+  DupBufs B;
+  uint8_t *dcodes;
+  int32_t *djw, *dkw;
+  if ((rc = B.upload(&dcodes, codes.data(), codes.size())) || (rc = B.upload(&djw, j_win, (size_t)n_hits)) ||
+      (rc = B.upload(&dkw, k_win, (size_t)n_hits)))
+    return rc;
+  void *r1, *r2, *l1, *de;
+  const size_t nb = (size_t)rows * kmer;
+  if ((rc = B.alloc(&r1, nb)) || (rc = B.alloc(&r2, nb)) || (rc = B.alloc(&l1, rows * sizeof(int32_t))) ||
+      (rc = B.alloc(&de, rows * sizeof(int32_t))))
+    return rc;
+  const int sgrid = (int)((rows + SF_SHUF_BLOCK - 1) / SF_SHUF_BLOCK);
+  const size_t lds = (((size_t)SF_SHUF_BLOCK * kmer + 3) & ~(size_t)3) * 2 + SF_SHUF_BLOCK * 25 * sizeof(uint16_t);
+  SF_LAUNCH(sf_lri_shuffle_kernel, sgrid, SF_SHUF_BLOCK, lds, g.stream, (const uint8_t *)dcodes, L, kmer, (const int32_t *)djw,
+            (const int32_t *)dkw, n_hits, r, kind, seed, (uint8_t *)r1, (uint8_t *)r2, (int32_t *)l1);
+  HIPCHK(hipGetLastError());
+  SfDupBatch A;
+  memset(&A, 0, sizeof A);
+  A.s1 = (const uint8_t *)r1; A.s2 = (const uint8_t *)r2; A.len1 = (const int32_t *)l1; A.len2 = nullptr;
+  A.n = (int)rows; A.ld = kmer; A.n2 = kmer; A.e = (int32_t *)de;
+  if ((rc = launch_duplex_batch(B, A, kmer, kmer))) return rc;
+  HIPCHK(hipMemcpyAsync(energies_out, de, rows * sizeof(int32_t), hipMemcpyDeviceToHost, g.stream));
+  if (rows1_out) HIPCHK(hipMemcpyAsync(rows1_out, r1, nb, hipMemcpyDeviceToHost, g.stream));
+  if (rows2_out) HIPCHK(hipMemcpyAsync(rows2_out, r2, nb, hipMemcpyDeviceToHost, g.stream));
+  return read_status(g.stream, false);
 }
 
 }  // extern "C"

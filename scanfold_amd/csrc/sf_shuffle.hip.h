@@ -43,6 +43,108 @@ __device__ inline double sf_rand_double(SfPhilox *g) {
   return ((double)a * 67108864.0 + (double)b) * (1.0 / 9007199254740992.0);
 }
 
+// One shuffled row: `src` is W nucleotides (ASCII or codes), `out` / `lst` W bytes and `cnt` 25 counters of the calling thread.
+__device__ __forceinline__ void sf_shuffle_row(const uint8_t *src, int W, int kind, SfPhilox &g, uint8_t *out, uint8_t *lst,
+                                               uint16_t *cnt) {
+  if (kind == SF_SHUFFLE_MONO) {
+    for (int x = 0; x < W; x++) out[x] = sf_encode_nt(src[x]);
+    for (int i = W - 1; i >= 1; i--) {
+      const int jj = (int)(((uint64_t)sf_rand_u32(&g) * (uint32_t)(i + 1)) >> 32);
+      const uint8_t t = out[i]; out[i] = out[jj]; out[jj] = t;
+    }
+  } else {
+    // vertex order of the reference's lists: A, C, G, U (codes 1..4), then N (0)
+    const int order[5] = {1, 2, 3, 4, 0};
+    for (int x = 0; x < 25; x++) cnt[x] = 0;
+    uint8_t prev = sf_encode_nt(src[0]);
+    const uint8_t first = prev;
+    for (int x = 1; x < W; x++) {
+      const uint8_t y = sf_encode_nt(src[x]);
+      cnt[prev * 5 + y]++;
+      prev = y;
+    }
+    const int lastCh = prev;
+    int outdeg[5], present[5], lastedge[5];
+    for (int a = 0; a < 5; a++) {
+      int s = 0;
+      for (int b = 0; b < 5; b++) s += cnt[a * 5 + b];
+      outdeg[a] = s;
+      present[a] = (s > 0) || (a == lastCh);
+    }
+    // draw last edges until every present vertex is connected to lastCh
+    for (;;) {
+      for (int oa = 0; oa < 5; oa++) {
+        const int a = order[oa];
+        lastedge[a] = -1;
+        if (!present[a] || a == lastCh) continue;
+        const double z = sf_rand_double(&g);
+        const double denom = (double)outdeg[a];
+        int num = 0, pick = order[4];
+        for (int ob = 0; ob < 4; ob++) {
+          num += cnt[a * 5 + order[ob]];
+          if (z < (double)num / denom) { pick = order[ob]; break; }
+        }
+        lastedge[a] = pick;
+      }
+      int Dm[5];
+      for (int a = 0; a < 5; a++) Dm[a] = (lastedge[a] == lastCh);
+      for (int rnd = 0; rnd < 4; rnd++)
+        for (int oa = 0; oa < 5; oa++) {
+          const int a = order[oa];
+          if (lastedge[a] >= 0 && Dm[lastedge[a]]) Dm[a] = 1;
+        }
+      int ok = 1;
+      for (int a = 0; a < 5; a++)
+        if (present[a] && a != lastCh && !Dm[a]) ok = 0;
+      if (ok) break;
+    }
+    // successor lists in order of occurrence
+    int start[5], fill[5];
+    {
+      int acc = 0;
+      for (int oa = 0; oa < 5; oa++) { const int a = order[oa]; start[a] = acc; acc += outdeg[a]; fill[a] = 0; }
+    }
+    prev = first;
+    for (int x = 1; x < W; x++) {
+      const uint8_t y = sf_encode_nt(src[x]);
+      lst[start[prev] + fill[prev]++] = y;
+      prev = y;
+    }
+    // remove the first occurrence of the chosen last edge, shuffle the rest, put the edge back at the end
+    for (int oa = 0; oa < 5; oa++) {
+      const int a = order[oa];
+      if (lastedge[a] < 0) continue;
+      uint8_t *Lx = lst + start[a];
+      int pos = 0;
+      while (Lx[pos] != (uint8_t)lastedge[a]) pos++;
+      for (int x = pos; x + 1 < outdeg[a]; x++) Lx[x] = Lx[x + 1];
+    }
+    for (int oa = 0; oa < 5; oa++) {
+      const int a = order[oa];
+      if (!present[a]) continue;
+      uint8_t *Lx = lst + start[a];
+      const int nlist = outdeg[a] - (lastedge[a] >= 0 ? 1 : 0);
+      int barrier = nlist;
+      for (int x = 0; x < nlist - 1; x++) {
+        const int z = (int)(sf_rand_double(&g) * (double)barrier);
+        const uint8_t t = Lx[z]; Lx[z] = Lx[barrier - 1]; Lx[barrier - 1] = t;
+        barrier--;
+      }
+      if (lastedge[a] >= 0) Lx[nlist] = (uint8_t)lastedge[a];
+    }
+    // Euler walk
+    int ptr[5] = {0, 0, 0, 0, 0};
+    out[0] = first;
+    int pc = first;
+    for (int x = 1; x < W - 1; x++) {
+      const uint8_t ch = lst[start[pc] + ptr[pc]++];
+      out[x] = ch;
+      pc = ch;
+    }
+    if (W > 1) out[W - 1] = (uint8_t)lastCh;
+  }
+}
+
 #define SF_SHUF_BLOCK 64
 
 // LDS per block: rows[64][W] output rows + lst[64][W] successor lists + cnt[64][25] uint16
@@ -71,103 +173,7 @@ __global__ void sf_shuffle_kernel(const uint8_t *__restrict__ transcript, int L,
       g.k0 = (uint32_t)seed; g.k1 = (uint32_t)(seed >> 32);
       g.c0 = 0; g.c1 = (uint32_t)k; g.c2 = (uint32_t)(win_begin + w); g.c3 = (uint32_t)kind;
       g.have = 0;
-      if (kind == SF_SHUFFLE_MONO) {
-        for (int x = 0; x < W; x++) out[x] = sf_encode_nt(src[x]);
-        for (int i = W - 1; i >= 1; i--) {
-          const int jj = (int)(((uint64_t)sf_rand_u32(&g) * (uint32_t)(i + 1)) >> 32);
-          const uint8_t t = out[i]; out[i] = out[jj]; out[jj] = t;
-        }
-      } else {
-        // vertex order of the reference's lists: A, C, G, U (codes 1..4), then N (0)
-        const int order[5] = {1, 2, 3, 4, 0};
-        for (int x = 0; x < 25; x++) cnt[x] = 0;
-        uint8_t prev = sf_encode_nt(src[0]);
-        const uint8_t first = prev;
-        for (int x = 1; x < W; x++) {
-          const uint8_t y = sf_encode_nt(src[x]);
-          cnt[prev * 5 + y]++;
-          prev = y;
-        }
-        const int lastCh = prev;
-        int outdeg[5], present[5], lastedge[5];
-        for (int a = 0; a < 5; a++) {
-          int s = 0;
-          for (int b = 0; b < 5; b++) s += cnt[a * 5 + b];
-          outdeg[a] = s;
-          present[a] = (s > 0) || (a == lastCh);
-        }
-        // draw last edges until every present vertex is connected to lastCh
-        for (;;) {
-          for (int oa = 0; oa < 5; oa++) {
-            const int a = order[oa];
-            lastedge[a] = -1;
-            if (!present[a] || a == lastCh) continue;
-            const double z = sf_rand_double(&g);
-            const double denom = (double)outdeg[a];
-            int num = 0, pick = order[4];
-            for (int ob = 0; ob < 4; ob++) {
-              num += cnt[a * 5 + order[ob]];
-              if (z < (double)num / denom) { pick = order[ob]; break; }
-            }
-            lastedge[a] = pick;
-          }
-          int Dm[5];
-          for (int a = 0; a < 5; a++) Dm[a] = (lastedge[a] == lastCh);
-          for (int rnd = 0; rnd < 4; rnd++)
-            for (int oa = 0; oa < 5; oa++) {
-              const int a = order[oa];
-              if (lastedge[a] >= 0 && Dm[lastedge[a]]) Dm[a] = 1;
-            }
-          int ok = 1;
-          for (int a = 0; a < 5; a++)
-            if (present[a] && a != lastCh && !Dm[a]) ok = 0;
-          if (ok) break;
-        }
-        // successor lists in order of occurrence
-        int start[5], fill[5];
-        {
-          int acc = 0;
-          for (int oa = 0; oa < 5; oa++) { const int a = order[oa]; start[a] = acc; acc += outdeg[a]; fill[a] = 0; }
-        }
-        prev = first;
-        for (int x = 1; x < W; x++) {
-          const uint8_t y = sf_encode_nt(src[x]);
-          lst[start[prev] + fill[prev]++] = y;
-          prev = y;
-        }
-        // remove the first occurrence of the chosen last edge, shuffle the rest, put the edge back at the end
-        for (int oa = 0; oa < 5; oa++) {
-          const int a = order[oa];
-          if (lastedge[a] < 0) continue;
-          uint8_t *Lx = lst + start[a];
-          int pos = 0;
-          while (Lx[pos] != (uint8_t)lastedge[a]) pos++;
-          for (int x = pos; x + 1 < outdeg[a]; x++) Lx[x] = Lx[x + 1];
-        }
-        for (int oa = 0; oa < 5; oa++) {
-          const int a = order[oa];
-          if (!present[a]) continue;
-          uint8_t *Lx = lst + start[a];
-          const int nlist = outdeg[a] - (lastedge[a] >= 0 ? 1 : 0);
-          int barrier = nlist;
-          for (int x = 0; x < nlist - 1; x++) {
-            const int z = (int)(sf_rand_double(&g) * (double)barrier);
-            const uint8_t t = Lx[z]; Lx[z] = Lx[barrier - 1]; Lx[barrier - 1] = t;
-            barrier--;
-          }
-          if (lastedge[a] >= 0) Lx[nlist] = (uint8_t)lastedge[a];
-        }
-        // Euler walk
-        int ptr[5] = {0, 0, 0, 0, 0};
-        out[0] = first;
-        int pc = first;
-        for (int x = 1; x < W - 1; x++) {
-          const uint8_t ch = lst[start[pc] + ptr[pc]++];
-          out[x] = ch;
-          pc = ch;
-        }
-        if (W > 1) out[W - 1] = (uint8_t)lastCh;
-      }
+      sf_shuffle_row(src, W, kind, g, out, lst, cnt);
     }
   }
   __syncthreads();

@@ -14,6 +14,9 @@ refolds of ScanFold.py:1582-1776 (scanfold_amd.motifs: `<that>.ExtractedStructur
 then with the -1 and the -2 filter's dot-bracket lines as hard constraints, through the RNA facade (whole-record folds,
 sf_fold_long), into `<that>.<--dbn_file_path>` and `<that>.AllDBN.txt`.  ScanFold.py's per-record directories and IGV
 wig exports are not reproduced.
+--lri replaces the window scan by the k-mer duplex scan (ScanFold.py:391-393,421,769-1034; scanfold_amd.lri): it writes
+`<that>.LRI.out`, reports the number of hits and stops — upstream's continuation into the Fold stage is not runnable in
+general (README.md) and is not reproduced.
 """
 import argparse
 import os
@@ -223,6 +226,10 @@ def build_parser():
                    help='Global refold option. Refold full sequence using Zavg <-1 and <-2 base pairs')
     p.add_argument('--dbn_file_path', type=str, default="AllDBN-global_refold.txt",
                    help='file name (after the output prefix) of the global refold records')
+    p.add_argument('--lri', action='store_true', help='scan for long range interactions (k-mer duplexes) instead of windows')
+    p.add_argument('--kmer', type=int, default=20, help='size of k-mer for lri scan')
+    p.add_argument('--kmer_step_size', type=int, default=1, help='step size of k-mer scan for lri')
+    p.add_argument('--lri_cutoff', type=int, default=-25, help='duplex energy (kcal/mol) a k-mer pair must stay below')
     p.add_argument('--dont_fold', action='store_true', help='scan only')
     p.add_argument('--dont_extract', action='store_true', help='no motif extraction / refolds after the Fold stage')
     p.add_argument('--seed', type=int, default=0)
@@ -240,6 +247,11 @@ def main(argv=None):
     if args.global_refold and (args.c == 0 or args.dont_fold):
         # upstream scans first and then fails on the dbn files those modes never write
         raise ValueError("--global_refold refolds with the -1 / -2 dbn files of the Fold stage: not with -c 0 or --dont_fold")
+    if args.lri:
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise ValueError("--lri runs on one GPU: start it without a multi-process launcher")
+        from . import lri as lrimod
+        lrimod.check_lri_args(args.kmer, args.kmer_step_size)
     from . import params as _params
     eng = _lib.get_engine()
     eng.set_max_bp_span(args.span or 0)
@@ -252,6 +264,13 @@ def main(argv=None):
             raise TypeError("exceptions must derive from BaseException")  # upstream: raise("Gaps found in sequence...")
         outname = read_name + ".win_" + str(W) + ".stp_" + str(step) + ".rnd_" + str(r) + ".shfl_" + str(args.type)
         print("Output name=" + str(outname))
+        if args.lri:  # replaces the window scan and everything after it (ScanFold.py:391-393,421,769-1034)
+            print(lrimod.WARNING)
+            print("Scanning for long range interactions...")
+            hits = lrimod.lri_scan(seq, args.kmer, args.kmer_step_size, args.lri_cutoff, r, args.type, eng, args.seed)
+            lrimod.write_lri(outname + ".LRI.out", hits)
+            print("LRI Scan Complete: %d hits in %s.LRI.out" % (len(hits), outname))
+            continue
         if len(seq) < W:
             print(read_name + " sequence is less than window size. Moving on to next entry.")
             continue
