@@ -433,14 +433,13 @@ int launch_mfe(const uint8_t *d_seqs, int n, int W, int32_t *d_out, hipStream_t 
       d_rows = it->second;
     }
     if ((rc = prof.begin(st))) return rc;
-    if (hc)
-      sf_fast_launch_hc(grid, threads, lds, st, d_seqs, n, W, (const SfDevParams *)g.dP, (const SfFastParams *)g.dF,
-                        d_rows, (int16_t *)g.fast_scratch.p, d_out, d_cnt, d_list, trace_stride, d_db, (int *)g.status.p, d_work,
-                        d_cons, d_sc);
-    else
-      sf_fast_launch(mfe_poison(), grid, threads, lds, st, d_seqs, n, W, (const SfDevParams *)g.dP, (const SfFastParams *)g.dF,
-                     d_rows, (int16_t *)g.fast_scratch.p, d_out, d_cnt, d_list, trace_stride, d_db, (int *)g.status.p,
-                     d_work, (const char *)nullptr, (const int32_t *)nullptr);
+    // (constrained folds have no poison build; without a constraint d_cons and d_sc are null)
+    if (!sf_fast_launch(hc, hc ? 0 : mfe_poison(), grid, threads, lds, st, d_seqs, n, W, (const SfDevParams *)g.dP,
+                        (const SfFastParams *)g.dF, d_rows, (int16_t *)g.fast_scratch.p, d_out, d_cnt, d_list, trace_stride, d_db,
+                        (int *)g.status.p, d_work, d_cons, d_sc)) {
+      g.last_hip_error = "launch_mfe: no instantiation of sf_mfe_fast_kernel for this width";
+      return SF_ERR_HIP;
+    }
     HIPCHK(hipGetLastError());
     if ((rc = prof.end(st))) return rc;
     // folds that left the int16 range (or hold a forced pair of non-complementary bases) are redone exactly

@@ -5,7 +5,7 @@
 //
 // One workgroup folds one sequence at a time (persistent grid; a workgroup's first fold is its block index, every further one comes
 // from a device-wide counter); two anti-diagonals per step (two thread groups), one barrier per step (two on the long diagonals).
-// The steps of a fold run as one loop PER KIND of step — size-tested / guarded / unsplit / split (and finer: SF_LOOPS_BY_KIND, the
+// The steps of a fold run as one loop PER KIND of step — size-tested / guarded / unsplit / split (and finer: SfStep, the
 // loops at the end of the kernel) — because each loop then gets its own register allocation and schedule: +5-8 % at every width.
 // Thread mapping: a thread owns a CENTRE s = i+j (two centres, one per parity of d):
 // on diagonal d it handles the cell i = v - d/2, j = i+d with v = (tid+OFF) mod NT.  The cell of the same
@@ -62,37 +62,19 @@
 // even diagonals below this one skip whole batches of loop sizes above the limit (CH); from here to 36 the skipped
 // work is small and the unbroken straight-line code is faster (measured: 20 / 24 / 28 / 36 -> 87.5 / 87.1 / 87.0 / 87.9 ms)
 #define SF_FAST_CHUNK_D0 36
-#ifndef SF_FAST_ROWTAB
-#define SF_FAST_ROWTAB 1  // rolling-row offsets from a table (scalar loads, SfFastRows) instead of per-row ring arithmetic
-#endif
 #ifndef SF_FAST_UNPACK
 #define SF_FAST_UNPACK 1  // narrow kernels, from d0 = 36 on: the generic-loop recurrence on full-rate 16-bit instructions (SfHU)
-#endif
-#ifndef SF_LOOPS_BY_KIND
-#define SF_LOOPS_BY_KIND 1  // one loop per kind of step instead of one loop with the kinds as branches (0: the round-4 structure)
 #endif
 #ifndef SF_UNP_PB
 #define SF_UNP_PB 4  // size pairs per batch of reads in the unpacked recurrence (3 / 4 / 6 / 12: 58.0 / 57.5 / 58.6 / 58.3 ms per 262 144 folds)
 #endif
-#define SF_FAST_SPLIT 1  // long diagonals: the idle second wave of a group takes part of the cell's work
-#define SF_FAST_DML2 1   // ... and the first runs the multiloop split two cells per lane, the lanes in chunks over the terms
-// split steps at W <= 128: 1 = ONE helper wave serves both diagonals of a step, on a compacted list of the cells that
-// can pair (3 of 8): the special / bulge / 1xn block runs once per step instead of twice
-// (W < SF_HELP_MERGE_MAXW, and the W = 120 instantiation: SF_MG120.  With folds handed out dynamically the merge measures +3.6 % at W=80, +2.3 % at W=100,
-// +1.1 % at W=110, +1.5 % at W=116 and -2.9 % at W=120, -1.4 % at W=128: the compacted lanes read scattered words, three or four deep
-// in the LDS banks, and at the widths where LDS cycles are tightest that costs more than the saved pass.)
+// Split steps (long diagonals: the idle waves of a group take part of the cell's work) at W <= 128: below this width ONE helper wave
+// serves both diagonals of a step, on a compacted list of the cells that can pair (3 of 8) — the special / bulge / 1xn block runs
+// once per step instead of twice (the merged helper, MG in the kernel).  The compacted lanes read scattered words, three or four
+// deep in the LDS banks, and at the widths where LDS cycles are tightest that costs more than the saved pass: the generic
+// instantiation stops here; the W = 120 instantiation runs the merged helper all the same, its cell lists in the place of the LDS
+// copy of the size tables (see cell_list in the kernel).  (The figures per width: profiles/HISTORY.md, "Switches settled".)
 #define SF_HELP_MERGE_MAXW 118
-#define SF_HELP_MERGE 1
-// the W = 120 instantiation runs the merged helper too (round 4: +1.1 %, 59.5 -> 58.8 ms per 262 144 folds) — its cell lists take the
-// place of the LDS copy of the size tables (see cell_list in the kernel); the generic instantiation keeps the W < 118 rule
-#ifndef SF_MG120
-#define SF_MG120 1
-#endif
-// split steps at W > 128 (four waves per diagonal): 1 = the group's outer waves help the two middle ones
-#define SF_FAST_SPLIT_256 1
-#ifndef SF_FAST_NARROW_256
-#define SF_FAST_NARROW_256 1  // ... and from the diagonal where a diagonal's cells fit one wave on, one main + one helper wave (NARROW in the kernel)
-#endif
 // split steps of the wide kernel (NG = 256, where the split is most of a cell): the helper waves take (terms / 2 - bias)
 // terms of the multiloop split, the ones with the largest m.  The narrow kernel's helpers take none: their special-loop
 // work already balances the main wave (any share measured the same or worse in rounds 2 and 3).
@@ -250,7 +232,7 @@ static inline void sf_fast_build_rows(int W, SfFastRows &R) {
 // LDS carve (bytes); every piece a multiple of 4
 struct SfFastLayout {
   int tri;  // int16 entries of the fML triangle (diagonals >= 4)
-  int off_ci, off_c1n, off_cb, off_dml, off_list, off_next, off_tab, off_red, off_flag, off_S;
+  int off_ci, off_c1n, off_cb, off_dml, off_list, off_next, off_tab, off_flag, off_S;
   int off_hc;     // (hc layouts) constraint characters | partners | enclosing pairs | int16 pseudo-energies
   int total;
 };
@@ -287,14 +269,13 @@ static inline __host__ __device__ SfFastLayout sf_fast_layout(int W, bool hc = f
   // from one base as well)
   o += mirror * 4;
   L.off_list = o;
-  if (W < SF_HELP_MERGE_MAXW && SF_HELP_MERGE) o += 2 * 128;
+  if (W < SF_HELP_MERGE_MAXW) o += 2 * 128;
   // (What follows the rolling tables matters: on the short diagonals the straight-line cell code reads candidates of
   // loop sizes that do not exist yet — up to 23 words past the end of a row, past the end of the last row into
   // whatever comes next — and relies on finding energy-sized values there (they get a weight of 32767 and saturate).
   // The mirror row and the parameter tables are that; the cell list is never in reach where it is written (W >= 64),
   // and is filled with "no structure" where it is not; the two control words below sit behind the tables.)
   L.off_tab = o; o += SF_FAST_TAB_BYTES;
-  L.off_red = o;  // (unused)
   L.off_flag = o; o += 4;
   L.off_next = o; o += 4;  // index of the workgroup's next fold (dynamic distribution)
   L.off_S = o; o += (W + 2 + 3) & ~3;
@@ -411,15 +392,10 @@ __device__ __forceinline__ void sf_fast_split_stretch(const int16_t *pa, const i
 }
 
 // (CB, C1N) of the cell at column i0 of a row into the interleaved bulge / 1xn table; w points at the cell's own word.
-// SHIFT: the C1N half belongs in the previous word (column 0's is never read: 1xn candidates start at column 2).
-template <bool SHIFT>
+// The C1N half belongs in the previous word (column 0's is never read: 1xn candidates start at column 2).
 __device__ __forceinline__ void sf_fast_publish_bn(int16_t *w, const int i0, const uint32_t bn) {
-  if (SHIFT) {
-    w[0] = (int16_t)sf_lo(bn);
-    if (i0 > 0) w[-1] = (int16_t)sf_hi(bn);
-  } else {
-    sf_stw(w, bn);
-  }
+  w[0] = (int16_t)sf_lo(bn);
+  if (i0 > 0) w[-1] = (int16_t)sf_hi(bn);
 }
 
 // Entry idx of an int16 table inside the parameter block (wave-uniform base F): the byte offset — the table's place in the block
@@ -529,10 +505,9 @@ __device__ __forceinline__ void sf_fast_cell(const SfFastCtx &X, const int d, co
   const int16_t *const ubase = G ? X.uNIN : (CH ? Fc->uniG[sfd_max(sfd_min(d - 2 - (SFD_TURN + 1), 30), 0)] : Fc->uni);
   const int16_t *const uNIN = ubase, *const uIL = ubase + 32, *const uBN = ubase + 64;
 // Word x of a row holds (CB[x], C1N[x+1]) — the two left-edge candidates of a size, CB at column 1 and C1N at column
-// 2, are then ONE word.  (SHIFT = false: (CB[x], C1N[x]), the layout until late in round 2.)
-  constexpr bool SHIFT = true;
+// 2, are then ONE word.
 #define CBAT(x) X.BN[2 * (x)]
-#define C1NAT(x) X.BN[2 * ((x) - (SHIFT ? 1 : 0)) + 1]
+#define C1NAT(x) X.BN[2 * ((x) - 1) + 1]
 // H[x] (x = size - 4) lives in the int16 halves of HP[x/2]: 14 registers instead of 27 under the 128-VGPR cap
 #define HGET(x) (((x)&1) ? ((int)HP[(x) >> 1] >> 16) : (int)(int16_t)(HP[(x) >> 1] & 0xffffu))
 #define HSET(x, v)                                                                                       \
@@ -584,7 +559,7 @@ __device__ __forceinline__ void sf_fast_cell(const SfFastCtx &X, const int d, co
 // build spills registers — see SF_UNI — so the scalar unit keeps computing them)
 #define ROW(u) ((slot2 - (u) < 0 ? slot2 - (u) + SF_FAST_NR : slot2 - (u)) * RW)
   // TBL (the all-sizes code): the rows' byte offsets come from SfFastRows — scalar loads of consecutive entries
-  constexpr bool TBL = !G && (TBLK != 0) && SF_FAST_ROWTAB;
+  constexpr bool TBL = !G && TBLK != 0;
   const SfFastRows *const Rc = TBL ? sf_const_base(X.R) : X.R;  // (the base is pinned by a volatile asm: only where it is used)
   const int32_t *const rci_o = Rc->ci_odd[slot2], *const rci_e = Rc->ci_even[slot2];
   const int32_t *const rbn_o = Rc->bn_odd[slot2], *const rbn_e = Rc->bn_even[slot2];
@@ -792,7 +767,7 @@ __device__ __forceinline__ void sf_fast_cell(const SfFastCtx &X, const int d, co
 #pragma unroll
         for (int ub = 2; ub <= 30; ub += SF_HELP_NB) {
           if (CH && ub > um) continue;
-          uint32_t w0[SF_HELP_NB], w1[SF_HELP_NB], w2[SF_HELP_NB], w3[SF_HELP_NB], wt[SF_HELP_NB], t[SF_HELP_NB];
+          uint32_t w0[SF_HELP_NB], w2[SF_HELP_NB], w3[SF_HELP_NB], wt[SF_HELP_NB], t[SF_HELP_NB];
 #pragma unroll
           for (int k = 0; k < SF_HELP_NB; k++) {
             const int u = ub + k;
@@ -803,8 +778,7 @@ __device__ __forceinline__ void sf_fast_cell(const SfFastCtx &X, const int d, co
               sf_emul_check_bn_row((const char *)tp, 4 * i0, 4 * RW, FOLD);
 #endif
               w0[k] = sf_ldw(tp + 2 * 1);
-              if (!SHIFT) w1[k] = sf_ldw(tp + 2 * 2);
-              w2[k] = sf_ldw(tp + 2 * (SHIFT ? u - 1 : u)); w3[k] = sf_ldw(tp + 2 * (u + 1));
+              w2[k] = sf_ldw(tp + 2 * (u - 1)); w3[k] = sf_ldw(tp + 2 * (u + 1));
               wt[k] = sf_ldw(uBN + 2 * u);
             }
           }
@@ -813,7 +787,7 @@ __device__ __forceinline__ void sf_fast_cell(const SfFastCtx &X, const int d, co
             for (int k = 0; k < SF_HELP_NB; k++) {
               const int u = ub + k;
               if (u <= 30) {
-                const uint32_t x = SHIFT ? w0[k] : ((w0[k] & 0xffffu) | (w1[k] & 0xffff0000u));  // (CB[1], C1N[2])
+                const uint32_t x = w0[k];  // (CB[1], C1N[2])
                 const uint32_t y = (w3[k] & 0xffffu) | (w2[k] & 0xffff0000u);  // (CB[1+u], C1N[u])
                 t[k] = sf_pkmin(x, y);
               }
@@ -835,7 +809,7 @@ __device__ __forceinline__ void sf_fast_cell(const SfFastCtx &X, const int d, co
             for (int k = 0; k < SF_HELP_NB; k++) {
               const int u = ub + k;
               if (u <= 30) {
-                const uint32_t x = SHIFT ? w0[k] : ((w0[k] & 0xffffu) | (w1[k] & 0xffff0000u));  // (CB[1], C1N[2])
+                const uint32_t x = w0[k];  // (CB[1], C1N[2])
                 const uint32_t y = (w3[k] & 0xffffu) | (w2[k] & 0xffff0000u);  // (CB[1+u], C1N[u])
                 acc = sf_pkmin(acc, sf_pkadd(sf_pkmin(x, y), wt[k]));
               }
@@ -1012,8 +986,8 @@ __device__ __forceinline__ void sf_fast_cell(const SfFastCtx &X, const int d, co
     X.CI[rbd] = (int16_t)(c + sf_lo(pub.a));
     if (!FOLD && slotd == 0) X.CI[SF_FAST_NR * RW + i0] = (int16_t)(c + sf_lo(pub.a));
     const uint32_t bn = sf_pk(c + pub.tau, c + sf_hi(pub.a));  // (CB, C1N)
-    sf_fast_publish_bn<SHIFT>(X.BN + 2 * rbd, i0, bn);
-    if (X.bn_dup && slotd == 0) sf_fast_publish_bn<SHIFT>(X.BN + 2 * (SF_FAST_NR * RW + i0), i0, bn);
+    sf_fast_publish_bn(X.BN + 2 * rbd, i0, bn);
+    if (X.bn_dup && slotd == 0) sf_fast_publish_bn(X.BN + 2 * (SF_FAST_NR * RW + i0), i0, bn);
     f = c + sf_lo(pub.b);
     cx = sfd_min(c + sf_hi(pub.b), SF_INF16);
   } else if (type) {
@@ -1023,8 +997,8 @@ __device__ __forceinline__ void sf_fast_cell(const SfFastCtx &X, const int d, co
     X.CI[rbd] = (int16_t)(c + X.tI[SF_TIDX(tr, sq1, sp1)]);
     if (!FOLD && slotd == 0) X.CI[SF_FAST_NR * RW + i0] = X.CI[rbd];
     const uint32_t bn = sf_pk(c + tau_in, c + X.t1n[SF_TIDX(tr, sq1, sp1)]);  // (CB, C1N)
-    sf_fast_publish_bn<SHIFT>(X.BN + 2 * rbd, i0, bn);
-    if (X.bn_dup && slotd == 0) sf_fast_publish_bn<SHIFT>(X.BN + 2 * (SF_FAST_NR * RW + i0), i0, bn);
+    sf_fast_publish_bn(X.BN + 2 * rbd, i0, bn);
+    if (X.bn_dup && slotd == 0) sf_fast_publish_bn(X.BN + 2 * (SF_FAST_NR * RW + i0), i0, bn);
     // E_MLstem and ExtLoop of (type, S[i-1], S[j+1]) differ in the mismatch table only; at the sequence ends both
     // are a dangle
     int stem, ext;
@@ -1035,9 +1009,9 @@ __device__ __forceinline__ void sf_fast_cell(const SfFastCtx &X, const int d, co
     f = c + stem + tau_in + X.MLintern;
     cx = sfd_min(c + ext + tau_in, SF_INF16);
   } else {
-    X.CI[rbd] = SF_INF16; sf_fast_publish_bn<SHIFT>(X.BN + 2 * rbd, i0, sf_pk(SF_INF16, SF_INF16));
+    X.CI[rbd] = SF_INF16; sf_fast_publish_bn(X.BN + 2 * rbd, i0, sf_pk(SF_INF16, SF_INF16));
     if (!FOLD && slotd == 0) X.CI[SF_FAST_NR * RW + i0] = SF_INF16;
-    if (X.bn_dup && slotd == 0) sf_fast_publish_bn<SHIFT>(X.BN + 2 * (SF_FAST_NR * RW + i0), i0, sf_pk(SF_INF16, SF_INF16));
+    if (X.bn_dup && slotd == 0) sf_fast_publish_bn(X.BN + 2 * (SF_FAST_NR * RW + i0), i0, sf_pk(SF_INF16, SF_INF16));
   }
   // the scratch (row i, column j: the exterior sweep reads rows coalesced) takes c + ExtLoop, the only form the
   // sweep needs; the traceback (native windows only) subtracts the term again (sf_fast_c).  (Storing only the cells
@@ -1440,14 +1414,11 @@ __device__ __forceinline__ void sf_fast_exterior(const SfFastCtx &X, const int W
 // L2 <-> fabric traffic per cfg3 launch).  It runs the SAME recurrence from the other end,
 //   f3[i] = min(f3[i+1], min_j c[i,j] + ExtLoop(i,j) + f3[j+1]),   f3[k > W-4] = 0,   MFE = f3[1] (= f5[W]),
 // whose rows are needed in DESCENDING order — and row i of the scratch is complete as soon as diagonal W-i is, so the
-// sweep trails the fill inside the same fold: the helper wave of the odd diagonal group sweeps up to SF_DEFER_ROWS rows in
+// sweep trails the fill inside the same fold: the helper wave of the odd diagonal group sweeps up to DROWS rows in
 // every step of the long-diagonal phase, in the slack it has there (loads issued before its own work, consumed after
 // it), and only the rows the last step completes are left for the end of the fold.  One scratch per workgroup.
 // State: lane l holds f3[j+1] of its columns j = l+1, l+65, ...; f3 of the row above the next one.
-#define SF_DEFER 1
-#define SF_DEFER_256 1  // the wide kernel trails too (four columns per lane)
-#define SF_DEFER_W200 1
-#define SF_DEFER_ROWS_256 3
+#define SF_DEFER_ROWS_256 3  // rows in flight per step in the W = 200 instantiation (four columns per lane)
 template <int NQ>
 struct SfTrail {
   int F[NQ];   // lane l: f3[j+1] for the columns j = l+1+64q (0 until row j+1 has been swept)
@@ -1502,13 +1473,27 @@ __device__ __forceinline__ void sf_trail_result(const SfTrail<NQ> &T, const int 
 
 
 // @section kernel_prologue
+// The kinds of step of a fold, in the order they run.  Each kind is a loop of its own at the end of the kernel and an instantiation
+// of its own of the step body: the same code, but every loop gets its own register allocation and schedule.
+enum SfStep {
+  SF_STEP_SIZED,    // d0 < SF_FAST_TINY_D0: the cell code that tests every loop size against the diagonal
+  SF_STEP_GUARDED,  // d0 < SF_FAST_CHUNK_D0: straight-line code with guarded size tables, batches above the limit skipped
+  SF_STEP_UNSPLIT,  // every loop size exists; every wave works on cells of its own
+  SF_STEP_SPLIT,    // d0 >= split_d0: a diagonal's cells fit the main waves, the others help (merged helper: dml2 chunks of 32 lanes)
+  SF_STEP_SPLIT16,  // ... merged-helper instantiations, d0 >= W - 30: dml2 chunks of 16 lanes
+  SF_STEP_SPLIT8,   // ... d0 >= W - 14: chunks of 8 lanes
+  SF_STEP_NARROW,   // wide kernel, d0 >= narrow_d0: a diagonal's cells fit ONE wave (one main + one helper, two on the multiloop split)
+};
+template <SfStep K>
+using SfStepTag = std::integral_constant<SfStep, K>;
+
 // the poison build's pattern for int16 entry x (see PZ below)
 __device__ __forceinline__ int16_t sf_poison16(const int poison, const int x) {
   const int k = poison == 5 ? 1 + (int)(((uint32_t)x * 2654435761u) >> 30) : poison;
   return (int16_t)(k == 1 ? -32768 : (k == 2 ? -28000 : (k == 3 ? 0 : 32767)));
 }
 
-// MG: the merged helper (narrow kernel, W < SF_HELP_MERGE_MAXW; the launcher picks the instantiation)
+// MG: the merged helper (narrow kernel: W < SF_HELP_MERGE_MAXW and the W = 120 instantiation, see SF_FAST_INSTANCES)
 // HC: every fold has its own hard constraint (cons_rows + seq * W, W characters) and / or Deigan pseudo-energies
 // (sc_rows + seq * W, dcal/mol per nucleotide): the constrained native windows of `-c` / `--react` (sf_fold_constrained)
 // PZ: the poison build (SCANFOLD_MFE_POISON, tests only): before every fold each LDS byte the fold has not written itself —
@@ -1558,21 +1543,20 @@ __global__ __launch_bounds__(2 * NG, SF_FAST_WAVES_PER_SIMD) void sf_mfe_fast_ke
   uint8_t *tRPair = (uint8_t *)(tab + SF_FAST_TAB_OLD);
   int16_t *t23in = tab + SF_FAST_TAB_OLD + 32;
   X.tRPair = tRPair; X.t23in = t23in;
-  (void)Lo.off_red;
   int32_t *flag = (int32_t *)(smem + Lo.off_flag);
   uint8_t *S = (uint8_t *)(smem + Lo.off_S);
   X.S = S;
   X.D = D; X.F = F; X.R = Rows; X.W = W; X.fold = FOLD; X.maxd = D->max_pair_dist;
-  constexpr bool MERGE = MG && SF_HELP_MERGE && (NG == 128);
+  constexpr bool MERGE = MG && (NG == 128);
   // the split steps' generic-loop recurrence with its state unpacked (SfHU): the W = 120 instantiation
   // (every narrow instantiation: +2-3 % at W = 64 .. 117 on top of the loops by kind, W = 128 +-0; the wide kernel measured 0.5-1.5 %
   // SLOWER with it — W = 200: 55.1 -> 55.6 ms per 65 536 folds, the generic wide instantiation at W = 136 .. 250 — and stays packed)
-  constexpr bool UNPK = SF_FAST_UNPACK && (NG == 128) && SF_FAST_DML2;
-  constexpr bool BYKIND = SF_LOOPS_BY_KIND != 0;  // the steps of a fold as one loop per kind of step (see the loops)
-  // ... and the split steps of the merged-helper instantiations once more by the chunk width of their two-cells-per-lane multiloop
+  constexpr bool UNPK = SF_FAST_UNPACK && (NG == 128);
+  // The steps of a fold run as one loop per kind of step (SfStep, the loops at the end of the kernel) — and the split steps of
+  // the merged-helper instantiations as three, by the chunk width of their two-cells-per-lane multiloop
   // split, the width a compile-time constant in each (W = 120: 56.2 -> 55.4 ms per 262 144 folds, W = 100 +1.4 %; the instantiation
   // without the merged helper, W = 118 .. 128, measured 1.2 % slower with it)
-  constexpr bool LGLOOPS = BYKIND && MG && (NG == 128) && SF_FAST_DML2;
+  constexpr bool LGLOOPS = MG && (NG == 128);
   // rolling-row offsets from SfFastRows (see sf_fast_cell): 1 = yes, 2 = yes + the long read batches of the generic merged-helper
   // instantiation, 0 = no (the generic wide kernel)
   constexpr int TBLK = WT > 0 ? 1 : (NG == 128 ? (MG ? 2 : 1) : 0);
@@ -1614,14 +1598,14 @@ __global__ __launch_bounds__(2 * NG, SF_FAST_WAVES_PER_SIMD) void sf_mfe_fast_ke
   // middle waves — the other waves of the group then work as helpers (see `split` below).
   constexpr int CENTRE = (NG == 256) ? 128 : 32;
   constexpr bool SHARE = SF_DML_HELPER_BIAS(NG, WT) < 10000;  // the helper waves take part of the multiloop split
-  constexpr bool DML2 = (NG == 128) && SF_FAST_DML2;    // split steps: the main wave splits two cells per lane (sf_fast_dml2)
+  constexpr bool DML2 = (NG == 128);                    // split steps: the main wave splits two cells per lane (sf_fast_dml2)
   const int OFFs = ((W + 1) >> 1) - CENTRE;                  // signed: v = tg + OFFs (mod NG)
   const int OFF = (NG > 64) ? (OFFs + NG) & (NG - 1) : 0;
   const int v = (tg + OFF) & (NG - 1);
   // first even diagonal from which the cells of both groups lie in the main lanes: tg in [0, 63] (NG = 128, W >= 64
   // so that nothing wraps) or [64, 191] (NG = 256)
   constexpr int MAIN_LO = (NG == 256) ? 64 : 0, MAIN_HI = (NG == 256) ? 191 : 63;
-  const bool can_split = SF_FAST_SPLIT && ((NG == 128 && W >= 64) || (NG == 256 && SF_FAST_SPLIT_256));
+  const bool can_split = (NG == 128 && W >= 64) || NG == 256;
   const int split_d0 = can_split ? ((sfd_max(sfd_max(SFD_MAXLOOP + 6, 2 * (MAIN_LO - 1 + OFFs)), 2 * (W - OFFs - MAIN_HI)) + 1) & ~1) : 1 << 30;
   // NARROW (wide kernel, round 4): from the even diagonal where the cells of a diagonal fit ONE wave (lanes 96..159 of the group,
   // <= 62 cells: d0 >= 138 at W = 200) the two main + two helper waves of a group are twice what the work needs — both mains
@@ -1629,7 +1613,7 @@ __global__ __launch_bounds__(2 * NG, SF_FAST_WAVES_PER_SIMD) void sf_mfe_fast_ke
   // (helper), waves 2 and 3 only keep the barriers; the per-thread state that follows a centre (the recurrence's 14 registers,
   // the enclosed cell's split minimum, the even group's neighbour term) changes lanes ONCE, through the unused ends of 32 rows of
   // the interleaved ring (a row holds <= 94 cells by then: dwords 100..163 of each row are free; needs W - 4 >= 164).
-  constexpr bool NARROW = (NG == 256) && SF_FAST_NARROW_256;
+  constexpr bool NARROW = (NG == 256);
   const int narrow_d0 = (NARROW && can_split && W >= 168)
                             ? sfd_max(split_d0, (sfd_max(2 * (96 - 1 + OFFs), 2 * (W - OFFs - 159)) + 1) & ~1) : 1 << 30;
 
@@ -1638,9 +1622,8 @@ __global__ __launch_bounds__(2 * NG, SF_FAST_WAVES_PER_SIMD) void sf_mfe_fast_ke
   // (round 2, with the sweep deferred to the next fold: the generic wide kernel gained 4-5 % — W = 136 / 160 / 256:
   // 1.35 -> 1.43 M, 1.09 -> 1.15 M, 327 -> 342 k; in the W = 200 instantiation the sweeper's state spills ~50 B/lane:
   // with four rows in flight it loses what it saves, with two it is +0.8 %, 894 -> 900 k)
-  constexpr bool DEFER = SF_DEFER && (NG == 128 || (SF_DEFER_256 && (WT != 200 || SF_DEFER_W200)));
   constexpr int NQ = NG / 64;  // columns per lane of the sweeper wave
-  const bool sweeper = DEFER && SF_WAVE_UNIFORM(tid >> 6) == (NG == 128 ? 3 : 7);  // a helper wave of the odd group
+  const bool sweeper = SF_WAVE_UNIFORM(tid >> 6) == (NG == 128 ? 3 : 7);  // a helper wave of the odd group
   const int n_split_steps = split_d0 < W ? (W - split_d0 + 1) / 2 : 0;
   // rows per step: what finishes the sweep inside the split phase, but no more than DROWS in flight (their loads live
   // in registers across the wave's own work: 4 x 2 columns in the narrow kernel, 2 x 4 in the wide one); what is
@@ -1648,7 +1631,7 @@ __global__ __launch_bounds__(2 * NG, SF_FAST_WAVES_PER_SIMD) void sf_mfe_fast_ke
   constexpr int DROWS = (NG == 128 || WT != 200) ? 4 : SF_DEFER_ROWS_256;
   const int defer_need = n_split_steps > 0 ? (W - SFD_TURN - 1 + n_split_steps - 1) / n_split_steps : 0;
   const int defer_rows = sfd_min(defer_need, DROWS);
-  const bool defer_on = DEFER && n_split_steps >= 8 && defer_need <= 4;
+  const bool defer_on = n_split_steps >= 8 && defer_need <= 4;
   SfTrail<NQ> T;
 #pragma unroll
   for (int q = 0; q < NQ; q++) T.F[q] = 0;
@@ -1749,28 +1732,24 @@ __global__ __launch_bounds__(2 * NG, SF_FAST_WAVES_PER_SIMD) void sf_mfe_fast_ke
       if (lane == 0) list[127] = (uint8_t)(cA + __popcll(mB));
     };
 // @section step_control
-    // One step = the diagonals d0 (even group) and d0 + 1 (odd group).  The body is instantiated once per kind of step (PH).
+    // One step = the diagonals d0 (even group) and d0 + 1 (odd group).  The body is instantiated once per kind of step (SfStep).
     SfHU HU;
-    auto step = [&](const int d0, auto phase_tag) {
-      // PH: the kind of step this instantiation of the body is for (BYKIND: one loop per kind, see below) — 3: d0 < 12 (size-tested
-      // code), 4: 12 <= d0 < 36 (guarded code), 1: the unsplit steps from d0 = 36 on, 2: the split steps, 5: the wide kernel's split
-      // steps from the diagonal on where a diagonal's cells fit one wave (NARROW); 0: any (one loop)
-      constexpr int PH = decltype(phase_tag)::value;
-      constexpr bool P2 = (PH == 2 || PH >= 5);  // a split step (5: the wide kernel's NARROW phase, 6 / 7: the narrow kernel's split steps
-                                                 // whose two-cells-per-lane multiloop split runs in chunks of 16 / 8 lanes — loops of their own as well)
-      constexpr int LGC = PH == 6 ? 4 : (PH == 7 ? 3 : (PH == 2 && LGLOOPS ? 5 : 0));
-      constexpr bool DO_G = (PH == 0 || PH == 3), DO_CH = (PH == 0 || PH == 4);
+    auto step = [&](const int d0, auto kind_tag) {
+      constexpr SfStep KIND = decltype(kind_tag)::value;
+      // lanes per chunk of the two-cells-per-lane multiloop split, as a power of two (0: sf_fast_dml2 derives it from d)
+      constexpr int LGC = KIND == SF_STEP_SPLIT16 ? 4 : (KIND == SF_STEP_SPLIT8 ? 3 : (KIND == SF_STEP_SPLIT && LGLOOPS ? 5 : 0));
+      constexpr bool DO_G = KIND == SF_STEP_SIZED, DO_CH = KIND == SF_STEP_GUARDED;
       const int d = d0 + grp;
       if (d0 == SFD_TURN + 1 + 2 && tid == 0) *next_slot = fetched;            // the barriers of this step publish it
       if (d0 == SFD_TURN + 1 + 4) next_seq = SF_WAVE_UNIFORM(*next_slot);
-      // Long diagonals (d0 >= split_d0): the cells of a group fit its first wave, so the second wave — which would
+      // Split steps (the long diagonals, d0 >= split_d0): the cells of a group fit its first wave, so the second wave — which would
       // idle — mirrors it (same lane -> same cell) and takes the special loops and the bulge / 1xn minima of
       // those cells, while the first does the generic-loop recurrence and the multiloop split; the partial
       // result crosses in LDS (in the C1N entry the cell will publish, unread until the next step) at a barrier,
       // then the first wave finishes the cell.  The dependent chain of such a step is ~45 % shorter.
-      const bool split = P2 || (!BYKIND && d0 >= split_d0);  // (BYKIND: the split steps are the last loop)
       // helper lanes mirror a main lane 64 away: NG = 128: wave 1 -> wave 0; NG = 256: wave 0 -> wave 1, wave 3 -> wave 2
-      const bool narrow = NARROW && (PH == 5 || (PH == 0 && d0 >= narrow_d0));
+      constexpr bool split = KIND >= SF_STEP_SPLIT;
+      constexpr bool narrow = KIND == SF_STEP_NARROW;  // (see NARROW above; its first step moves the centres' state)
       if (NARROW && d0 == narrow_d0) {
         // the one-time move of the centres' state: old owners tg = 96..159 -> new owners tg - 32 = 64..127
         uint32_t *const xa = (uint32_t *)X.BN;  // dword = cell of the interleaved ring; row r, cell 100 + lane
@@ -1793,7 +1772,7 @@ __global__ __launch_bounds__(2 * NG, SF_FAST_WAVES_PER_SIMD) void sf_mfe_fast_ke
       const bool helper = split && (NG == 256 ? (narrow ? tg < 64 : (tg < 64 || tg >= 192)) : tg >= 64);
       const int vh = NG == 256 ? (narrow ? v + 96 : (tg < 64 ? v + 64 : v - 64)) : v - 64;
       // (narrow: lanes 64..127 take the cells of lanes 96..159, lanes 0..63 mirror them; lanes >= 128 have no cell)
-      const int vm = (NARROW && narrow) ? ((v + 32) & (NG - 1)) : v;
+      const int vm = narrow ? ((v + 32) & (NG - 1)) : v;
       // (narrow: waves 2 and 3 of the group would idle — they mirror the main wave too and take most of the multiloop split, the
       // part of a cell that keeps growing with d: 40 % of the terms each, the main wave the first fifth; their partial minima
       // cross in the dwords the centres' state moved through)
@@ -1827,7 +1806,7 @@ __global__ __launch_bounds__(2 * NG, SF_FAST_WAVES_PER_SIMD) void sf_mfe_fast_ke
         if (DO_G && d0 < 8) sf_fast_cell<true, WT, SF_SEC_ALL, false, FOLD, 1>(X, d, i, valid, slot2, slotd, H, HU, ovf, grp == 0, fnb, fpart, dec, eh, e0, dprev, pub);
         else if (DO_G && d0 < SF_FAST_TINY_D0) sf_fast_cell<true, WT, SF_SEC_ALL, false, FOLD, 5>(X, d, i, valid, slot2, slotd, H, HU, ovf, grp == 0, fnb, fpart, dec, eh, e0, dprev, pub);
         else if (DO_CH && d0 < SF_FAST_CHUNK_D0) sf_fast_cell<false, WT, SF_SEC_ALL, true, FOLD, SFD_MAXLOOP, TBLK>(X, d, i, valid, slot2, slotd, H, HU, ovf, grp == 0, fnb, fpart, dec, eh, e0, dprev, pub);
-        else if (!P2 && !split) sf_fast_cell<false, WT, SF_SEC_ALL, false, FOLD, SFD_MAXLOOP, TBLK, false, UNPK && PH == 1>(X, d, i, valid, slot2, slotd, H, HU, ovf, grp == 0, fnb, fpart, dec, eh, e0, dprev, pub);
+        else if (!split) sf_fast_cell<false, WT, SF_SEC_ALL, false, FOLD, SFD_MAXLOOP, TBLK, false, UNPK && KIND == SF_STEP_UNSPLIT>(X, d, i, valid, slot2, slotd, H, HU, ovf, grp == 0, fnb, fpart, dec, eh, e0, dprev, pub);
         else if (DML4 && narrow) {
           // terms m = 4 .. d-5: main [4, cA), wave 2 [cA, cB), wave 3 [cB, d-5]
           const int nmain = dml_terms / 5, cA = SFD_TURN + 1 + nmain, cB = cA + (dml_terms - nmain + 1) / 2;
@@ -1845,10 +1824,11 @@ __global__ __launch_bounds__(2 * NG, SF_FAST_WAVES_PER_SIMD) void sf_mfe_fast_ke
         }
         else if (!helper) {
           if (SHARE) sf_fast_cell<false, WT, SF_SEC_P1 | SF_SEC_C0 | SF_SEC_DML | SF_SEC_PRE, false, FOLD, SFD_MAXLOOP, TBLK>(X, d, i, valid, slot2, slotd, H, HU, ovf, grp == 0, fnb, fpart, dec, eh, e0, dprev, pub, SFD_TURN + 1, dml_cut - 1);
-          else if (DML2) {
+          else {
+            static_assert(SHARE || DML2, "a main wave either shares the multiloop split with its helpers (NG = 256) or runs it two cells per lane (NG = 128)");
             dec = sf_fast_dml2<WT, LGC>(X, d, tid & 63, i, valid);
-            sf_fast_cell<false, WT, SF_SEC_P1 | SF_SEC_C0 | SF_SEC_PRE, false, FOLD, SFD_MAXLOOP, TBLK, false, UNPK && P2>(X, d, i, valid, slot2, slotd, H, HU, ovf, grp == 0, fnb, fpart, dec, eh, e0, dprev, pub);
-          } else sf_fast_cell<false, WT, SF_SEC_P1 | SF_SEC_C0 | SF_SEC_DML | SF_SEC_PRE, false, FOLD, SFD_MAXLOOP, TBLK>(X, d, i, valid, slot2, slotd, H, HU, ovf, grp == 0, fnb, fpart, dec, eh, e0, dprev, pub);
+            sf_fast_cell<false, WT, SF_SEC_P1 | SF_SEC_C0 | SF_SEC_PRE, false, FOLD, SFD_MAXLOOP, TBLK, false, UNPK && split>(X, d, i, valid, slot2, slotd, H, HU, ovf, grp == 0, fnb, fpart, dec, eh, e0, dprev, pub);
+          }
         } else if (MERGE) {
           // Merged helper (W <= 128).  ONE helper wave serves both diagonals of the step: it works on the list of the
           // cells of d0 and d0+1 that can pair (build_list above; 3 of 8 cells, so ordinary sequences fit wave 1's 64
@@ -1935,32 +1915,25 @@ __global__ __launch_bounds__(2 * NG, SF_FAST_WAVES_PER_SIMD) void sf_mfe_fast_ke
     };
     {
       int d0 = SFD_TURN + 1;
-      // BYKIND: the steps of a fold as four loops, one per kind of step — d0 < 12 (size-tested code), 12 <= d0 < 36 (guarded code),
-      // the unsplit steps from d0 = 36 on, the split steps — instead of one loop with the kinds as branches: the same code, but every
-      // loop gets its own register allocation and schedule (W = 120, per 262 144 folds: one loop 59.0 ms; two loops, the split steps
-      // apart, 59.8 packed / 57.5 with the split steps' state unpacked; three loops 56.6; four 56.2).
+      // One loop per kind of step, in SfStep's order.
       // UNPK: the state is unpacked at d0 = 36 — the first diagonal pair on which every loop size exists (the guarded code before it
       // needs the saturating packed adds; unpacked with v_add_i16 clamp it measured slower: 58.8 ms).
-      if constexpr (BYKIND) {
-        for (; d0 < SF_FAST_TINY_D0 && d0 < W; d0 += 2) step(d0, std::integral_constant<int, 3>{});
-        for (; d0 < SF_FAST_CHUNK_D0 && d0 < W; d0 += 2) step(d0, std::integral_constant<int, 4>{});
-        if constexpr (UNPK) {
+      for (; d0 < SF_FAST_TINY_D0 && d0 < W; d0 += 2) step(d0, SfStepTag<SF_STEP_SIZED>{});
+      for (; d0 < SF_FAST_CHUNK_D0 && d0 < W; d0 += 2) step(d0, SfStepTag<SF_STEP_GUARDED>{});
+      if constexpr (UNPK) {
 #pragma unroll
-          for (int x = 0; x < 27; x++) HU.v[x] = (short)((x & 1) ? (H[x >> 1] >> 16) : (H[x >> 1] & 0xffffu));
-        }
-        for (; d0 < split_d0 && d0 < W; d0 += 2) step(d0, std::integral_constant<int, 1>{});
-        if constexpr (LGLOOPS) {
-          // (chunks of 32 lanes while a diagonal has more than 30 cells, 16 down to 15 cells, then 8: d0 >= W - 30 / W - 14)
-          for (; d0 < W - 30 && d0 < W; d0 += 2) step(d0, std::integral_constant<int, 2>{});
-          for (; d0 < W - 14 && d0 < W; d0 += 2) step(d0, std::integral_constant<int, 6>{});
-          for (; d0 < W; d0 += 2) step(d0, std::integral_constant<int, 7>{});
-        }
-        for (; d0 < (NARROW ? narrow_d0 : W) && d0 < W; d0 += 2) step(d0, std::integral_constant<int, 2>{});
-        if constexpr (NARROW)
-          for (; d0 < W; d0 += 2) step(d0, std::integral_constant<int, 5>{});
-      } else {
-        for (; d0 < W; d0 += 2) step(d0, std::integral_constant<int, 0>{});
+        for (int x = 0; x < 27; x++) HU.v[x] = (short)((x & 1) ? (H[x >> 1] >> 16) : (H[x >> 1] & 0xffffu));
       }
+      for (; d0 < split_d0 && d0 < W; d0 += 2) step(d0, SfStepTag<SF_STEP_UNSPLIT>{});
+      if constexpr (LGLOOPS) {
+        // (chunks of 32 lanes while a diagonal has more than 30 cells, 16 down to 15 cells, then 8: d0 >= W - 30 / W - 14)
+        for (; d0 < W - 30 && d0 < W; d0 += 2) step(d0, SfStepTag<SF_STEP_SPLIT>{});
+        for (; d0 < W - 14 && d0 < W; d0 += 2) step(d0, SfStepTag<SF_STEP_SPLIT16>{});
+        for (; d0 < W; d0 += 2) step(d0, SfStepTag<SF_STEP_SPLIT8>{});
+      }
+      for (; d0 < (NARROW ? narrow_d0 : W) && d0 < W; d0 += 2) step(d0, SfStepTag<SF_STEP_SPLIT>{});
+      if constexpr (NARROW)
+        for (; d0 < W; d0 += 2) step(d0, SfStepTag<SF_STEP_NARROW>{});
     }
 
 // @section fold_epilogue
@@ -2004,27 +1977,38 @@ __global__ __launch_bounds__(2 * NG, SF_FAST_WAVES_PER_SIMD) void sf_mfe_fast_ke
 #undef FLEN
 }
 
-template <int NG, int WT, bool MG = false, bool HC = false, bool PZ = false>
-static inline hipError_t sf_fast_configure_one() {
-  return hipFuncSetAttribute((const void *)sf_mfe_fast_kernel<NG, WT, MG, HC, PZ>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+// Every instantiation of the kernel, X(NG, WT, MG, HC, PZ): what sf_fast_configure prepares and sf_fast_launch can start.
+// W = 120 is ScanFold's default window (ScanFold-Scan.py:37) and W = 200 is BASELINE config 5: they get instantiations with the
+// width folded in (less scalar index arithmetic, fewer spills); any other width, and every constrained fold (HC: per-fold hard
+// constraint / Deigan pseudo-energies), runs a generic one.  PZ: the poison builds (SCANFOLD_MFE_POISON, tests only).
+#define SF_FAST_INSTANCES(X)                                                                          \
+  X(128, 0, false, false, false) X(128, 0, true, false, false) X(128, 120, true, false, false)        \
+  X(256, 200, false, false, false) X(256, 0, false, false, false)                                     \
+  X(128, 0, false, true, false) X(128, 0, true, true, false) X(256, 0, false, true, false)            \
+  X(128, 0, false, false, true) X(128, 0, true, false, true) X(128, 120, true, false, true)           \
+  X(256, 200, false, false, true) X(256, 0, false, false, true)
+struct SfFastInstance {
+  int ng, wt;
+  bool mg, hc, pz;
+};
+// the instantiation that folds windows of W nt
+static inline SfFastInstance sf_fast_select(int W, bool hc, bool pz) {
+  SfFastInstance s;
+  s.ng = sf_fast_threads(W) / 2;
+  s.wt = (!hc && (W == 120 || W == 200)) ? W : 0;
+  s.mg = s.wt == 120 || W < SF_HELP_MERGE_MAXW;
+  s.hc = hc;
+  s.pz = pz;
+  return s;
 }
 static inline hipError_t sf_fast_configure() {
   hipError_t e;
-  if ((e = sf_fast_configure_one<128, 0>()) != hipSuccess) return e;
-  if ((e = sf_fast_configure_one<128, 0, true>()) != hipSuccess) return e;
-  if ((e = sf_fast_configure_one<128, 120, SF_MG120 != 0>()) != hipSuccess) return e;
-  if ((e = sf_fast_configure_one<256, 200>()) != hipSuccess) return e;
-  if ((e = sf_fast_configure_one<256, 0>()) != hipSuccess) return e;
-  // the instantiations for constrained folds (generic widths only)
-  if ((e = sf_fast_configure_one<128, 0, false, true>()) != hipSuccess) return e;
-  if ((e = sf_fast_configure_one<128, 0, true, true>()) != hipSuccess) return e;
-  if ((e = sf_fast_configure_one<256, 0, false, true>()) != hipSuccess) return e;
-  // the poison builds (SCANFOLD_MFE_POISON: tests only)
-  if ((e = sf_fast_configure_one<128, 0, false, false, true>()) != hipSuccess) return e;
-  if ((e = sf_fast_configure_one<128, 0, true, false, true>()) != hipSuccess) return e;
-  if ((e = sf_fast_configure_one<128, 120, SF_MG120 != 0, false, true>()) != hipSuccess) return e;
-  if ((e = sf_fast_configure_one<256, 200, false, false, true>()) != hipSuccess) return e;
-  return sf_fast_configure_one<256, 0, false, false, true>();
+#define SF_X(NG, WT, MG, HC, PZ)                                                                                                  \
+  e = hipFuncSetAttribute((const void *)sf_mfe_fast_kernel<NG, WT, MG, HC, PZ>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
+  if (e != hipSuccess) return e;
+  SF_FAST_INSTANCES(SF_X)
+#undef SF_X
+  return hipSuccess;
 }
 
 // grid / LDS / scratch for n folds of W nt on a chip with n_cu CUs
@@ -2047,30 +2031,18 @@ static inline void sf_fast_geometry(int W, int n_cu, int n, int *grid, int *thre
   *scratch = (size_t)((gsz + 7) & ~7LL) * SF_CG_ENTRIES(W) * sizeof(int16_t);  // whole groups of eight: sf_fast_scratch_slot
 }
 
-// W = 120 is ScanFold's default window (ScanFold-Scan.py:37) and W = 200 is BASELINE config 5: they get
-// instantiations with the width folded in (less scalar index arithmetic, fewer spills); any other width runs
-// the generic instantiation
-template <bool PZ, typename... A>
-static inline void sf_fast_launch_pz(int grid, int threads, size_t lds, hipStream_t st, const uint8_t *seqs, int n, int W,
-                                     A... args) {
-  if (threads == 256 && W == 120) SF_LAUNCH((sf_mfe_fast_kernel<128, 120, SF_MG120 != 0, false, PZ>), grid, 256, lds, st, seqs, n, W, args...);
-  else if (threads == 256 && W < SF_HELP_MERGE_MAXW && SF_HELP_MERGE) SF_LAUNCH((sf_mfe_fast_kernel<128, 0, true, false, PZ>), grid, 256, lds, st, seqs, n, W, args...);
-  else if (threads == 256) SF_LAUNCH((sf_mfe_fast_kernel<128, 0, false, false, PZ>), grid, 256, lds, st, seqs, n, W, args...);
-  else if (W == 200) SF_LAUNCH((sf_mfe_fast_kernel<256, 200, false, false, PZ>), grid, 512, lds, st, seqs, n, W, args...);
-  else SF_LAUNCH((sf_mfe_fast_kernel<256, 0, false, false, PZ>), grid, 512, lds, st, seqs, n, W, args...);
-}
-// poison != 0: the poison builds (tests only); the last kernel argument
+// Starts the instantiation sf_fast_select names; false if SF_FAST_INSTANCES does not hold it (nothing is started then).
+// poison != 0: the poison builds (tests only); the kernel's last argument
 template <typename... A>
-static inline void sf_fast_launch(int poison, int grid, int threads, size_t lds, hipStream_t st, const uint8_t *seqs, int n, int W,
-                                  A... args) {
-  if (poison) sf_fast_launch_pz<true>(grid, threads, lds, st, seqs, n, W, args..., poison);
-  else sf_fast_launch_pz<false>(grid, threads, lds, st, seqs, n, W, args..., 0);
-}
-// constrained folds (per-fold hard constraint / Deigan pseudo-energies; every fold traced)
-template <typename... A>
-static inline void sf_fast_launch_hc(int grid, int threads, size_t lds, hipStream_t st, const uint8_t *seqs, int n, int W,
-                                     A... args) {
-  if (threads == 256 && W < SF_HELP_MERGE_MAXW && SF_HELP_MERGE) SF_LAUNCH((sf_mfe_fast_kernel<128, 0, true, true>), grid, 256, lds, st, seqs, n, W, args..., 0);
-  else if (threads == 256) SF_LAUNCH((sf_mfe_fast_kernel<128, 0, false, true>), grid, 256, lds, st, seqs, n, W, args..., 0);
-  else SF_LAUNCH((sf_mfe_fast_kernel<256, 0, false, true>), grid, 512, lds, st, seqs, n, W, args..., 0);
+static inline bool sf_fast_launch(bool hc, int poison, int grid, int threads, size_t lds, hipStream_t st, const uint8_t *seqs, int n,
+                                  int W, A... args) {
+  const SfFastInstance s = sf_fast_select(W, hc, poison != 0);
+#define SF_X(NG, WT, MG, HC, PZ)                                                                                    \
+  if (s.ng == NG && s.wt == WT && s.mg == MG && s.hc == HC && s.pz == PZ && threads == 2 * NG) {                    \
+    SF_LAUNCH((sf_mfe_fast_kernel<NG, WT, MG, HC, PZ>), grid, 2 * NG, lds, st, seqs, n, W, args..., poison);         \
+    return true;                                                                                                    \
+  }
+  SF_FAST_INSTANCES(SF_X)
+#undef SF_X
+  return false;
 }

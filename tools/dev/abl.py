@@ -17,7 +17,7 @@ FAST = "scanfold_amd/csrc/sf_mfe_fast.hip.h"
 CELLS = "      if (__ballot(valid)) {\n        if (DO_G && d0 < 8)"
 FIN = "        if (!helper && !dmlw && __ballot(valid)) {"
 DML2 = "            dec = sf_fast_dml2<WT, LGC>(X, d, tid & 63, i, valid);"
-MAINCALL = ("            sf_fast_cell<false, WT, SF_SEC_P1 | SF_SEC_C0 | SF_SEC_PRE, false, FOLD, SFD_MAXLOOP, TBLK, false, UNPK && P2>(X, d, i, valid, "
+MAINCALL = ("            sf_fast_cell<false, WT, SF_SEC_P1 | SF_SEC_C0 | SF_SEC_PRE, false, FOLD, SFD_MAXLOOP, TBLK, false, UNPK && split>(X, d, i, valid, "
             "slot2, slotd, H, HU, ovf, grp == 0, fnb, fpart, dec, eh, e0, dprev, pub);")
 MGHCALL = "            sf_fast_cell<false, WT, SF_SEC_HELP, false, FOLD, SFD_MAXLOOP, TBLK, true>(Xh, d0 + g, iC,"
 
@@ -27,8 +27,8 @@ HOST = "scanfold_amd/csrc/scanfold_hip.hip"
 # steps), the end of the finish [1], the exit of the end-of-step barrier [2], the end of the step (after the fML fix-up) [3];
 # [4] counts.  The sums live behind the status word; sf_prof_get dumps them to $SF_STAMP_OUT (tools/dev/stamp_report.py reads it).
 STAMP_PATCHES = [
-    (FAST, "      constexpr bool DO_G = (PH == 0 || PH == 3), DO_CH = (PH == 0 || PH == 4);\n      const int d = d0 + grp;\n",
-     "      constexpr bool DO_G = (PH == 0 || PH == 3), DO_CH = (PH == 0 || PH == 4);\n      const int d = d0 + grp;\n"
+    (FAST, "      constexpr bool DO_G = KIND == SF_STEP_SIZED, DO_CH = KIND == SF_STEP_GUARDED;\n      const int d = d0 + grp;\n",
+     "      constexpr bool DO_G = KIND == SF_STEP_SIZED, DO_CH = KIND == SF_STEP_GUARDED;\n      const int d = d0 + grp;\n"
      "      unsigned long long *const SFP = (unsigned long long *)(status + 64) + (size_t)(((d0 >> 1) * 4 + (tid >> 6)) * 8);\n"
      "      const bool SFL = (tid & 63) == 0 && (blockIdx.x & 63) == 5;\n"
      "      const long long SFT0 = SFL ? (long long)clock64() : 0;\n"),
