@@ -40,7 +40,8 @@ typedef enum sf_status {
   SF_ERR_NO_DEVICE = -7,    /* no usable GPU */
   SF_ERR_INTERNAL = -8,     /* a traceback found no decomposition (would indicate a kernel bug) */
   SF_ERR_CONSTRAINT = -9,   /* unbalanced brackets in a window's constraint string (ViennaRNA aborts there) */
-  SF_ERR_TABLE = -10        /* sf_tabulate_pairs: an unbalanced structure string, or window starts not ascending */
+  SF_ERR_TABLE = -10,       /* sf_tabulate_pairs: an unbalanced structure string, or window starts not ascending */
+  SF_ERR_RANGE = -11        /* sf_pf_long (scanfold_hip_long.h): the partition function left FP64's range under every scale tried */
 } sf_status;
 
 #define SF_MAX_W 400 /* longest window the kernels accept */

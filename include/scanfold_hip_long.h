@@ -5,6 +5,9 @@
  *
  * Kept out of scanfold_hip.h on purpose: that header is the contract the CPU twin of the C ABI implements symbol for
  * symbol, and the twin has no long fold.  Bind these symbols only where the loaded library exports them.
+ *
+ * sf_fold_long gives the MFE and its structure, sf_pf_long the partition function (ensemble free energy, centroid, ensemble
+ * diversity) of the same whole record.  Soft constraints (SHAPE) are not provided past SF_MAX_W.
  */
 #ifndef SCANFOLD_HIP_LONG_H
 #define SCANFOLD_HIP_LONG_H
@@ -30,6 +33,27 @@ int sf_fold_long(const uint8_t *seq, int L, const char *cons, int32_t *mfe_dcal_
 /* Device-event times (ms) of the phases of the last successful sf_fold_long: the fill of c / fML (one launch per
  * diagonal), the exterior loop f5, and the traceback (0 when it was not asked for).  Any pointer may be NULL. */
 int sf_fold_long_times(double *fill_ms, double *f5_ms, double *trace_ms);
+
+/* fc.pf(); fc.centroid(); fc.mean_bp_distance() — RNAfold -p — for one sequence of any length 1..SF_MAX_LONG
+ * (ScanFoldFunctions.py:758-772, rna_refold).  seq, cons as for sf_fold_long; the resident parameter set (rescaled
+ * temperature sets included) and base-pair span apply.  mfe_dcal_hint: NULL, or the sequence's MFE in dcal/mol under the same
+ * model and constraint (sf_fold_long's), from which the per-nucleotide scale of the first attempt is taken; without it a fixed
+ * estimate is used and a long record usually costs a second inside pass.  Outputs: the ensemble free energy (kcal/mol), the
+ * mean base-pair distance 2 sum p (1 - p), the centroid (pairs with p > 0.5; L+1 bytes, or NULL) and its mean distance to
+ * the ensemble.  Any output pointer may be NULL.  Two calls with the same arguments on the same device return bit-identical
+ * results.  Agreement with sf_pf_batch / sf_fold_constrained at L <= SF_MAX_W is to rounding (sums in another order).
+ * The tables live in device memory, allocated for the call and freed before it returns:
+ *   56 * L (L+1) / 2 + ~60 L bytes  (25.0 GB at L = 29 903, 30.1 GB at SF_MAX_LONG).
+ * Not enough device memory: SF_ERR_HIP with the text in sf_last_hip_error().  Unbalanced brackets: SF_ERR_CONSTRAINT.
+ * L < 1, L > SF_MAX_LONG, seq NULL: SF_ERR_BAD_ARG.  The scaled tables left FP64's range on every attempt: SF_ERR_RANGE
+ * (no output is written). */
+int sf_pf_long(const uint8_t *seq, int L, const char *cons, const int32_t *mfe_dcal_hint, double *ens_dG, double *mean_bp_dist,
+               char *centroid_out, double *centroid_dist);
+
+/* Of the last sf_pf_long that ran: device-event times (ms) of the inside passes (all attempts, q5 / q3 included) and of the
+ * outside pass with the probabilities, the number of attempts, and the final per-nucleotide scale ln s.  Any pointer may be
+ * NULL. */
+int sf_pf_long_times(double *inside_ms, double *outside_ms, int *attempts, double *lns);
 
 #ifdef __cplusplus
 }

@@ -9,8 +9,10 @@ fc.hc_add_from_db and fc.sc_add_SHAPE_deigan (ScanFold-Scan.py:410; ScanFold.py:
 sf_fold_constrained.  RNA.duplexfold(s1, s2) (ScanFold.py:785; ScanFoldFunctions.py:824) folds through sf_duplex_batch.
 Not provided: plotting, Zarringhalam soft constraints (upstream's call fails too).
 Sequences longer than SF_MAX_W (400 nt, the window kernels' limit) fold with fc.mfe() / RNA.fold through sf_fold_long
-(whole records up to 32 767 nt: ScanFold.py --global_refold, :1509-1547), hc_add_from_db included; their partition
-function, centroid and SHAPE term do not exist and raise NotImplementedError.
+(whole records up to 32 767 nt: ScanFold.py --global_refold, :1509-1547), hc_add_from_db included.  Their partition
+function, centroid and mean base-pair distance exist in the engine (Engine.pf_long; functions.rna_refold) but this facade
+does not route to them yet: fc.pf() / fc.centroid() / fc.mean_bp_distance() raise NotImplementedError, as does the SHAPE
+term, which does not exist past 400 nt.
 """
 import numpy as np
 
@@ -111,9 +113,9 @@ class fold_compound:
         ViennaRNA's pair-propensity string (ScanFold discards it, ScanFold-Scan.py:383)."""
         self._eng = _check_md(self._model)
         if self._long():
-            raise NotImplementedError("no partition function (and so no centroid / mean base-pair distance) for a sequence "
-                                      "longer than %d nt: only the MFE of a whole record is implemented (sf_fold_long)"
-                                      % _lib.SF_MAX_W)
+            raise NotImplementedError("no partition function (and so no centroid / mean base-pair distance) through this "
+                                      "facade for a sequence longer than %d nt: only the MFE of a whole record is routed "
+                                      "(sf_fold_long); call Engine.pf_long or functions.rna_refold" % _lib.SF_MAX_W)
         if self._sc is not None:
             raise NotImplementedError("partition function with SHAPE soft constraints (the reference calls fc.pf() "
                                       "before sc_add_SHAPE_*, ScanFold.py:525-539)")

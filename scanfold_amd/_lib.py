@@ -78,6 +78,10 @@ def _header_define(header, name):
 _LONG_EXPORTS = {
     "sf_fold_long": (ctypes.c_int, [_c_u8p, ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_void_p]),
     "sf_fold_long_times": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double)] * 3),
+    "sf_pf_long": (ctypes.c_int, [_c_u8p, ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                  ctypes.c_void_p, ctypes.c_void_p]),
+    "sf_pf_long_times": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                        ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)]),
 }
 
 
@@ -319,6 +323,44 @@ class Engine:
         t = [ctypes.c_double() for _ in range(3)]
         self._check(self.lib.sf_fold_long_times(*(ctypes.byref(x) for x in t)))
         return tuple(x.value for x in t)
+
+    def has_pf_long(self):
+        return getattr(self.lib, "sf_pf_long", None) is not None
+
+    def _need_pf_long(self):
+        if not self.has_pf_long():
+            raise ScanFoldHipError("this library (%s) has no sf_pf_long: whole-record partition functions need "
+                                   "libscanfold_hip.so" % getattr(self.lib, "_name", "?"))
+
+    def pf_long(self, seq, cons=None, mfe_hint=None):
+        """fc.hc_add_from_db(cons); fc.pf(); fc.centroid(); fc.mean_bp_distance() (RNAfold -p -C, ScanFoldFunctions.py:758-772)
+        for ONE sequence of 1..SF_MAX_LONG nt -> dict(dG, mean_bp_dist, centroid, centroid_dist), the keys of one pf_batch
+        item.  mfe_hint: the sequence's MFE in dcal/mol (fold_long's), which sets the scale of the first attempt.  Raises
+        ScanFoldHipError on a library without the entry point (there is no fallback)."""
+        self._need_pf_long()
+        s = seq if isinstance(seq, (bytes, bytearray)) else str(seq).encode("ascii")
+        L = len(s)
+        c = None
+        if cons is not None:
+            c = cons if isinstance(cons, (bytes, bytearray)) else str(cons).encode("ascii")
+            if len(c) != L:
+                raise ValueError("constraint string and sequence differ in length")
+        arr = np.frombuffer(bytes(s), dtype=np.uint8) if L else np.zeros(1, dtype=np.uint8)
+        hint = None if mfe_hint is None else np.array([int(mfe_hint)], dtype=np.int32)
+        out = np.zeros(3)
+        cen = np.zeros(L + 1, dtype=np.uint8)
+        self._check(self.lib.sf_pf_long(arr.ctypes.data, L, None if c is None else bytes(c),
+                                        None if hint is None else hint.ctypes.data, out[0:].ctypes.data, out[1:].ctypes.data,
+                                        cen.ctypes.data, out[2:].ctypes.data))
+        return dict(dG=float(out[0]), mean_bp_dist=float(out[1]), centroid=bytes(cen[:L]).decode(),
+                    centroid_dist=float(out[2]))
+
+    def pf_long_times(self):
+        """-> dict(inside_ms, outside_ms, attempts, lns) of the last pf_long (device events; lns = the per-nucleotide scale)."""
+        self._need_pf_long()
+        a, b, n, l = ctypes.c_double(), ctypes.c_double(), ctypes.c_int(), ctypes.c_double()
+        self._check(self.lib.sf_pf_long_times(ctypes.byref(a), ctypes.byref(b), ctypes.byref(n), ctypes.byref(l)))
+        return dict(inside_ms=a.value, outside_ms=b.value, attempts=n.value, lns=l.value)
 
     # -- duplex folds and the LRI scan (include/scanfold_hip_duplex.h) --
     def has_duplex(self):

@@ -21,6 +21,7 @@
 #include "sf_mfe_fast.hip.h"
 #include "sf_mfe_long.hip.h"
 #include "sf_pf.hip.h"
+#include "sf_pf_long.hip.h"
 #include "sf_pf_fast.hip.h"
 #include "sf_pf_lds.hip.h"
 #include "sf_shuffle.hip.h"
@@ -57,6 +58,7 @@ struct Ctx {
     int fast_ok = 0;
     int span = 0;          // the max_bp_span its max_pair_dist field was written for
     double temperature = 37.0;
+    double pf_kT = 0.0, pf_MLbase = 1.0, pf_hp30 = 0.0;  // host copies of X.kT, X.MLbase, X.hp_init[30] (sf_pf_long)
     uint64_t used = 0;     // load counter value of its last use
   } slot[2];
   uint64_t loads = 0;
@@ -482,6 +484,7 @@ const char *sf_strerror(int status) {
     case SF_ERR_INTERNAL: return "internal error: traceback found no decomposition";
     case SF_ERR_TABLE: return "scan table: unbalanced structure string, or window starts not ascending";
     case SF_ERR_CONSTRAINT: return "unbalanced brackets in a window's constraint string";
+    case SF_ERR_RANGE: return "partition function left the FP64 range under every scale tried (sf_pf_long)";
     case SF_ERR_DUPLEX_HITS: return "LRI scan: more hits than max_hits (raise the capacity or lower the cutoff)";
     default: return "unknown status";
   }
@@ -625,6 +628,7 @@ int sf_params_load_rescaled(const void *blob, size_t nbytes, double temperature_
     }
     g.slot[k].key = key; g.slot[k].valid = true; g.slot[k].fast_ok = F.fast_ok; g.slot[k].span = g.max_bp_span;
     g.slot[k].temperature = temperature_c;
+    g.slot[k].pf_kT = X.kT; g.slot[k].pf_MLbase = X.MLbase; g.slot[k].pf_hp30 = X.hp_init[30];
     hit = k;
   } else if (g.slot[hit].span != g.max_bp_span) {  // sf_set_max_bp_span was called while the other model was the resident one
     HIPCHK(hipDeviceSynchronize());
@@ -1068,6 +1072,7 @@ double g_long_ms[3] = {0, 0, 0};  // fill, f5, traceback of the last sf_fold_lon
 struct LongBufs {
   std::vector<void *> ptrs;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  const char *who = "sf_fold_long";  // the entry point named in an out-of-memory text
   ~LongBufs() {
     hipStreamSynchronize(g.stream);
     for (void *p : ptrs) hipFree(p);
@@ -1081,7 +1086,7 @@ struct LongBufs {
     if (e != hipSuccess) {
       hipGetLastError();
       char b[512];
-      snprintf(b, sizeof b, "sf_fold_long: hipMalloc of %zu bytes (%s) failed: %s", bytes, what, hipGetErrorString(e));
+      snprintf(b, sizeof b, "%s: hipMalloc of %zu bytes (%s) failed: %s", who, bytes, what, hipGetErrorString(e));
       g.last_hip_error = b;
       *p = nullptr;
       return SF_ERR_HIP;
@@ -1195,6 +1200,195 @@ int sf_fold_long_times(double *fill_ms, double *f5_ms, double *trace_ms) {
   if (fill_ms) *fill_ms = g_long_ms[0];
   if (f5_ms) *f5_ms = g_long_ms[1];
   if (trace_ms) *trace_ms = g_long_ms[2];
+  return SF_OK;
+}
+
+}  // extern "C"
+
+// ---------------- whole-record partition function (sf_pf_long.hip.h) ----------------
+namespace {
+double g_pfl_ms[2] = {0, 0};  // inside (all attempts, with q5 / q3), outside (with the probabilities) of the last sf_pf_long
+int g_pfl_attempts = 0;
+double g_pfl_lns = 0.0;
+
+// lanes per cell of a diagonal with `cells` cells whose longest sum has `terms` terms: fill the lane budget, at most one wave,
+// and no more lanes than leave each some sixteen terms (four lanes for the interior loops of a short diagonal)
+int pfl_group(size_t cells, int terms, size_t lanes) {
+  int G = 1;
+  while (G < 64 && (size_t)(2 * G) * cells <= lanes && 32 * G <= std::max(64, terms)) G *= 2;
+  return G;
+}
+}  // namespace
+
+extern "C" {
+
+int sf_pf_long(const uint8_t *seq, int L, const char *cons, const int32_t *mfe_dcal_hint, double *ens_dG, double *mean_bp_dist,
+               char *centroid_out, double *centroid_dist) {
+  int rc = check_ready();
+  if (rc) return rc;
+  if (!seq || L < 1 || L > SF_MAX_LONG) return SF_ERR_BAD_ARG;
+  bool noncanonical = false;
+  if (cons && (rc = scan_constraints(seq, cons, 1, L, &noncanonical))) return rc;
+  const sf_params_blob *P = (const sf_params_blob *)g.slot[g.cur].src.data();  // the resident set as it was handed in
+  const Ctx::ModelSlot &M = g.slot[g.cur];  // its host copies of kT, MLbase and the hairpin initiation weight at 30
+  const double kT = M.pf_kT;
+  std::vector<uint8_t> hS((size_t)L + 2, 0);
+  for (int x = 0; x < L; x++) hS[x + 1] = sf_encode_nt(seq[x]);
+  std::vector<double> hhp((size_t)L + 1), hsc((size_t)L + 2), hml((size_t)L + 2);
+  for (int s = 0; s <= L; s++)  // (read only past the resident table, SF_MAX_W + 1: build_dev_params' extrapolation)
+    hhp[s] = (s <= 30) ? 0.0 : M.pf_hp30 * exp(-(P->lxc * log(s / 30.)) * 10. / kT);
+
+  const size_t tri = SF_LONG_TRI(L);
+  LongBufs B;
+  B.who = "sf_pf_long";
+  SfPfLong F;
+  memset(&F, 0, sizeof F);
+  F.L = L;
+  void *p;
+  double *triangles[SF_PFLONG_NTRI];
+  static const char *const tri_names[SF_PFLONG_NTRI] = {"qb", "qb transposed / A0", "qm", "qm transposed", "qm1 / w", "ob", "A1"};
+  for (int k = 0; k < SF_PFLONG_NTRI; k++) {
+    if ((rc = B.alloc(&p, tri * sizeof(double), tri_names[k]))) return rc;
+    triangles[k] = (double *)p;
+  }
+  F.qb = triangles[0]; F.qbt = triangles[1]; F.qm = triangles[2]; F.qmt = triangles[3]; F.qm1t = triangles[4];
+  F.ob = triangles[5]; F.a1 = triangles[6];
+  F.a0 = F.qbt;   // (dead after q5)
+  F.wt = F.qm1t;  // (dead after the inside pass)
+  const size_t lanes = (size_t)(g.n_cu > 0 ? g.n_cu : 1) * SF_PFLONG_LANES_PER_CU;
+  const int prob_waves = (int)std::min<size_t>((size_t)L, lanes / 64);
+  double *d_hp, *d_sc, *d_ml;
+  if ((rc = B.alloc(&p, ((size_t)L + 1) * sizeof(double), "hairpin weights"))) return rc;
+  d_hp = (double *)p;
+  if ((rc = B.alloc(&p, ((size_t)L + 2) * sizeof(double), "scale powers"))) return rc;
+  d_sc = (double *)p;
+  if ((rc = B.alloc(&p, ((size_t)L + 2) * sizeof(double), "MLbase powers"))) return rc;
+  d_ml = (double *)p;
+  F.hpx = d_hp; F.sc = d_sc; F.mlbs = d_ml;
+  if ((rc = B.alloc(&p, ((size_t)L + 2) * sizeof(double), "q5"))) return rc;
+  F.q5 = (double *)p;
+  if ((rc = B.alloc(&p, ((size_t)L + 3) * sizeof(double), "q3"))) return rc;
+  F.q3 = (double *)p;
+  if ((rc = B.alloc(&p, 2 * (size_t)prob_waves * sizeof(double), "partial sums"))) return rc;
+  F.part = (double *)p;
+  if ((rc = B.alloc(&p, 3 * sizeof(double), "results"))) return rc;
+  F.out = (double *)p;
+  if ((rc = B.alloc(&p, (size_t)L + 1, "centroid"))) return rc;
+  F.cen = (char *)p;
+  if ((rc = B.alloc(&p, (size_t)L + 2, "sequence"))) return rc;
+  F.S = (const uint8_t *)p;
+  HIPCHK(hipMemcpyAsync(p, hS.data(), (size_t)L + 2, hipMemcpyHostToDevice, g.stream));
+  HIPCHK(hipMemcpyAsync(d_hp, hhp.data(), ((size_t)L + 1) * sizeof(double), hipMemcpyHostToDevice, g.stream));
+  F.hc.c = nullptr;
+  if (cons) {
+    void *src, *hc, *part, *encl, *stack;
+    if ((rc = B.alloc(&src, (size_t)L, "constraint"))) return rc;
+    if ((rc = B.alloc(&hc, (size_t)L + 2, "constraint"))) return rc;
+    if ((rc = B.alloc(&part, ((size_t)L + 2) * sizeof(int16_t), "bracket partners"))) return rc;
+    if ((rc = B.alloc(&encl, ((size_t)L + 2) * sizeof(int16_t), "enclosing pairs"))) return rc;
+    if ((rc = B.alloc(&stack, ((size_t)L + 2) * sizeof(int16_t), "bracket stack"))) return rc;
+    HIPCHK(hipMemcpyAsync(src, cons, (size_t)L, hipMemcpyHostToDevice, g.stream));
+    SF_LAUNCH(sf_long_hc_kernel, 1, 64, 0, g.stream, (const char *)src, L, (char *)hc, (int16_t *)part, (int16_t *)encl,
+              (int16_t *)stack, (int *)g.status.p);
+    HIPCHK(hipGetLastError());
+    F.hc.c = (const char *)hc;
+    F.hc.partner = (const int16_t *)part;
+    F.hc.encl = (const int16_t *)encl;
+    if ((rc = read_status(g.stream, false))) return rc;
+  }
+  for (auto &e : B.ev) HIPCHK(hipEventCreate(&e));
+  const SfDevParams *D = (const SfDevParams *)g.dP;
+  const SfDevParamsPF *X = (const SfDevParamsPF *)g.dX;
+  const int threads = 256;
+  auto diagonal = [&](int d, int *G, int *grid) {
+    const size_t cells = (size_t)(L - d);
+    *G = pfl_group(cells, d, lanes);
+    const size_t total = std::min(cells * (size_t)*G, lanes);
+    *grid = (int)((total + threads - 1) / threads);
+  };
+
+  double lns = SF_PFLONG_LNS_DEFAULT;
+  if (mfe_dcal_hint) lns = SF_PFLONG_MFE_FACTOR * (-(double)*mfe_dcal_hint * 10.0 / kT) / L;
+  const double ln_mlbase = log(M.pf_MLbase);
+  double res[3] = {0, 0, 0};
+  std::vector<char> cen((size_t)L + 1);
+  double ms_in = 0.0, ms_out = 0.0;
+  int attempt = 0;
+  bool done = false;
+  for (; attempt < SF_PFLONG_MAX_ATTEMPTS && !done; attempt++) {
+    for (int k = 0; k <= L + 1; k++) {
+      hsc[k] = exp(-lns * k);
+      hml[k] = exp((ln_mlbase - lns) * k);
+    }
+    HIPCHK(hipMemcpyAsync(d_sc, hsc.data(), ((size_t)L + 2) * sizeof(double), hipMemcpyHostToDevice, g.stream));
+    HIPCHK(hipMemcpyAsync(d_ml, hml.data(), ((size_t)L + 2) * sizeof(double), hipMemcpyHostToDevice, g.stream));
+    HIPCHK(hipEventRecord(B.ev[0], g.stream));
+    for (int d = 0; d < L; d++) {
+      int G, grid;
+      diagonal(d, &G, &grid);
+      SF_LAUNCH(sf_pflong_inside_kernel, grid, threads, 0, g.stream, F, d, G, D, X);
+    }
+    HIPCHK(hipGetLastError());
+    SF_LAUNCH(sf_pflong_exterior_kernel, 1, 64, 0, g.stream, F, D, X);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(B.ev[1], g.stream));
+    HIPCHK(hipMemcpyAsync(res, F.out, sizeof(double), hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipStreamSynchronize(g.stream));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, B.ev[0], B.ev[1]));
+    ms_in += ms;
+    const double lz = res[0];
+    if (!isfinite(lz) || fabs(lz) > SF_PF_LNZ_MAX) {
+      // (q5[L] = +inf: log = +inf; an underflow to 0: -inf; NaN counts as an overflow)
+      lns += isfinite(lz) ? lz / L : ((lz < 0 ? -700.0 : 700.0) / L);
+      continue;
+    }
+    HIPCHK(hipMemsetAsync(F.cen, '.', (size_t)L, g.stream));
+    HIPCHK(hipMemsetAsync(F.cen + L, 0, 1, g.stream));
+    HIPCHK(hipEventRecord(B.ev[2], g.stream));
+    for (int d = L - 1; d >= SFD_TURN + 1; d--) {
+      int G, grid;
+      diagonal(d, &G, &grid);
+      SF_LAUNCH(sf_pflong_outside_kernel, grid, threads, 0, g.stream, F, d, G, D, X);
+    }
+    HIPCHK(hipGetLastError());
+    SF_LAUNCH(sf_pflong_prob_kernel, prob_waves, 64, 0, g.stream, F);
+    SF_LAUNCH(sf_pflong_finish_kernel, 1, 64, 0, g.stream, F, prob_waves);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(B.ev[3], g.stream));
+    HIPCHK(hipMemcpyAsync(res, F.out, sizeof res, hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipMemcpyAsync(cen.data(), F.cen, (size_t)L + 1, hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipStreamSynchronize(g.stream));
+    HIPCHK(hipEventElapsedTime(&ms, B.ev[2], B.ev[3]));
+    ms_out += ms;
+    if (isfinite(res[1]) && isfinite(res[2])) {
+      done = true;
+    } else {
+      if (fabs(lz) < 1.0) break;  // Z_s is centred and the outside tables still leave the range
+      lns += lz / L;
+    }
+  }
+  if ((rc = read_status(g.stream, false))) return rc;
+  g_pfl_ms[0] = ms_in;
+  g_pfl_ms[1] = ms_out;
+  g_pfl_attempts = attempt;
+  g_pfl_lns = lns;
+  if (!done) return SF_ERR_RANGE;
+  const double dG = -(res[0] + (double)L * lns) * kT / 1000.0;
+  if (!isfinite(dG)) return SF_ERR_RANGE;
+  if (ens_dG) *ens_dG = dG;
+  if (mean_bp_dist) *mean_bp_dist = res[1];
+  if (centroid_dist) *centroid_dist = res[2];
+  if (centroid_out) memcpy(centroid_out, cen.data(), (size_t)L + 1);
+  return SF_OK;
+}
+
+int sf_pf_long_times(double *inside_ms, double *outside_ms, int *attempts, double *lns) {
+  SF_ENTER();
+  if (inside_ms) *inside_ms = g_pfl_ms[0];
+  if (outside_ms) *outside_ms = g_pfl_ms[1];
+  if (attempts) *attempts = g_pfl_attempts;
+  if (lns) *lns = g_pfl_lns;
   return SF_OK;
 }
 

@@ -12,6 +12,7 @@ dinuclShuffle(s)                       SFF:255-277   identical strings under the
 simple_transcribe(seq)                 SFF:580-584
 pvalue_function(energy_list, r)        SFF:727-738
 zscore_function(energy_list, r)        SFF:741-751   statistics.stdev variant, 0.0 when sd == 0
+rna_refold(frag, T, constraint_file)   SFF:758-772   RNAfold -p -T -C: whole records through fold_long / pf_long
 rna_folder((frag, T, algo))            SFF:774-789   one batched device launch of size 1
 randomizer(frag)                       SFF:800-802
 energies(seq_list, T, algo)            SFF:805-814   ONE batched launch for the whole list
@@ -171,6 +172,36 @@ def rna_folder(arg):
         frag, temperature, algo = arg
         return energies([frag], temperature, algo)[0]
     return energies([arg])[0]
+
+
+def rna_refold(frag, temperature, constraint_file):
+    """`RNAfold -p -T temperature -C` on one sequence (ScanFoldFunctions.py:758-772) -> (structure, centroid, MFE, ED).
+    constraint_file has the layout RNAfold -C reads: the sequence line, then the constraint line (a header line starting
+    with '>' before them is skipped); `frag` is the sequence that is folded, as upstream hands it to RNAfold's input.
+    MFE in kcal/mol as ViennaRNA returns it; ED is the ensemble diversity (mean base-pair distance) rounded to 2 decimals,
+    as RNAfold prints it.  Up to SF_MAX_W nt the window entry points fold (fold_constrained); longer sequences, up to
+    SF_MAX_LONG, go through fold_long and pf_long, the latter scaled from the former's energy.
+    Unlike upstream's subprocess the call is not stateless: like rna_folder it leaves the shared engine's resident model at
+    `temperature` (Engine.set_temperature), which is what the next fold of this module sets anyway."""
+    from . import _lib
+    eng = _lib.get_engine()
+    eng.set_temperature(float(temperature))
+    seq = str(frag).strip().upper().replace("T", "U")
+    with open(constraint_file) as f:
+        lines = [ln.rstrip("\r\n") for ln in f if ln.strip() and not ln.startswith(">")]
+    if len(lines) < 2:
+        raise ValueError("%s: expected a sequence line and a constraint line" % constraint_file)
+    cons = lines[1].split()[0]
+    if len(cons) != len(seq):
+        raise ValueError("constraint string and sequence differ in length")
+    if len(seq) > _lib.SF_MAX_W:
+        e, structure = eng.fold_long(seq, cons)
+        r = eng.pf_long(seq, cons, mfe_hint=e)
+        centroid, ed = r["centroid"], r["mean_bp_dist"]
+    else:
+        r = eng.fold_constrained([seq], [cons])
+        e, structure, centroid, ed = r["mfe"][0], r["structure"][0], r["centroid"][0], float(r["mean_bp_dist"][0])
+    return structure, centroid, _dcal_to_float([e])[0], round(ed, 2)
 
 
 # ----------------------------------------------------------------------------- statistics

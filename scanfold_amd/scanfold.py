@@ -150,7 +150,7 @@ def read_reactivities(path):
     return vec
 
 
-def global_refold(seq, name, outname, temperature, dbn_file_path="AllDBN-global_refold.txt"):
+def global_refold(seq, name, outname, temperature, dbn_file_path="AllDBN-global_refold.txt", ensemble=False):
     """ScanFold.py:1509-1547 (--global_refold): a fresh RNA.md() at md.temperature = int(-t) — no --span, exactly as
     upstream — folds the whole record unconstrained and with line 3 of `<outname>.ScanFold.-1.dbn` / `.-2.dbn` as
     hc_add_from_db constraint, and writes the three records to `<outname>.<dbn_file_path>`; `<outname>.AllDBN.txt` is the
@@ -160,7 +160,10 @@ def global_refold(seq, name, outname, temperature, dbn_file_path="AllDBN-global_
     last window's end; when the windows stop short of the record's end the line is padded with '.' (no ScanFold pair
     there, so no constraint) to the record's length.
     The engine's model (base-pair span, temperature, and the RNA facade's record of the span) is put back exactly as it
-    was, also when a fold raises: the stages after this one, and the next records, fold as they would without the flag."""
+    was, also when a fold raises: the stages after this one, and the next records, fold as they would without the flag.
+    ensemble (--global_ensemble, not upstream): the partition function of the same three folds (Engine.pf_long, scaled from
+    each fold's MFE) into `<outname>.<dbn_file_path minus .txt>.ensemble.txt`, three records of a header line (ensemble free
+    energy, ED = mean base-pair distance to 2 decimals, centroid distance), the sequence and the centroid."""
     from . import RNA
     md = RNA.md()
     md.temperature = int(temperature)
@@ -182,6 +185,14 @@ def global_refold(seq, name, outname, temperature, dbn_file_path="AllDBN-global_
         fc.hc_add_from_db(cons[1])
         s2, e2 = fc.mfe()
         s0, e0 = RNA.fold_compound(seq, md).mfe()
+        ens = []
+        if ensemble:
+            for c, e in ((None, e0), (cons[0], e1), (cons[1], e2)):
+                if len(seq) > _lib.SF_MAX_W:
+                    ens.append(eng.pf_long(seq, c, mfe_hint=int(round(e * 100))))
+                else:
+                    r = eng.fold_constrained([seq], ["." * len(seq) if c is None else c], mfe=False)
+                    ens.append({k: (r[k][0] if k == "centroid" else float(r[k][0])) for k in r})
     finally:
         if eng.params is not params0:
             eng._load(params0)
@@ -195,6 +206,12 @@ def global_refold(seq, name, outname, temperature, dbn_file_path="AllDBN-global_
         w.write(">" + str(name) + "\tGlobal Full MFE=" + str(e0) + "\n" + seq + "\n" + s0 + "\n")
         w.write(">" + str(name) + "\tRefolded with -1 constraints MFE=" + str(e1) + "\n" + seq + "\n" + s1 + "\n")
         w.write(">" + str(name) + "\tRefolded with -2 constraints MFE=" + str(e2) + "\n" + seq + "\n" + s2 + "\n")
+    if ensemble:
+        stem = dbn_file_path[:-4] if dbn_file_path.endswith(".txt") else dbn_file_path
+        with open(outname + "." + stem + ".ensemble.txt", "w") as w:
+            for label, r in zip(("Global Full", "Refolded with -1 constraints", "Refolded with -2 constraints"), ens):
+                w.write(">%s\t%s ensemble dG=%.2f ED=%.2f centroid distance=%.2f\n%s\n%s\n"
+                        % (name, label, r["dG"], r["mean_bp_dist"], r["centroid_dist"], seq, r["centroid"]))
     with open(outname + ".AllDBN.txt", "w") as w:
         for tag in ("no_filter", "-1", "-2"):
             with open(outname + ".ScanFold." + tag + ".dbn") as f:
@@ -224,6 +241,8 @@ def build_parser():
     p.add_argument('--span', type=int, help='Max bp span')
     p.add_argument('--global_refold', action='store_true',
                    help='Global refold option. Refold full sequence using Zavg <-1 and <-2 base pairs')
+    p.add_argument('--global_ensemble', action='store_true',
+                   help='with --global_refold: also write ensemble free energy, ED and centroid of the three whole-record folds')
     p.add_argument('--dbn_file_path', type=str, default="AllDBN-global_refold.txt",
                    help='file name (after the output prefix) of the global refold records')
     p.add_argument('--lri', action='store_true', help='scan for long range interactions (k-mer duplexes) instead of windows')
@@ -247,6 +266,8 @@ def main(argv=None):
     if args.global_refold and (args.c == 0 or args.dont_fold):
         # upstream scans first and then fails on the dbn files those modes never write
         raise ValueError("--global_refold refolds with the -1 / -2 dbn files of the Fold stage: not with -c 0 or --dont_fold")
+    if args.global_ensemble and not args.global_refold:
+        raise ValueError("--global_ensemble adds the partition function to the folds of --global_refold: give both")
     if args.lri:
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             raise ValueError("--lri runs on one GPU: start it without a multi-process launcher")
@@ -310,7 +331,7 @@ def main(argv=None):
             writers.write_wig(table.ed.tolist(), step, args.name, outname + ".scan-ED.wig")
             if args.global_refold:
                 print("Refolding full sequence using ScanFold results as constraints...")
-                global_refold(seq, args.name, outname, args.t, args.dbn_file_path)
+                global_refold(seq, args.name, outname, args.t, args.dbn_file_path, ensemble=args.global_ensemble)
             if args.c == 1 and not args.dont_extract:
                 with open(outname + ".ScanFold.-2.dbn") as f:
                     line = f.readlines()[2]
