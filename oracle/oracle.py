@@ -113,6 +113,7 @@ def _bind_common(L):
     L.sfo_pf.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_void_p,
                          ctypes.c_char_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
     L.sfo_brute_dG.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_void_p]
+    L.sfo_pf_cubic.argtypes = L.sfo_pf.argtypes
     L.sfo_pf_unscaled.argtypes = [ctypes.c_char_p, ctypes.c_int] + [ctypes.POINTER(ctypes.c_double)] * 4
     L.sfo_set_constraint.argtypes = [ctypes.c_char_p, ctypes.c_void_p]
     return L
@@ -139,9 +140,10 @@ def set_params(paramset, L=None):
         raise RuntimeError("sfo_set_params rc=%d" % rc)
 
 
-def set_max_bp_span(span):
-    """RNA.md().max_bp_span: pairs (i, j) with j - i + 1 > span do not exist; <= 0 removes the limit."""
-    lib().sfo_set_max_bp_span(int(span or 0))
+def set_max_bp_span(span, precision="double"):
+    """RNA.md().max_bp_span: pairs (i, j) with j - i + 1 > span do not exist; <= 0 removes the limit.  Each precision's
+    library keeps its own."""
+    _lib_for(precision).sfo_set_max_bp_span(int(span or 0))
 
 
 _keep = {}
@@ -211,7 +213,7 @@ def brute(seq, want_bpp=False, precision="double"):
     return e.value, Z.value, bpp, cnt.value
 
 
-def pf(seq, want_bpp=False, precision="double"):
+def pf(seq, want_bpp=False, precision="double", _entry="sfo_pf"):
     """-> dict(dG, centroid, centroid_dist, mean_bp_dist, bpp).  precision="double": the FP64 oracle, scaled per
     nucleotide where the fold needs it; "long": the unscaled long-double reference (lib_long)."""
     n = len(seq)
@@ -220,11 +222,17 @@ def pf(seq, want_bpp=False, precision="double"):
     mbd = ctypes.c_double()
     cen = ctypes.create_string_buffer(n + 1)
     bpp = np.zeros((n + 1, n + 1)) if want_bpp else None
-    rc = _lib_for(precision).sfo_pf(seq.encode(), n, ctypes.byref(dG), bpp.ctypes.data if want_bpp else None, cen,
-                      ctypes.byref(cd), ctypes.byref(mbd))
+    rc = getattr(_lib_for(precision), _entry)(seq.encode(), n, ctypes.byref(dG), bpp.ctypes.data if want_bpp else None, cen,
+                                              ctypes.byref(cd), ctypes.byref(mbd))
     if rc:
-        raise RuntimeError("sfo_pf rc=%d" % rc)
+        raise RuntimeError("%s rc=%d" % (_entry, rc))
     return dict(dG=dG.value, centroid=cen.value.decode(), centroid_dist=cd.value, mean_bp_dist=mbd.value, bpp=bpp)
+
+
+def pf_cubic(seq, want_bpp=False, precision="double"):
+    """pf with the O(n^3) outside pass (sfo_pf_cubic: outside tables for qm and qm1, OpenMP over each diagonal): the same
+    contract, for whole records past the few hundred nt that pf's O(n^4) pass can answer."""
+    return pf(seq, want_bpp, precision, _entry="sfo_pf_cubic")
 
 
 def pf_unscaled(seq, precision="double"):

@@ -920,11 +920,15 @@ int sfo_brute_dG(const char *seq, int n, double *ensemble_dG, double *bpp) {
 
 /* =================================== partition function =================================== */
 /* Inside: qb, qm, qm1 (unambiguous McCaskill decomposition, dangles=2), q5/q3 exterior.
- * Outside: direct O(n^4) summation over enclosing pairs (an oracle, not a fast path).
+ * Outside: direct O(n^4) summation over enclosing pairs (an oracle, not a fast path); cubic != 0 runs pf_outside_cubic,
+ * the O(n^3) rule-by-rule inverse of the inside grammar, in its place (and the inside pass's diagonals under OpenMP).
  * Scaled by s = e^lns per nucleotide: every weight that covers k nucleotides not yet covered by the tables it
  * multiplies carries sc[k] = s^-k, so each table entry holds its weight times s^-(nucleotides it spans) and
  * Z_s = Z s^-n.  lns = 0 multiplies by exactly 1.  Returns ln Z_s. */
-static double pf_run(const seq_t *qs, sf_real lns, double *ensemble_dG, double *bpp_out, char *centroid,
+static void pf_outside_cubic(const seq_t *qs, const sf_real *qb, const sf_real *qm, const sf_real *qm1, const sf_real *q5,
+                             const sf_real *q3, const sf_real *mlb, const sf_real *sc, sf_real *ob);
+
+static double pf_run(const seq_t *qs, sf_real lns, int cubic, double *ensemble_dG, double *bpp_out, char *centroid,
                      double *centroid_dist, double *mean_bp_dist) {
   const seq_t q = *qs;
   const int n = q.n;
@@ -943,7 +947,12 @@ static double pf_run(const seq_t *qs, sf_real lns, double *ensemble_dG, double *
   for (int k = 1; k <= n + 1; k++) mlb[k] = mlb[k - 1] * XP->MLbase * sc[1];
 
   for (int d = TURN + 1; d < n; d++) {
-    for (int i = 1; i + d <= n; i++) {
+    /* The cells of a diagonal are independent, which is what makes the loop safe under OpenMP: a cell reads narrower
+     * diagonals and, on its own diagonal, only itself -- qm1[i][j] reads the qb[i][j] and qm[i][j] the qm1[i][j] (the term
+     * u = i) that the same iteration wrote just before.  One thread sums a whole cell, in the serial order, so the tables
+     * are those of the serial pass bit for bit. */
+#pragma omp parallel for schedule(dynamic, 16) if (cubic && n > 200)
+    for (int i = 1; i <= n - d; i++) {
       int j = i + d;
       int type = ptype(&q, i, j);
       if (type) {
@@ -1003,7 +1012,8 @@ static double pf_run(const seq_t *qs, sf_real lns, double *ensemble_dG, double *
   if (ensemble_dG) *ensemble_dG = (double)(-(SF_LOG(Z) + lns * n) * XP->kT / 1000);
 
   /* outside of pairs, widest first */
-  for (int d = n - 1; d >= TURN + 1; d--) {
+  if (cubic) pf_outside_cubic(&q, qb, qm, qm1, q5, q3, mlb, sc, ob);
+  else for (int d = n - 1; d >= TURN + 1; d--) {
     for (int i = 1; i + d <= n; i++) {
       int j = i + d;
       int type = ptype(&q, i, j);
@@ -1062,20 +1072,101 @@ static double pf_run(const seq_t *qs, sf_real lns, double *ensemble_dG, double *
 
 /* A fold whose ln Z passes SF_PF_LNZ_MAX (or is not finite) is redone scaled: by its own ln Z_s / n where that is finite,
  * which brings ln Z_s to ~0, else by 700 / n more, which lowers ln Z_s (> 709 before) by exactly 700. */
-int sfo_pf(const char *seq, int n, double *ensemble_dG, double *bpp_out, char *centroid, double *centroid_dist,
-           double *mean_bp_dist) {
+static int pf_rescaled(const char *seq, int n, int cubic, double *ensemble_dG, double *bpp_out, char *centroid,
+                       double *centroid_dist, double *mean_bp_dist) {
   if (!have_params) return -10;
   seq_t q;
   seq_init(&q, seq, n);
   if (q.cons_bad) { seq_free(&q); return -3; }
   sf_real lns = 0;
   for (int attempt = 0; attempt < 40; attempt++) {
-    const double lz = pf_run(&q, lns, ensemble_dG, bpp_out, centroid, centroid_dist, mean_bp_dist);
+    const double lz = pf_run(&q, lns, cubic, ensemble_dG, bpp_out, centroid, centroid_dist, mean_bp_dist);
     if (!SF_PF_RESCALE || lz <= SF_PF_LNZ_MAX) break;
     lns += (isfinite(lz) ? lz : 700.0) / n;
   }
   seq_free(&q);
   return 0;
+}
+int sfo_pf(const char *seq, int n, double *ensemble_dG, double *bpp_out, char *centroid, double *centroid_dist,
+           double *mean_bp_dist) {
+  return pf_rescaled(seq, n, 0, ensemble_dG, bpp_out, centroid, centroid_dist, mean_bp_dist);
+}
+
+/* The outside pass in O(n^3): every rule of the inside grammar read backwards, with outside tables for qm (oqm) and qm1
+ * (oqm1) next to ob.  X-hat[i][j] is the summed weight of everything around the segment i..j in structures that use the
+ * table entry X[i][j], so that p(i,j) = ob[i][j] qb[i][j] / Z.  The inside rules and what each gives back:
+ *   qb[k][l]  += C(k,l) qm[k+1][u-1] qm1[u][l-1]       oqm[k+1][u-1] += ob[k][l] C(k,l) qm1[u][l-1]
+ *                                                      oqm1[u][l-1]  += ob[k][l] C(k,l) qm[k+1][u-1]
+ *   qm[i][l]  += (mlb[u-i] + qm[i][u-1]) qm1[u][l]     oqm[i][u-1]   += oqm[i][l] qm1[u][l]
+ *                                                      oqm1[u][l]    += oqm[i][l] (mlb[u-i] + qm[i][u-1])
+ *   qm1[i][l] += qb[i][j] stem(i,j) mlb[l-j]           ob[i][j]      += oqm1[i][l] stem(i,j) mlb[l-j]
+ * with C(k,l) = MLclosing * mlstem of the closing pair seen from inside * sc[2]; the exterior and interior-loop terms of
+ * ob are those of the O(n^4) pass.  Each is written as a gather into the cell (i,j): oqm[i][j] first, then oqm1[i][j],
+ * which reads it, then ob[i][j], which reads oqm1[i][j]; every other term comes from a wider diagonal, so the cells of a
+ * diagonal are independent.  The scale factors need no care of their own: the rules are linear in every table.
+ * obc = ob * C and the transposes obcT, oqmT, qmT exist only so that the sums over a column read memory in order. */
+static void pf_outside_cubic(const seq_t *qs, const sf_real *qb, const sf_real *qm, const sf_real *qm1, const sf_real *q5,
+                             const sf_real *q3, const sf_real *mlb, const sf_real *sc, sf_real *ob) {
+  const seq_t q = *qs;
+  const int n = q.n;
+  const int *S = q.S;
+  const size_t sz = (size_t)(n + 2) * (size_t)(n + 2);
+  sf_real *oqm = (sf_real *)calloc(sz, sizeof(sf_real));
+  sf_real *oqm1 = (sf_real *)calloc(sz, sizeof(sf_real));
+  sf_real *obc = (sf_real *)calloc(sz, sizeof(sf_real));
+  sf_real *obcT = (sf_real *)calloc(sz, sizeof(sf_real));
+  sf_real *oqmT = (sf_real *)calloc(sz, sizeof(sf_real));
+  sf_real *qmT = (sf_real *)calloc(sz, sizeof(sf_real));
+  for (int i = 1; i <= n; i++)
+    for (int j = i; j <= n; j++) qmT[IX(j, i)] = qm[IX(i, j)];
+
+  for (int d = n - 1; d >= TURN + 1; d--) {
+#pragma omp parallel for schedule(dynamic, 16) if (n > 200)
+    for (int i = 1; i <= n - d; i++) {
+      const int j = i + d;
+      /* oqm[i][j]: qm[i][j] left of the last branch qm1[j+1][l-1] of a multiloop closed by (i-1,l), or left of the last
+       * branch qm1[j+1][l] of qm[i][l] */
+      sf_real a = 0;
+      if (i >= 2)
+        for (int l = j + 2; l <= n; l++) a += obc[IX(i - 1, l)] * qm1[IX(j + 1, l - 1)];
+      for (int l = j + 1; l <= n; l++) a += oqm[IX(i, l)] * qm1[IX(j + 1, l)];
+      oqm[IX(i, j)] = oqmT[IX(j, i)] = a;
+      /* oqm1[i][j]: the last branch of a multiloop closed by (k,j+1) right of qm[k+1][i-1], or the last branch of qm[k][j]
+       * right of unpaired bases or of qm[k][i-1] */
+      sf_real b = 0;
+      if (j < n)
+        for (int k = 1; k <= i - 2; k++) b += obcT[IX(j + 1, k)] * qmT[IX(i - 1, k + 1)];
+      for (int k = 1; k < i; k++) b += oqmT[IX(j, k)] * (mlb[i - k] + qmT[IX(i - 1, k)]);
+      b += a; /* k = i: mlb[0] = 1 and nothing left of the branch */
+      oqm1[IX(i, j)] = b;
+
+      const int type = ptype(&q, i, j);
+      if (!type || qb[IX(i, j)] == 0) continue;
+      sf_real o = q5[i - 1] * q3[j + 1] * X_extloop(type, ml_nb5(&q, i), ml_nb3(&q, j));
+      for (int k = MAX2(1, i - MAXLOOP - 1); k < i; k++) {
+        const int u1 = i - k - 1;
+        for (int l = j + 1; l <= n && (l - j - 1) + u1 <= MAXLOOP; l++) {
+          const int tk = ptype(&q, k, l);
+          if (!tk || ob[IX(k, l)] == 0) continue;
+          o += ob[IX(k, l)] *
+               X_intloop(u1, l - j - 1, tk, rtype[type], S[k + 1], S[l - 1], S[i - 1], S[j + 1]) * sc[(i - k) + (l - j)];
+        }
+      }
+      /* (i,j) as the stem of qm1[i][l] */
+      sf_real m = 0;
+      for (int l = j; l <= n; l++) m += oqm1[IX(i, l)] * mlb[l - j];
+      o += m * X_mlstem(type, ml_nb5(&q, i), ml_nb3(&q, j));
+      ob[IX(i, j)] = o;
+      obc[IX(i, j)] = obcT[IX(j, i)] = o * XP->MLclosing * X_mlstem(rtype[type], S[j - 1], S[i + 1]) * sc[2];
+    }
+  }
+  free(oqm); free(oqm1); free(obc); free(obcT); free(oqmT); free(qmT);
+}
+
+/* sfo_pf with the O(n^3) outside pass: the reference for whole records, where sfo_pf's O(n^4) pass takes too long */
+int sfo_pf_cubic(const char *seq, int n, double *ensemble_dG, double *bpp_out, char *centroid, double *centroid_dist,
+                 double *mean_bp_dist) {
+  return pf_rescaled(seq, n, 1, ensemble_dG, bpp_out, centroid, centroid_dist, mean_bp_dist);
 }
 
 /* the scale-free FP64 fold (lns = 0) with its ln Z, for the tests that show where it leaves the range */
@@ -1085,7 +1176,7 @@ int sfo_pf_unscaled(const char *seq, int n, double *ensemble_dG, double *centroi
   seq_t q;
   seq_init(&q, seq, n);
   if (q.cons_bad) { seq_free(&q); return -3; }
-  const double lz = pf_run(&q, 0, ensemble_dG, NULL, NULL, centroid_dist, mean_bp_dist);
+  const double lz = pf_run(&q, 0, 0, ensemble_dG, NULL, NULL, centroid_dist, mean_bp_dist);
   if (ln_z) *ln_z = lz;
   seq_free(&q);
   return 0;

@@ -5,14 +5,18 @@ The bar is the project's PF_TOL made relative: |got - ref| <= PF_TOL * max(1, |r
 (a 3-kb record's dG is in the thousands; FP64 carries 16 digits whatever the magnitude), and equal centroids except at
 pairs whose oracle probability lies within 1e-9 of the 0.5 threshold, at most MAX_EXCUSED positions of them.
 
-The oracle's outside pass is O(n^4), so records past ~520 nt are built from blocks it can still answer: under
+The outside pass of oracle.pf is O(n^4).  Whole records past ~520 nt without a span are checked against oracle.pf_cubic in
+long double (cubic_reference), whose O(n^3) outside pass tests/test_pf_cubic.py proves against oracle.pf; nested_record
+builds inputs whose long diagonals carry weight.  Longer records are built from blocks oracle.pf can still answer: under
 max_bp_span = S, blocks joined by runs of S N fold independently (long_util.separated_record shows it for the MFE), so Z is
 the product of the blocks' Z — dG, mean_bp_dist and centroid_dist are the sums of the blocks' — and the centroid is the
 blocks' centroids joined by dots.  Each block is folded with one flanking N on each inner side, which a stem's exterior
 term reads."""
 import numpy as np
+import pytest
 
-from long_util import rand_seq
+from scanfold_amd import params
+from long_util import COMP, hairpin_rich, pair_table, rand_seq
 from test_gpu_parity import PF_TOL
 
 MAX_EXCUSED = 2
@@ -76,3 +80,67 @@ def block_record(oracle, block_lens, S, seed, fill):
 def gc_only(L=480):
     """the G/C-only sequence whose unscaled partition function leaves FP64's range (ln Z ~ 742)"""
     return rand_seq(np.random.default_rng(2), L, "GC")
+
+
+def nested_record(rng, L):
+    """-> (seq, outer, branches): a record of exactly L nt whose top diagonals are live.  A G/C stem of 12 pairs joins its two
+    ends and closes a multiloop of three branches, each a hairpin_rich stretch of about L/3 closed by a G/C stem of 10 pairs,
+    with two A between the stems.  outer and branches[k] list the planted pairs (0-based, outermost first)."""
+    def helix(n):
+        a = rand_seq(rng, n, "GC")
+        return a, a[::-1].translate(COMP)
+    room = L - 2 * 12 - 4 * 2 - 3 * 2 * 10
+    lens = [room // 3, room // 3, room - 2 * (room // 3)]
+    o5, o3 = helix(12)
+    seq, branches = o5, []
+    for m in lens:
+        b5, b3 = helix(10)
+        start = len(seq) + 2
+        seq += "AA" + b5 + hairpin_rich(rng, m) + b3
+        branches.append([(start + k, len(seq) - 1 - k) for k in range(10)])
+    seq += "AA" + o3
+    assert len(seq) == L
+    return seq, [(k, L - 1 - k) for k in range(12)], branches
+
+
+_cubic = {}
+
+
+@pytest.fixture(scope="module", autouse=True)
+def forget_cubic_references():
+    """A module that imports this fixture drops its references when its last test has run: each keeps a whole bpp matrix
+    (36 MB at 2 112 nt), which no later module reads."""
+    yield
+    _cubic.clear()
+
+
+def cubic_reference(oracle, seq, paramset, cons=None, span=0):
+    """oracle.pf_cubic(seq, want_bpp=True, precision="long") under paramset, constraint and span, computed once per module run:
+    dict(dG, mean_bp_dist, centroid_dist, centroid, bpp).  The long-double library keeps its own tables, span and constraint;
+    they are set for the call, and the default set, no constraint and no span are put back."""
+    key = (seq, paramset.blob(), cons, span)
+    if key not in _cubic:
+        oracle.set_params(paramset, L=oracle.lib_long())
+        oracle.set_constraint(cons, precision="long")
+        oracle.set_max_bp_span(span, precision="long")
+        try:
+            _cubic[key] = oracle.pf_cubic(seq, want_bpp=True, precision="long")
+        finally:
+            oracle.set_constraint(None, precision="long")
+            oracle.set_max_bp_span(0, precision="long")
+            oracle.set_params(params.default_params(), L=oracle.lib_long())
+    return _cubic[key]
+
+
+def assert_carries_weight(ref, outer, branches, L):
+    """The reference of a nested_record must itself depend on the long diagonals: the outermost planted pair is likelier than
+    not, the centroid holds a pair spanning all but 40 nt and a planted pair of every branch, and no probability lies within
+    1e-6 of the centroid's threshold, so that assert_close has nothing to excuse."""
+    bpp, pt = ref["bpp"], pair_table(ref["centroid"])
+    assert bpp[outer[0][0] + 1, outer[0][1] + 1] > 0.5, bpp[outer[0][0] + 1, outer[0][1] + 1]
+    assert any(j - i >= L - 40 for i, j in pt.items())
+    for b, pairs in enumerate(branches):
+        assert any(pt.get(i) == j for i, j in pairs), b
+    gap = float(np.abs(bpp - 0.5).min())
+    print("closest probability to 0.5: |p - 0.5| = %.3g" % gap)
+    assert gap > 1e-6, gap

@@ -15,7 +15,8 @@ from scanfold_amd import RNA
 from scanfold_amd import functions as sff
 from scanfold_amd import scanfold as sfd
 import pf_util
-from long_pf_util import KEYS, assert_close, block_record, gc_only, oracle_pf
+from long_pf_util import (KEYS, assert_carries_weight, assert_close, block_record, cubic_reference, forget_cubic_references,
+                          gc_only, nested_record, oracle_pf)  # (forget_cubic_references: an autouse fixture)
 from long_util import hairpin_rich, rand_seq
 from test_long_fold import constraint_string, params_in, planted_stem
 
@@ -243,3 +244,12 @@ def test_bad_arguments(emul):
     assert lib.sf_pf_long(s, 40, None, None, None, None, None, None) == 0  # every output is optional
     assert lib.sf_pf_long(s, 40, None, None, *a) == 0 and all(np.isfinite(v) for v in out) and len(buf.value) == 40
     assert set(KEYS) | {"centroid"} == set(emul.pf_long("ACGU" * 10))
+
+
+def test_unspanned_nested_record(emul, oracle):
+    """600 nt without a span, against oracle.pf_cubic in long double: under the emulation's lane budget a group walks several
+    cells per launch, here with live data on the long diagonals (the block records above leave them dead)."""
+    seq, outer, branches = nested_record(np.random.default_rng(2), 600)
+    ref = cubic_reference(oracle, seq, params.default_params())
+    assert_carries_weight(ref, outer, branches, 600)
+    assert_close(emul.pf_long(seq), ref, "nested 600", ref["bpp"])
