@@ -7,7 +7,9 @@
  * symbol, and the twin has no long fold.  Bind these symbols only where the loaded library exports them.
  *
  * sf_fold_long gives the MFE and its structure, sf_pf_long the partition function (ensemble free energy, centroid, ensemble
- * diversity) of the same whole record.  Soft constraints (SHAPE) are not provided past SF_MAX_W.
+ * diversity) of the same whole record; sf_fold_long_batch is sf_fold_long for many sequences of any lengths side by side
+ * (a record and its shuffles: the z-score of a sequence past SF_MAX_W).  Soft constraints (SHAPE) are not provided past
+ * SF_MAX_W.
  */
 #ifndef SCANFOLD_HIP_LONG_H
 #define SCANFOLD_HIP_LONG_H
@@ -33,6 +35,28 @@ int sf_fold_long(const uint8_t *seq, int L, const char *cons, int32_t *mfe_dcal_
 /* Device-event times (ms) of the phases of the last successful sf_fold_long: the fill of c / fML (one launch per
  * diagonal), the exterior loop f5, and the traceback (0 when it was not asked for).  Any pointer may be NULL. */
 int sf_fold_long_times(double *fill_ms, double *f5_ms, double *trace_ms);
+
+/* sf_fold_long for n sequences at once.  Row s of seqs (n rows of ld bytes) holds len[s] bytes, 1 <= len[s] <= SF_MAX_LONG
+ * and <= ld; the rows may differ in length freely.  cons: NULL, or n rows of ld characters with the meaning of
+ * sf_fold_constrained, row s holding len[s] of them; a row of '.' only is no constraint.  mfe_dcal_out: n energies.
+ * db_out: n rows of ld + 1 bytes (row s: len[s] characters and a NUL), or NULL: energies only, no traceback and no memory
+ * for it.  The resident parameter set and base-pair span apply.  Energies and structures are those of sf_fold_long, byte
+ * for byte, whatever the order of the rows and however the call is chunked.
+ * One fill launch per anti-diagonal covers every sequence of a chunk; a chunk holds as many consecutive rows as fit the
+ * byte budget (each row counted as 12 * L (L+1) / 2 + 80 L bytes; always at least one row), and its tables are a few device
+ * allocations made for the chunk and freed after it.  The budget is 8 GiB unless sf_set_long_batch_bytes changed it.
+ * n == 0: SF_OK.  n < 0, a length < 1, > SF_MAX_LONG or > ld, seqs / len / mfe_dcal_out NULL with n > 0: SF_ERR_BAD_ARG.
+ * Unbalanced brackets in any row: SF_ERR_CONSTRAINT.  Not enough device memory: SF_ERR_HIP with the text in
+ * sf_last_hip_error().  On any error no output is written. */
+int sf_fold_long_batch(const uint8_t *seqs, int n, int ld, const int32_t *len, const char *cons, int32_t *mfe_dcal_out,
+                       char *db_out);
+
+/* Device-event times (ms) of the last successful sf_fold_long_batch, summed over its chunks: fill, f5, traceback (0 when it
+ * was not asked for), and the number of chunks it ran as.  Any pointer may be NULL. */
+int sf_fold_long_batch_times(double *fill_ms, double *f5_ms, double *trace_ms, int *chunks);
+
+/* The byte budget of one chunk of sf_fold_long_batch; 0 restores the default (8 GiB). */
+int sf_set_long_batch_bytes(size_t bytes);
 
 /* fc.pf(); fc.centroid(); fc.mean_bp_distance() — RNAfold -p — for one sequence of any length 1..SF_MAX_LONG
  * (ScanFoldFunctions.py:758-772, rna_refold).  seq, cons as for sf_fold_long; the resident parameter set (rescaled

@@ -78,6 +78,10 @@ def _header_define(header, name):
 _LONG_EXPORTS = {
     "sf_fold_long": (ctypes.c_int, [_c_u8p, ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_void_p]),
     "sf_fold_long_times": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double)] * 3),
+    "sf_fold_long_batch": (ctypes.c_int, [_c_u8p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p]),
+    "sf_fold_long_batch_times": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double)] * 3 + [ctypes.POINTER(ctypes.c_int)]),
+    "sf_set_long_batch_bytes": (ctypes.c_int, [ctypes.c_size_t]),
     "sf_pf_long": (ctypes.c_int, [_c_u8p, ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                   ctypes.c_void_p, ctypes.c_void_p]),
     "sf_pf_long_times": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
@@ -323,6 +327,62 @@ class Engine:
         t = [ctypes.c_double() for _ in range(3)]
         self._check(self.lib.sf_fold_long_times(*(ctypes.byref(x) for x in t)))
         return tuple(x.value for x in t)
+
+    def has_fold_long_batch(self):
+        return getattr(self.lib, "sf_fold_long_batch", None) is not None
+
+    def _need_fold_long_batch(self):
+        if not self.has_fold_long_batch():
+            raise ScanFoldHipError("this library (%s) has no sf_fold_long_batch: folds of sequences past %d nt need "
+                                   "libscanfold_hip.so" % (getattr(self.lib, "_name", "?"), SF_MAX_W))
+
+    def fold_long_batch(self, seqs, cons=None, structure=False):
+        """fold_long for many sequences of 1..SF_MAX_LONG nt, of any mix of lengths, side by side in the same launches
+        (sf_fold_long_batch) -> int32 array of energies (dcal/mol), or (energies, [dot-bracket]) with structure=True.
+        cons: None, or one item per sequence, each a constraint string of the sequence's length or None.  Raises
+        ScanFoldHipError on a library without the entry point (there is no fallback)."""
+        self._need_fold_long_batch()
+        rows = [s if isinstance(s, (bytes, bytearray)) else str(s).encode("ascii") for s in seqs]
+        n = len(rows)
+        ld = max([1] + [len(s) for s in rows])
+        arr = np.zeros((n, ld), dtype=np.uint8)
+        for k, s in enumerate(rows):
+            arr[k, :len(s)] = np.frombuffer(bytes(s), dtype=np.uint8)
+        lens = np.array([len(s) for s in rows], dtype=np.int32)
+        c = None
+        if cons is not None:
+            cons = list(cons)
+            if len(cons) != n:
+                raise ValueError("one constraint item (a string or None) per sequence")
+            if any(x is not None for x in cons):
+                c = np.full((n, ld), ord("."), dtype=np.uint8)
+                for k, x in enumerate(cons):
+                    if x is None:
+                        continue
+                    x = x if isinstance(x, (bytes, bytearray)) else str(x).encode("ascii")
+                    if len(x) != len(rows[k]):
+                        raise ValueError("constraint string and sequence differ in length")
+                    c[k, :len(x)] = np.frombuffer(bytes(x), dtype=np.uint8)
+        e = np.zeros(n, dtype=np.int32)
+        db = np.zeros((n, ld + 1), dtype=np.uint8) if structure else None
+        self._check(self.lib.sf_fold_long_batch(arr.ctypes.data, n, ld, lens.ctypes.data, None if c is None else c.ctypes.data,
+                                                e.ctypes.data, None if db is None else db.ctypes.data))
+        if not structure:
+            return e
+        return e, [bytes(db[k, :lens[k]]).decode() for k in range(n)]
+
+    def fold_long_batch_times(self):
+        """-> dict(fill_ms, f5_ms, trace_ms, chunks) of the last fold_long_batch (device events, summed over its chunks)."""
+        self._need_fold_long_batch()
+        t = [ctypes.c_double() for _ in range(3)]
+        ch = ctypes.c_int()
+        self._check(self.lib.sf_fold_long_batch_times(*(ctypes.byref(x) for x in t), ctypes.byref(ch)))
+        return dict(fill_ms=t[0].value, f5_ms=t[1].value, trace_ms=t[2].value, chunks=ch.value)
+
+    def set_long_batch_bytes(self, nbytes):
+        """the device memory one chunk of fold_long_batch may take for its tables; 0 restores the default (8 GiB)"""
+        self._need_fold_long_batch()
+        self._check(self.lib.sf_set_long_batch_bytes(int(nbytes)))
 
     def has_pf_long(self):
         return getattr(self.lib, "sf_pf_long", None) is not None

@@ -20,6 +20,7 @@
 #include "sf_mfe_full.hip.h"
 #include "sf_mfe_fast.hip.h"
 #include "sf_mfe_long.hip.h"
+#include "sf_mfe_long_batch.hip.h"
 #include "sf_pf.hip.h"
 #include "sf_pf_long.hip.h"
 #include "sf_pf_fast.hip.h"
@@ -1200,6 +1201,234 @@ int sf_fold_long_times(double *fill_ms, double *f5_ms, double *trace_ms) {
   if (fill_ms) *fill_ms = g_long_ms[0];
   if (f5_ms) *f5_ms = g_long_ms[1];
   if (trace_ms) *trace_ms = g_long_ms[2];
+  return SF_OK;
+}
+
+}  // extern "C"
+
+// ---------------- many whole-record folds at once (sf_mfe_long_batch.hip.h) ----------------
+namespace {
+const size_t kLongBatchBytesDefault = (size_t)8 << 30;  // device memory one chunk's tables may take
+const int kLongBatchMaxSeqs = 1 << 15;                  // sequences per chunk: keeps every grid far inside an int
+size_t g_longb_bytes = kLongBatchBytesDefault;
+double g_longb_ms[3] = {0, 0, 0};  // fill, f5, traceback of the last sf_fold_long_batch, summed over its chunks
+int g_longb_chunks = 0;
+
+size_t long_batch_seq_bytes(int L) { return 12 * SF_LONG_TRI(L) + 80 * (size_t)L; }
+
+// Sequences s0 .. s0 + n - 1 of the batch as one chunk.  e_host / db_host: the caller's staging buffers (the chunk's energies
+// at e_host[s0 ..], its structures back to back, L + 1 bytes each, from db_host[db_off]); they hold the results once the
+// stream has drained, which read_status below waits for.
+int long_batch_chunk(const uint8_t *seqs, int ld, const int32_t *len, const char *cons, const std::vector<char> &constrained,
+                     int s0, int n, int32_t *e_host, char *db_host, double ms_out[3]) {
+  int rc;
+  const sf_params_blob *P = (const sf_params_blob *)g.slot[g.cur].src.data();  // the resident set as it was handed in
+  int Lmax = 0, n_hc = 0;
+  size_t tri = 0, n_L = 0, n_hcL = 0, n_stk = 0;
+  for (int k = 0; k < n; k++) {
+    const int L = len[s0 + k];
+    Lmax = std::max(Lmax, L);
+    tri += SF_LONG_TRI(L);
+    n_L += (size_t)L;
+    n_stk += SF_LONG_STACK_INTS(L);
+    if (constrained[s0 + k]) { n_hc++; n_hcL += (size_t)L; }
+  }
+  const bool trace = db_host != nullptr;
+  // slices of the int32 / int16 / byte allocations, in elements
+  const size_t o_hp = 0, o_mfe = o_hp + (size_t)Lmax + 1, o_f5 = o_mfe + (size_t)n, o_stk = o_f5 + n_L + (size_t)n;
+  const size_t n_i32 = o_stk + (trace ? n_stk : 0);
+  const size_t n_i16 = 3 * (n_hcL + 2 * (size_t)n_hc);                     // partner, encl, stack: L + 2 each
+  const size_t o_S = 0, o_src = o_S + n_L + 2 * (size_t)n, o_hc = o_src + n_hcL, o_db = o_hc + n_hcL + 2 * (size_t)n_hc;
+  const size_t n_u8 = o_db + (trace ? n_L + (size_t)n : 0);
+
+  std::vector<uint8_t> h8(o_hc, 0);  // sequences (codes, zero on both sides) and constraint rows, copied up in one piece
+  std::vector<int32_t> hhp((size_t)Lmax + 1);
+  for (int s = 0; s <= Lmax; s++) hhp[s] = (s <= 30) ? P->hairpin[s] : P->hairpin[30] + (int)(P->lxc * log(s / 30.));
+  std::vector<SfLong> hF((size_t)n);
+
+  LongBufs B;
+  B.who = "sf_fold_long_batch";
+  void *p;
+  int32_t *d_c, *d_fML, *d_fMLt, *d_dml, *d_i32;
+  int16_t *d_i16 = nullptr;
+  uint8_t *d_u8;
+  SfLong *d_F;
+  if ((rc = B.alloc(&p, tri * sizeof(int32_t), "c"))) return rc;
+  d_c = (int32_t *)p;
+  if ((rc = B.alloc(&p, tri * sizeof(int32_t), "fML"))) return rc;
+  d_fML = (int32_t *)p;
+  if ((rc = B.alloc(&p, tri * sizeof(int32_t), "fML transposed"))) return rc;
+  d_fMLt = (int32_t *)p;
+  if ((rc = B.alloc(&p, 3 * (n_L + 2 * (size_t)n) * sizeof(int32_t), "DML rings"))) return rc;
+  d_dml = (int32_t *)p;
+  if ((rc = B.alloc(&p, n_i32 * sizeof(int32_t), "hairpin table, energies, f5, traceback stacks"))) return rc;
+  d_i32 = (int32_t *)p;
+  if (n_i16) {
+    if ((rc = B.alloc(&p, n_i16 * sizeof(int16_t), "bracket partners"))) return rc;
+    d_i16 = (int16_t *)p;
+  }
+  if ((rc = B.alloc(&p, n_u8, "sequences, constraints, structures"))) return rc;
+  d_u8 = (uint8_t *)p;
+  if ((rc = B.alloc(&p, (size_t)n * sizeof(SfLong), "fold states"))) return rc;
+  d_F = (SfLong *)p;
+
+  size_t a_tri = 0, a_L = 0, a_hcL = 0, a_stk = 0;
+  int a_hc = 0;
+  for (int k = 0; k < n; k++) {
+    const int L = len[s0 + k];
+    const uint8_t *row = seqs + (size_t)(s0 + k) * ld;
+    uint8_t *hS = h8.data() + o_S + a_L + 2 * (size_t)k;
+    for (int x = 0; x < L; x++) hS[x + 1] = sf_encode_nt(row[x]);
+    SfLong &F = hF[k];
+    memset(&F, 0, sizeof F);
+    F.L = L;
+    F.S = d_u8 + o_S + a_L + 2 * (size_t)k;
+    F.hp = d_i32 + o_hp;
+    F.c = d_c + a_tri;
+    F.fML = d_fML + a_tri;
+    F.fMLt = d_fMLt + a_tri;
+    F.dml = d_dml + 3 * (a_L + 2 * (size_t)k);
+    F.f5 = d_i32 + o_f5 + a_L + (size_t)k;
+    F.status = (int *)g.status.p;
+    if (trace) {
+      F.stk = d_i32 + o_stk + a_stk;
+      F.db = (char *)d_u8 + o_db + a_L + (size_t)k;
+    }
+    if (constrained[s0 + k]) {
+      memcpy(h8.data() + o_src + a_hcL, cons + (size_t)(s0 + k) * ld, (size_t)L);
+      const size_t o16 = 3 * (a_hcL + 2 * (size_t)a_hc);
+      F.hc.c = (const char *)d_u8 + o_hc + a_hcL + 2 * (size_t)a_hc;
+      F.hc.partner = d_i16 + o16;
+      F.hc.encl = d_i16 + o16 + (size_t)L + 2;
+      a_hcL += (size_t)L;
+      a_hc++;
+    }
+    a_tri += SF_LONG_TRI(L);
+    a_L += (size_t)L;
+    a_stk += SF_LONG_STACK_INTS(L);
+  }
+  HIPCHK(hipMemcpyAsync(d_u8, h8.data(), h8.size(), hipMemcpyHostToDevice, g.stream));
+  HIPCHK(hipMemcpyAsync(d_i32 + o_hp, hhp.data(), hhp.size() * sizeof(int32_t), hipMemcpyHostToDevice, g.stream));
+  HIPCHK(hipMemcpyAsync(d_F, hF.data(), (size_t)n * sizeof(SfLong), hipMemcpyHostToDevice, g.stream));
+  a_hcL = 0;
+  for (int k = 0; k < n; k++) {  // the bracket partners and enclosing pairs of every constrained row
+    if (!constrained[s0 + k]) continue;
+    const SfLong &F = hF[k];
+    SF_LAUNCH(sf_long_hc_kernel, 1, 64, 0, g.stream, (const char *)d_u8 + o_src + a_hcL, F.L, (char *)F.hc.c,
+              (int16_t *)F.hc.partner, (int16_t *)F.hc.encl, (int16_t *)F.hc.encl + (size_t)F.L + 2, (int *)g.status.p);
+    a_hcL += (size_t)F.L;
+  }
+  HIPCHK(hipGetLastError());
+
+  for (auto &e : B.ev) HIPCHK(hipEventCreate(&e));
+  const SfDevParams *D = (const SfDevParams *)g.dP;
+  const int threads = SF_LONGB_THREADS;
+  const size_t budget = (size_t)(g.n_cu > 0 ? g.n_cu : 1) * SF_LONGB_LANES_PER_CU;
+  HIPCHK(hipEventRecord(B.ev[0], g.stream));
+  for (int d = 0; d < Lmax; d++) {
+    int G = long_group(d);
+    while (G > 1 && (size_t)n * (size_t)(Lmax - d) * (size_t)G > budget) G >>= 1;
+    const int bps = (int)(((size_t)(Lmax - d) * (size_t)G + threads - 1) / threads);
+    SF_LAUNCH(sf_longb_fill_kernel, n * bps, threads, 0, g.stream, (const SfLong *)d_F, d, G, bps, D);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(B.ev[1], g.stream));
+  SF_LAUNCH(sf_longb_f5_kernel, n, threads, 0, g.stream, (const SfLong *)d_F, D, d_i32 + o_mfe);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(B.ev[2], g.stream));
+  if (trace) {
+    SF_LAUNCH(sf_longb_trace_kernel, n, threads, 0, g.stream, (const SfLong *)d_F, D);
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipEventRecord(B.ev[3], g.stream));
+  HIPCHK(hipMemcpyAsync(e_host + s0, d_i32 + o_mfe, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, g.stream));
+  if (trace) HIPCHK(hipMemcpyAsync(db_host, d_u8 + o_db, n_L + (size_t)n, hipMemcpyDeviceToHost, g.stream));
+  if ((rc = read_status(g.stream, false))) return rc;
+  for (int k = 0; k < 3; k++) {
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, B.ev[k], B.ev[k + 1]));
+    ms_out[k] += (k == 2 && !trace) ? 0.0 : ms;
+  }
+  return SF_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int sf_fold_long_batch(const uint8_t *seqs, int n, int ld, const int32_t *len, const char *cons, int32_t *mfe_out, char *db_out) {
+  int rc = check_ready();
+  if (rc) return rc;
+  if (n < 0 || (n > 0 && (!seqs || !len || !mfe_out))) return SF_ERR_BAD_ARG;
+  for (int k = 0; k < n; k++)
+    if (len[k] < 1 || len[k] > SF_MAX_LONG || len[k] > ld) return SF_ERR_BAD_ARG;
+  if (n == 0) {
+    for (int k = 0; k < 3; k++) g_longb_ms[k] = 0.0;
+    g_longb_chunks = 0;
+    return SF_OK;
+  }
+  // every constraint row is looked at before anything is launched: a row of dots is no constraint
+  std::vector<char> constrained((size_t)n, 0);
+  if (cons)
+    for (int k = 0; k < n; k++) {
+      const char *c = cons + (size_t)k * ld;
+      bool any = false, noncanonical = false;
+      for (int x = 0; x < len[k] && !any; x++) any = c[x] != '.';
+      if (!any) continue;
+      if ((rc = scan_constraints(seqs + (size_t)k * ld, c, 1, len[k], &noncanonical))) return rc;
+      constrained[k] = 1;
+    }
+  // results are staged and handed over only when every chunk has succeeded (they outlive the chunks' device buffers)
+  std::vector<int32_t> e_host((size_t)n);
+  std::vector<char> db_host;
+  if (db_out) {
+    size_t total = 0;
+    for (int k = 0; k < n; k++) total += (size_t)len[k] + 1;
+    db_host.resize(total);
+  }
+  double ms[3] = {0, 0, 0};
+  int chunks = 0;
+  size_t db_off = 0;
+  for (int s0 = 0; s0 < n;) {
+    size_t bytes = 0, db_bytes = 0;
+    int m = 0;
+    while (s0 + m < n && m < kLongBatchMaxSeqs) {
+      const size_t b = long_batch_seq_bytes(len[s0 + m]);
+      if (m > 0 && bytes + b > g_longb_bytes) break;
+      bytes += b;
+      db_bytes += (size_t)len[s0 + m] + 1;
+      m++;
+    }
+    if ((rc = long_batch_chunk(seqs, ld, len, cons, constrained, s0, m, e_host.data(), db_out ? db_host.data() + db_off : nullptr,
+                               ms)))
+      return rc;
+    db_off += db_bytes;
+    s0 += m;
+    chunks++;
+  }
+  memcpy(mfe_out, e_host.data(), (size_t)n * sizeof(int32_t));
+  if (db_out) {
+    size_t off = 0;
+    for (int k = 0; k < n; k++) {
+      memcpy(db_out + (size_t)k * ((size_t)ld + 1), db_host.data() + off, (size_t)len[k] + 1);
+      off += (size_t)len[k] + 1;
+    }
+  }
+  for (int k = 0; k < 3; k++) g_longb_ms[k] = ms[k];
+  g_longb_chunks = chunks;
+  return SF_OK;
+}
+
+int sf_fold_long_batch_times(double *fill_ms, double *f5_ms, double *trace_ms, int *chunks) {
+  SF_ENTER();
+  if (fill_ms) *fill_ms = g_longb_ms[0];
+  if (f5_ms) *f5_ms = g_longb_ms[1];
+  if (trace_ms) *trace_ms = g_longb_ms[2];
+  if (chunks) *chunks = g_longb_chunks;
+  return SF_OK;
+}
+
+int sf_set_long_batch_bytes(size_t bytes) {
+  g_longb_bytes = bytes ? bytes : kLongBatchBytesDefault;
   return SF_OK;
 }
 

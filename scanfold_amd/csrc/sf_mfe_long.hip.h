@@ -76,12 +76,10 @@ __global__ void sf_long_hc_kernel(const char *src, int L, char *c, int16_t *part
   if (threadIdx.x == 0 && blockIdx.x == 0 && sf_hc_parse(src, L, c, partner, encl, stack)) atomicOr(status, 2);
 }
 
-// Diagonal d of the fill.  Thread t of the grid is lane t % G of the group of cell i = t / G + 1.
-__global__ void sf_long_fill_kernel(SfLong F, int d, int G, const SfDevParams *__restrict__ D) {
+// Cell i = cell + 1 of diagonal d, as lane r of the cell's group of G lanes (shared with sf_mfe_long_batch.hip.h).  Every lane
+// of a wave comes here, with or without a cell: the group's minimum is a butterfly over the wave.
+__device__ __forceinline__ void sfl_fill_cell(const SfLong &F, int d, int G, int r, size_t cell, const SfDevParams *__restrict__ D) {
   const int L = F.L;
-  const size_t gt = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int r = (int)(gt % (size_t)G);
-  const size_t cell = gt / (size_t)G;
   const bool valid = cell < (size_t)(L - d);
   const int i = (int)cell + 1, j = i + d;
   int32_t *dml_d = F.dml + (size_t)(d % 3) * (size_t)(L + 2);
@@ -148,8 +146,14 @@ __global__ void sf_long_fill_kernel(SfLong F, int d, int G, const SfDevParams *_
   }
 }
 
+// Diagonal d of the fill.  Thread t of the grid is lane t % G of the group of cell i = t / G + 1.
+__global__ void sf_long_fill_kernel(SfLong F, int d, int G, const SfDevParams *__restrict__ D) {
+  const size_t gt = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  sfl_fill_cell(F, d, G, (int)(gt % (size_t)G), gt / (size_t)G, D);
+}
+
 // f5[j] = min(f5[j-1], min_i f5[i-1] + c[i][j] + ExtLoop(i, j)); one workgroup, column j of c read contiguously.
-__global__ void sf_long_f5_kernel(SfLong F, const SfDevParams *__restrict__ D, int32_t *mfe_out) {
+__device__ __forceinline__ void sfl_f5(const SfLong &F, const SfDevParams *__restrict__ D, int32_t *mfe_out) {
   __shared__ int red[16];
   const int tid = threadIdx.x, L = F.L;
   if (tid == 0) F.f5[0] = 0;
@@ -167,11 +171,12 @@ __global__ void sf_long_f5_kernel(SfLong F, const SfDevParams *__restrict__ D, i
   }
   if (tid == 0 && mfe_out) *mfe_out = F.f5[L];
 }
+__global__ void sf_long_f5_kernel(SfLong F, const SfDevParams *__restrict__ D, int32_t *mfe_out) { sfl_f5(F, D, mfe_out); }
 
 // Traceback in one workgroup (the oracle's mfe_traceback step by step).  Thread 0 keeps the stack and the nibbling loops; each
 // search over candidates is spread over the workgroup and takes the first match in the oracle's order (a block minimum over
 // the candidate's position in that order).
-__global__ void sf_long_trace_kernel(SfLong F, const SfDevParams *__restrict__ D) {
+__device__ __forceinline__ void sfl_trace(const SfLong &F, const SfDevParams *__restrict__ D) {
   __shared__ int red[16];
   __shared__ int sh_i, sh_j, sh_ml, sh_s, sh_bad, sh_pair;
   const int tid = threadIdx.x, nt = blockDim.x, L = F.L;
@@ -294,3 +299,4 @@ __global__ void sf_long_trace_kernel(SfLong F, const SfDevParams *__restrict__ D
   }
   if (tid == 0 && sh_bad) atomicOr(F.status, 1);
 }
+__global__ void sf_long_trace_kernel(SfLong F, const SfDevParams *__restrict__ D) { sfl_trace(F, D); }

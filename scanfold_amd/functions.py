@@ -15,7 +15,7 @@ zscore_function(energy_list, r)        SFF:741-751   statistics.stdev variant, 0
 rna_refold(frag, T, constraint_file)   SFF:758-772   RNAfold -p -T -C: whole records through fold_long / pf_long
 rna_folder((frag, T, algo))            SFF:774-789   one batched device launch of size 1
 randomizer(frag)                       SFF:800-802
-energies(seq_list, T, algo)            SFF:805-814   ONE batched launch for the whole list
+energies(seq_list, T, algo)            SFF:805-814   ONE batched launch for the whole list (past 400 nt: fold_long_batch)
 scramble(text, r, type)                SFF:834-851
 get_gc_content(frag)                   SFF:1023-1036
 get_dinucleotide_counts(frag)          SFF:1079-1094
@@ -144,7 +144,10 @@ def _dcal_to_float(dcal):
 
 
 def energies(seq_list, temperature=37, algo="rnafold"):
-    """MFE (kcal/mol) of every sequence, order preserved.  One device launch per distinct length."""
+    """MFE (kcal/mol) of every sequence, order preserved.  Lengths up to SF_MAX_W: one device launch (mfe_batch) per distinct
+    length.  Every longer sequence of the call, up to SF_MAX_LONG and of any mix of lengths, goes to ONE fold_long_batch
+    (whole-record folds side by side; chunked by device memory inside the library), so a record past the window limit and its
+    shuffles cost little more than one fold.  A library without sf_fold_long_batch raises ScanFoldHipError."""
     from . import _lib
     if algo != "rnafold":
         # the reference leaves MFE unbound for any other algo (ScanFoldFunctions.py:785-789)
@@ -156,7 +159,16 @@ def energies(seq_list, temperature=37, algo="rnafold"):
     by_len = {}
     for k, s in enumerate(seqs):
         by_len.setdefault(len(s), []).append(k)
+    long_ks = [k for k, s in enumerate(seqs) if len(s) > _lib.SF_MAX_W]
+    if long_ks:
+        if not eng.has_fold_long_batch():
+            raise _lib.ScanFoldHipError("energies: a sequence of more than %d nt needs sf_fold_long_batch, which this library "
+                                        "(%s) does not export" % (_lib.SF_MAX_W, getattr(eng.lib, "_name", "?")))
+        for k, v in zip(long_ks, _dcal_to_float(eng.fold_long_batch([seqs[k] for k in long_ks]))):
+            out[k] = v
     for n, ks in by_len.items():
+        if n > _lib.SF_MAX_W:
+            continue
         if n == 0:
             for k in ks:
                 out[k] = 0.0

@@ -14,6 +14,8 @@ refolds of ScanFold.py:1582-1776 (scanfold_amd.motifs: `<that>.ExtractedStructur
 then with the -1 and the -2 filter's dot-bracket lines as hard constraints, through the RNA facade (whole-record folds,
 sf_fold_long), into `<that>.<--dbn_file_path>` and `<that>.AllDBN.txt`.  ScanFold.py's per-record directories and IGV
 wig exports are not reproduced.
+--global_zscore (not upstream) z-scores the whole record against shuffles of itself (one batched whole-record fold,
+sf_fold_long_batch) into `<that>.global_zscore.txt`.
 --lri replaces the window scan by the k-mer duplex scan (ScanFold.py:391-393,421,769-1034; scanfold_amd.lri): it writes
 `<that>.LRI.out`, reports the number of hits and stops — upstream's continuation into the Fold stage is not runnable in
 general (README.md) and is not reproduced.
@@ -218,6 +220,46 @@ def global_refold(seq, name, outname, temperature, dbn_file_path="AllDBN-global_
                 w.write(f.read())
 
 
+GLOBAL_ZSCORE_HEADER = ("Name\tLength\tTemperature\tRandomizations\tShuffleType\tMFE\tShuffleMeanMFE\tShuffleStdevMFE\t"
+                        "Z-score\tP-value\n")
+
+
+def global_zscore(seq, name, outname, temperature, randomizations, shuffle_type, seed=0):
+    """--global_zscore (not upstream): the z-score of the WHOLE record.  The unconstrained MFE of `seq` at int(-t) under the
+    model of global_refold (no --span) against `randomizations` shuffles of it (`functions.scramble`, "di" or "mono"), folded
+    in one `functions.energies` call — past 400 nt one batched whole-record fold (sf_fold_long_batch) — and turned into a
+    z-score and p-value by `zscore_function` / `pvalue_function`, quirks included.  Writes `<outname>.global_zscore.txt`: a
+    header line and one tab-separated row of name, length, temperature, randomizations, shuffle type, MFE, mean and sample
+    standard deviation of the shuffles' MFEs, z-score, p-value, the numbers through str(round(x, 2)) as in the scan table.
+    Cost: r + 1 folds of the whole record, O(L^3) each: tenths of a second at 1 kb, about twenty minutes at 30 kb with
+    r = 100 by the single-fold time of DESIGN 4.4 (the batch's tables for such a record are one chunk per sequence).
+    The shuffles draw from Python's `random` seeded with `seed`; the generator's state, and the engine's span, parameter
+    set and temperature, are put back as they were, also when a fold raises, so every other output of the run is the same
+    with and without the flag."""
+    import random
+    eng = _lib.get_engine()
+    span0, params0 = eng.max_bp_span, eng.params
+    state0 = random.getstate()
+    try:
+        random.seed(seed)
+        shuffles = sff.scramble(seq, randomizations, shuffle_type)
+        eng.set_max_bp_span(0)  # (the scan's --span is engine state; the whole-record model has none)
+        E = sff.energies([seq] + shuffles, int(temperature))
+    finally:
+        random.setstate(state0)
+        if eng.params is not params0:
+            eng._load(params0)
+            eng.params = params0
+        eng.set_max_bp_span(span0)
+    z = sff.zscore_function(E, randomizations)
+    p = sff.pvalue_function(E, randomizations)
+    row = [str(name), str(len(seq)), str(int(temperature)), str(randomizations), str(shuffle_type)]
+    row += [str(round(x, 2)) for x in (E[0], statistics.mean(E[1:]), statistics.stdev(E[1:]), z, p)]
+    with open(outname + ".global_zscore.txt", "w") as w:
+        w.write(GLOBAL_ZSCORE_HEADER)
+        w.write("\t".join(row) + "\n")
+
+
 def build_parser():
     p = argparse.ArgumentParser(description="ScanFold (scan + fold) on the MI355X HIP engine")
     p.add_argument('filename', type=str, help='input fasta')
@@ -243,6 +285,9 @@ def build_parser():
                    help='Global refold option. Refold full sequence using Zavg <-1 and <-2 base pairs')
     p.add_argument('--global_ensemble', action='store_true',
                    help='with --global_refold: also write ensemble free energy, ED and centroid of the three whole-record folds')
+    p.add_argument('--global_zscore', action='store_true',
+                   help='not in upstream ScanFold: z-score of the whole record (its MFE at -t, no --span, against -r shuffles of '
+                        '--type seeded with --seed) into <output prefix>.global_zscore.txt; costs r + 1 whole-record folds')
     p.add_argument('--dbn_file_path', type=str, default="AllDBN-global_refold.txt",
                    help='file name (after the output prefix) of the global refold records')
     p.add_argument('--lri', action='store_true', help='scan for long range interactions (k-mer duplexes) instead of windows')
@@ -268,6 +313,15 @@ def main(argv=None):
         raise ValueError("--global_refold refolds with the -1 / -2 dbn files of the Fold stage: not with -c 0 or --dont_fold")
     if args.global_ensemble and not args.global_refold:
         raise ValueError("--global_ensemble adds the partition function to the folds of --global_refold: give both")
+    if args.global_zscore and args.lri:
+        raise ValueError("--global_zscore z-scores the record of a window scan: not with --lri")
+    if args.global_zscore:  # refused before any record is scanned
+        if args.type not in ("di", "mono"):
+            raise ValueError('Shuffle type not properly designated; please input "di" or "mono"')
+        for read_name, seq in scanmod.read_fasta(args.filename):
+            if len(seq) > _lib.SF_MAX_LONG:
+                raise ValueError("--global_zscore: record %s has %d nt, whole-record folds stop at %d"
+                                 % (read_name, len(seq), _lib.SF_MAX_LONG))
     if args.lri:
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             raise ValueError("--lri runs on one GPU: start it without a multi-process launcher")
@@ -329,6 +383,9 @@ def main(argv=None):
             writers.write_wig(zlist, step, args.name, outname + ".scan-zscores.wig")
             writers.write_wig(table.pvalues, step, args.name, outname + ".scan-pvalue.wig")
             writers.write_wig(table.ed.tolist(), step, args.name, outname + ".scan-ED.wig")
+            if args.global_zscore:
+                print("Folding the full sequence and its shuffles for the global z-score...")
+                global_zscore(seq, args.name, outname, args.t, r, args.type, args.seed)
             if args.global_refold:
                 print("Refolding full sequence using ScanFold results as constraints...")
                 global_refold(seq, args.name, outname, args.t, args.dbn_file_path, ensemble=args.global_ensemble)
@@ -338,6 +395,8 @@ def main(argv=None):
                 found = motifmod.extract_structures(line, seq)
                 motifmod.refold_motifs(read_name, found, args.type, outname + ".ExtractedStructures.gff3",
                                        folder=motifmod.EngineFolder(args.t, args.algo), file_prefix=outname)
+        elif args.global_zscore:
+            global_zscore(seq, args.name, outname, args.t, r, args.type, args.seed)
     return 0
 
 
