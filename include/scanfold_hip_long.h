@@ -8,8 +8,9 @@
  *
  * sf_fold_long gives the MFE and its structure, sf_pf_long the partition function (ensemble free energy, centroid, ensemble
  * diversity) of the same whole record; sf_fold_long_batch is sf_fold_long for many sequences of any lengths side by side
- * (a record and its shuffles: the z-score of a sequence past SF_MAX_W).  Soft constraints (SHAPE) are not provided past
- * SF_MAX_W.
+ * (a record and its shuffles: the z-score of a sequence past SF_MAX_W), and sf_pf_long_batch is sf_pf_long for many
+ * sequences, constraints and hints side by side (the three ensembles of --global_ensemble; fc.pf() over long fragments),
+ * every row bit for bit what sf_pf_long returns for it.  Soft constraints (SHAPE) are not provided past SF_MAX_W.
  */
 #ifndef SCANFOLD_HIP_LONG_H
 #define SCANFOLD_HIP_LONG_H
@@ -55,7 +56,7 @@ int sf_fold_long_batch(const uint8_t *seqs, int n, int ld, const int32_t *len, c
  * was not asked for), and the number of chunks it ran as.  Any pointer may be NULL. */
 int sf_fold_long_batch_times(double *fill_ms, double *f5_ms, double *trace_ms, int *chunks);
 
-/* The byte budget of one chunk of sf_fold_long_batch; 0 restores the default (8 GiB). */
+/* The byte budget of one chunk of sf_fold_long_batch and of sf_pf_long_batch; 0 restores the default (8 GiB). */
 int sf_set_long_batch_bytes(size_t bytes);
 
 /* fc.pf(); fc.centroid(); fc.mean_bp_distance() — RNAfold -p — for one sequence of any length 1..SF_MAX_LONG
@@ -78,6 +79,35 @@ int sf_pf_long(const uint8_t *seq, int L, const char *cons, const int32_t *mfe_d
  * outside pass with the probabilities, the number of attempts, and the final per-nucleotide scale ln s.  Any pointer may be
  * NULL. */
 int sf_pf_long_times(double *inside_ms, double *outside_ms, int *attempts, double *lns);
+
+/* One row of sf_pf_long_batch: sf_pf_long's three numbers, the final per-nucleotide scale ln s and the number of inside
+ * passes the row took (what sf_pf_long_times reports for the row folded alone). */
+typedef struct { double ens_dG, mean_bp_dist, centroid_dist, lns; int32_t attempts, reserved; } sf_pf_long_row;
+#define SF_PF_LONG_NO_HINT INT32_MIN /* mfe_dcal_hint[s]: no MFE known for row s */
+
+/* sf_pf_long for n sequences at once.  seqs, n, ld, len, cons exactly as for sf_fold_long_batch: ragged rows of
+ * 1 <= len[s] <= SF_MAX_LONG and <= ld; cons NULL or n rows of ld characters, a row of '.' only being no constraint.
+ * mfe_dcal_hint: NULL, or n values with the meaning of sf_pf_long's, SF_PF_LONG_NO_HINT where a row has none.
+ * out: n records, or NULL.  centroid_out: n rows of ld + 1 bytes (row s: len[s] characters and a NUL), or NULL.
+ * For every row ens_dG, mean_bp_dist, centroid_dist, the centroid, lns and attempts are bit for bit what sf_pf_long (and
+ * sf_pf_long_times) gives for that sequence, constraint and hint on the same device, whatever else is in the call, in
+ * whatever row order and however the call is chunked: a row's lane groups, its probability waves and the powers of its
+ * scale are those of the single call.
+ * One launch per anti-diagonal covers every row of a chunk, in the inside and in the outside pass.  Each row has its own
+ * scale: after an inside pass only the rows whose ln Z_s left the range repeat it, the others wait for the outside pass.
+ * A chunk holds as many consecutive rows as fit the byte budget of sf_set_long_batch_bytes (8 GiB by default), each row
+ * counted as 56 * L (L+1) / 2 + 60 L bytes, always at least one row; its tables are a fixed number of device allocations
+ * made for the chunk and freed after it.
+ * n == 0: SF_OK.  n < 0, a length < 1, > SF_MAX_LONG or > ld, seqs / len NULL with n > 0: SF_ERR_BAD_ARG.  Unbalanced
+ * brackets in any row: SF_ERR_CONSTRAINT, before anything is launched.  Not enough device memory: SF_ERR_HIP with the text
+ * in sf_last_hip_error().  A row that used up its attempts: SF_ERR_RANGE.  On any error no output is written. */
+int sf_pf_long_batch(const uint8_t *seqs, int n, int ld, const int32_t *len, const char *cons, const int32_t *mfe_dcal_hint,
+                     sf_pf_long_row *out, char *centroid_out);
+
+/* Of the last successful sf_pf_long_batch, summed over its chunks: device-event times (ms) of the inside passes (q5 / q3
+ * included) and of the outside and probability passes, the number of chunks, and the number of inside passes run (one per
+ * chunk when no row needed another scale).  Any pointer may be NULL. */
+int sf_pf_long_batch_times(double *inside_ms, double *outside_ms, int *chunks, int *inside_passes);
 
 #ifdef __cplusplus
 }

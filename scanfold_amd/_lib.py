@@ -86,7 +86,14 @@ _LONG_EXPORTS = {
                                   ctypes.c_void_p, ctypes.c_void_p]),
     "sf_pf_long_times": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                         ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)]),
+    "sf_pf_long_batch": (ctypes.c_int, [_c_u8p, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 5),
+    "sf_pf_long_batch_times": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                              ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
 }
+# one row of sf_pf_long_batch (struct sf_pf_long_row) and its "no hint for this row" (SF_PF_LONG_NO_HINT)
+PF_LONG_ROW_DTYPE = np.dtype([("ens_dG", np.float64), ("mean_bp_dist", np.float64), ("centroid_dist", np.float64),
+                              ("lns", np.float64), ("attempts", np.int32), ("reserved", np.int32)])
+SF_PF_LONG_NO_HINT = -2 ** 31
 
 
 # include/scanfold_hip_duplex.h: likewise optional (duplex folds and the LRI scan)
@@ -421,6 +428,65 @@ class Engine:
         a, b, n, l = ctypes.c_double(), ctypes.c_double(), ctypes.c_int(), ctypes.c_double()
         self._check(self.lib.sf_pf_long_times(ctypes.byref(a), ctypes.byref(b), ctypes.byref(n), ctypes.byref(l)))
         return dict(inside_ms=a.value, outside_ms=b.value, attempts=n.value, lns=l.value)
+
+    def has_pf_long_batch(self):
+        return getattr(self.lib, "sf_pf_long_batch", None) is not None
+
+    def _need_pf_long_batch(self):
+        if not self.has_pf_long_batch():
+            raise ScanFoldHipError("this library (%s) has no sf_pf_long_batch: partition functions of many sequences past "
+                                   "%d nt need libscanfold_hip.so" % (getattr(self.lib, "_name", "?"), SF_MAX_W))
+
+    def pf_long_batch(self, seqs, cons=None, mfe_hints=None):
+        """pf_long for many sequences of 1..SF_MAX_LONG nt, of any mix of lengths, side by side in the same launches
+        (sf_pf_long_batch) -> a list of pf_long's dicts with two more keys, lns (the row's final per-nucleotide scale) and
+        attempts (its inside passes).  cons / mfe_hints: None, or one item per sequence, each a constraint string of the
+        sequence's length / the sequence's MFE in dcal/mol, or None.  Every row equals pf_long of that row bit for bit.
+        Raises ScanFoldHipError on a library without the entry point (there is no fallback)."""
+        self._need_pf_long_batch()
+        rows = [s if isinstance(s, (bytes, bytearray)) else str(s).encode("ascii") for s in seqs]
+        n = len(rows)
+        ld = max([1] + [len(s) for s in rows])
+        arr = np.zeros((n, ld), dtype=np.uint8)
+        for k, s in enumerate(rows):
+            arr[k, :len(s)] = np.frombuffer(bytes(s), dtype=np.uint8)
+        lens = np.array([len(s) for s in rows], dtype=np.int32)
+        c = None
+        if cons is not None:
+            cons = list(cons)
+            if len(cons) != n:
+                raise ValueError("one constraint item (a string or None) per sequence")
+            if any(x is not None for x in cons):
+                c = np.full((n, ld), ord("."), dtype=np.uint8)
+                for k, x in enumerate(cons):
+                    if x is None:
+                        continue
+                    x = x if isinstance(x, (bytes, bytearray)) else str(x).encode("ascii")
+                    if len(x) != len(rows[k]):
+                        raise ValueError("constraint string and sequence differ in length")
+                    c[k, :len(x)] = np.frombuffer(bytes(x), dtype=np.uint8)
+        h = None
+        if mfe_hints is not None:
+            mfe_hints = list(mfe_hints)
+            if len(mfe_hints) != n:
+                raise ValueError("one MFE hint (an energy in dcal/mol or None) per sequence")
+            if any(x is not None for x in mfe_hints):
+                h = np.array([SF_PF_LONG_NO_HINT if x is None else int(x) for x in mfe_hints], dtype=np.int32)
+        out = np.zeros(n, dtype=PF_LONG_ROW_DTYPE)
+        cen = np.zeros((n, ld + 1), dtype=np.uint8)
+        self._check(self.lib.sf_pf_long_batch(arr.ctypes.data, n, ld, lens.ctypes.data, None if c is None else c.ctypes.data,
+                                              None if h is None else h.ctypes.data, out.ctypes.data, cen.ctypes.data))
+        return [dict(dG=float(out["ens_dG"][k]), mean_bp_dist=float(out["mean_bp_dist"][k]),
+                     centroid=bytes(cen[k, :lens[k]]).decode(), centroid_dist=float(out["centroid_dist"][k]),
+                     lns=float(out["lns"][k]), attempts=int(out["attempts"][k])) for k in range(n)]
+
+    def pf_long_batch_times(self):
+        """-> dict(inside_ms, outside_ms, chunks, inside_passes) of the last pf_long_batch (device events, summed over its
+        chunks; inside_passes = chunks when no row needed another scale)."""
+        self._need_pf_long_batch()
+        a, b, ch, ps = ctypes.c_double(), ctypes.c_double(), ctypes.c_int(), ctypes.c_int()
+        self._check(self.lib.sf_pf_long_batch_times(ctypes.byref(a), ctypes.byref(b), ctypes.byref(ch), ctypes.byref(ps)))
+        return dict(inside_ms=a.value, outside_ms=b.value, chunks=ch.value, inside_passes=ps.value)
 
     # -- duplex folds and the LRI scan (include/scanfold_hip_duplex.h) --
     def has_duplex(self):

@@ -23,6 +23,7 @@
 #include "sf_mfe_long_batch.hip.h"
 #include "sf_pf.hip.h"
 #include "sf_pf_long.hip.h"
+#include "sf_pf_long_batch.hip.h"
 #include "sf_pf_fast.hip.h"
 #include "sf_pf_lds.hip.h"
 #include "sf_shuffle.hip.h"
@@ -1440,12 +1441,22 @@ double g_pfl_ms[2] = {0, 0};  // inside (all attempts, with q5 / q3), outside (w
 int g_pfl_attempts = 0;
 double g_pfl_lns = 0.0;
 
-// lanes per cell of a diagonal with `cells` cells whose longest sum has `terms` terms: fill the lane budget, at most one wave,
-// and no more lanes than leave each some sixteen terms (four lanes for the interior loops of a short diagonal)
-int pfl_group(size_t cells, int terms, size_t lanes) {
-  int G = 1;
-  while (G < 64 && (size_t)(2 * G) * cells <= lanes && 32 * G <= std::max(64, terms)) G *= 2;
-  return G;
+// sc[k] = s^-k and mlbs[k] = (MLbase / s)^k, k = 0 .. L + 1, for the per-nucleotide scale s = e^lns.  Made on the host by
+// this one loop for sf_pf_long and for every row of sf_pf_long_batch: a device exp may differ from it in the last bit.
+void pfl_scale_powers(double lns, double ln_mlbase, int L, double *sc, double *mlbs) {
+  for (int k = 0; k <= L + 1; k++) {
+    sc[k] = exp(-lns * k);
+    mlbs[k] = exp((ln_mlbase - lns) * k);
+  }
+}
+// the scale of a row's first attempt
+double pfl_first_lns(const int32_t *mfe_dcal_hint, double kT, int L) {
+  return mfe_dcal_hint ? SF_PFLONG_MFE_FACTOR * (-(double)*mfe_dcal_hint * 10.0 / kT) / L : SF_PFLONG_LNS_DEFAULT;
+}
+// the scale of the next attempt after an inside pass that left the range (ln Z_s = lz)
+double pfl_next_lns(double lns, double lz, int L) {
+  // (q5[L] = +inf: log = +inf; an underflow to 0: -inf; NaN counts as an overflow)
+  return lns + (isfinite(lz) ? lz / L : ((lz < 0 ? -700.0 : 700.0) / L));
 }
 }  // namespace
 
@@ -1485,7 +1496,7 @@ int sf_pf_long(const uint8_t *seq, int L, const char *cons, const int32_t *mfe_d
   F.a0 = F.qbt;   // (dead after q5)
   F.wt = F.qm1t;  // (dead after the inside pass)
   const size_t lanes = (size_t)(g.n_cu > 0 ? g.n_cu : 1) * SF_PFLONG_LANES_PER_CU;
-  const int prob_waves = (int)std::min<size_t>((size_t)L, lanes / 64);
+  const int prob_waves = pfl_prob_waves(L, lanes);
   double *d_hp, *d_sc, *d_ml;
   if ((rc = B.alloc(&p, ((size_t)L + 1) * sizeof(double), "hairpin weights"))) return rc;
   d_hp = (double *)p;
@@ -1536,8 +1547,7 @@ int sf_pf_long(const uint8_t *seq, int L, const char *cons, const int32_t *mfe_d
     *grid = (int)((total + threads - 1) / threads);
   };
 
-  double lns = SF_PFLONG_LNS_DEFAULT;
-  if (mfe_dcal_hint) lns = SF_PFLONG_MFE_FACTOR * (-(double)*mfe_dcal_hint * 10.0 / kT) / L;
+  double lns = pfl_first_lns(mfe_dcal_hint, kT, L);
   const double ln_mlbase = log(M.pf_MLbase);
   double res[3] = {0, 0, 0};
   std::vector<char> cen((size_t)L + 1);
@@ -1545,10 +1555,7 @@ int sf_pf_long(const uint8_t *seq, int L, const char *cons, const int32_t *mfe_d
   int attempt = 0;
   bool done = false;
   for (; attempt < SF_PFLONG_MAX_ATTEMPTS && !done; attempt++) {
-    for (int k = 0; k <= L + 1; k++) {
-      hsc[k] = exp(-lns * k);
-      hml[k] = exp((ln_mlbase - lns) * k);
-    }
+    pfl_scale_powers(lns, ln_mlbase, L, hsc.data(), hml.data());
     HIPCHK(hipMemcpyAsync(d_sc, hsc.data(), ((size_t)L + 2) * sizeof(double), hipMemcpyHostToDevice, g.stream));
     HIPCHK(hipMemcpyAsync(d_ml, hml.data(), ((size_t)L + 2) * sizeof(double), hipMemcpyHostToDevice, g.stream));
     HIPCHK(hipEventRecord(B.ev[0], g.stream));
@@ -1568,8 +1575,7 @@ int sf_pf_long(const uint8_t *seq, int L, const char *cons, const int32_t *mfe_d
     ms_in += ms;
     const double lz = res[0];
     if (!isfinite(lz) || fabs(lz) > SF_PF_LNZ_MAX) {
-      // (q5[L] = +inf: log = +inf; an underflow to 0: -inf; NaN counts as an overflow)
-      lns += isfinite(lz) ? lz / L : ((lz < 0 ? -700.0 : 700.0) / L);
+      lns = pfl_next_lns(lns, lz, L);
       continue;
     }
     HIPCHK(hipMemsetAsync(F.cen, '.', (size_t)L, g.stream));
@@ -1618,6 +1624,322 @@ int sf_pf_long_times(double *inside_ms, double *outside_ms, int *attempts, doubl
   if (outside_ms) *outside_ms = g_pfl_ms[1];
   if (attempts) *attempts = g_pfl_attempts;
   if (lns) *lns = g_pfl_lns;
+  return SF_OK;
+}
+
+}  // extern "C"
+
+// ---------------- many whole-record partition functions at once (sf_pf_long_batch.hip.h) ----------------
+namespace {
+double g_pflb_ms[2] = {0, 0};  // inside passes (q5 / q3 included), outside and probability passes of the last sf_pf_long_batch
+int g_pflb_chunks = 0, g_pflb_passes = 0;
+
+// Rows s0 .. s0 + n - 1 of the batch as one chunk.  rows_host / cen_host: the caller's staging buffers (the chunk's records at
+// rows_host[s0 ..], its centroids back to back, L + 1 bytes each, from cen_host).  ms_out: inside, outside; *passes: inside
+// passes run.  A fixed number of device allocations whatever n is; all freed on return.
+int pf_long_batch_chunk(const uint8_t *seqs, int ld, const int32_t *len, const char *cons, const std::vector<char> &constrained,
+                        const int32_t *hint, int s0, int n, sf_pf_long_row *rows_host, char *cen_host, double ms_out[2],
+                        int *passes) {
+  int rc;
+  const sf_params_blob *P = (const sf_params_blob *)g.slot[g.cur].src.data();  // the resident set as it was handed in
+  const Ctx::ModelSlot &M = g.slot[g.cur];
+  const double kT = M.pf_kT, ln_mlbase = log(M.pf_MLbase);
+  // the budget of ONE sf_pf_long call: it sizes every row's lane groups and probability waves, whatever the batch holds
+  const size_t lanes = (size_t)(g.n_cu > 0 ? g.n_cu : 1) * SF_PFLONG_LANES_PER_CU;
+  const size_t budget = (size_t)(g.n_cu > 0 ? g.n_cu : 1) * SF_PFLONGB_LANES_PER_CU;  // the batch's own, per launch
+  int Lmax = 0, n_hc = 0, wmax = 0;
+  size_t tri = 0, n_L = 0, n_hcL = 0, n_part = 0;
+  for (int k = 0; k < n; k++) {
+    const int L = len[s0 + k];
+    Lmax = std::max(Lmax, L);
+    tri += SF_LONG_TRI(L);
+    n_L += (size_t)L;
+    const int w = pfl_prob_waves(L, lanes);
+    wmax = std::max(wmax, w);
+    n_part += 2 * (size_t)w;
+    if (constrained[s0 + k]) { n_hc++; n_hcL += (size_t)L; }
+  }
+  // slices of the FP64 / int16 / byte allocations, in elements.  FP64: the results first (one copy reads every row's), then
+  // the powers of every row's scale (one copy writes them), the shared hairpin table, q5, q3 and the partial sums.
+  const size_t o_out = 0, o_pow = o_out + 3 * (size_t)n, n_pow = 2 * (n_L + 2 * (size_t)n), o_hp = o_pow + n_pow;
+  const size_t o_q5 = o_hp + (size_t)Lmax + 1, o_q3 = o_q5 + n_L + 2 * (size_t)n, o_part = o_q3 + n_L + 3 * (size_t)n;
+  const size_t n_f64 = o_part + n_part;
+  const size_t n_i16 = 3 * (n_hcL + 2 * (size_t)n_hc);  // partner, encl, stack: L + 2 each
+  const size_t o_S = 0, o_src = o_S + n_L + 2 * (size_t)n, o_hc = o_src + n_hcL, o_cen = o_hc + n_hcL + 2 * (size_t)n_hc;
+  const size_t o_act = o_cen + n_L + (size_t)n, n_u8 = o_act + (size_t)n;
+
+  std::vector<uint8_t> h8(o_hc, 0);  // sequences (codes, zero on both sides) and constraint rows, copied up in one piece
+  std::vector<double> hhp((size_t)Lmax + 1), hpow(n_pow), hout(3 * (size_t)n);
+  for (int s = 0; s <= Lmax; s++)  // (read only past the resident table: sf_pf_long's own extrapolation, the same for every L)
+    hhp[s] = (s <= 30) ? 0.0 : M.pf_hp30 * exp(-(P->lxc * log(s / 30.)) * 10. / kT);
+  std::vector<SfPfLong> hF((size_t)n);
+  std::vector<char> hcen(n_L + (size_t)n);
+
+  LongBufs B;
+  B.who = "sf_pf_long_batch";
+  void *p;
+  double *d_tri[SF_PFLONG_NTRI], *d_f64;
+  int16_t *d_i16 = nullptr;
+  uint8_t *d_u8;
+  SfPfLong *d_F;
+  static const char *const tri_names[SF_PFLONG_NTRI] = {"qb", "qb transposed / A0", "qm", "qm transposed", "qm1 / w", "ob", "A1"};
+  for (int k = 0; k < SF_PFLONG_NTRI; k++) {
+    if ((rc = B.alloc(&p, tri * sizeof(double), tri_names[k]))) return rc;
+    d_tri[k] = (double *)p;
+  }
+  if ((rc = B.alloc(&p, n_f64 * sizeof(double), "results, scale powers, hairpin weights, q5, q3, partial sums"))) return rc;
+  d_f64 = (double *)p;
+  if (n_i16) {
+    if ((rc = B.alloc(&p, n_i16 * sizeof(int16_t), "bracket partners"))) return rc;
+    d_i16 = (int16_t *)p;
+  }
+  if ((rc = B.alloc(&p, n_u8, "sequences, constraints, centroids, row marks"))) return rc;
+  d_u8 = (uint8_t *)p;
+  if ((rc = B.alloc(&p, (size_t)n * sizeof(SfPfLong), "partition function states"))) return rc;
+  d_F = (SfPfLong *)p;
+
+  std::vector<size_t> pow_off((size_t)n), cen_off((size_t)n);
+  size_t a_tri = 0, a_L = 0, a_hcL = 0, a_part = 0;
+  int a_hc = 0;
+  for (int k = 0; k < n; k++) {
+    const int L = len[s0 + k];
+    const uint8_t *row = seqs + (size_t)(s0 + k) * ld;
+    uint8_t *hS = h8.data() + o_S + a_L + 2 * (size_t)k;
+    for (int x = 0; x < L; x++) hS[x + 1] = sf_encode_nt(row[x]);
+    SfPfLong &F = hF[k];
+    memset(&F, 0, sizeof F);
+    F.L = L;
+    F.S = d_u8 + o_S + a_L + 2 * (size_t)k;
+    F.hpx = d_f64 + o_hp;
+    pow_off[k] = 2 * (a_L + 2 * (size_t)k);
+    F.sc = d_f64 + o_pow + pow_off[k];
+    F.mlbs = F.sc + (size_t)L + 2;
+    F.qb = d_tri[0] + a_tri; F.qbt = d_tri[1] + a_tri; F.qm = d_tri[2] + a_tri; F.qmt = d_tri[3] + a_tri;
+    F.qm1t = d_tri[4] + a_tri; F.ob = d_tri[5] + a_tri; F.a1 = d_tri[6] + a_tri;
+    F.a0 = F.qbt;   // (dead after q5)
+    F.wt = F.qm1t;  // (dead after the inside pass)
+    F.q5 = d_f64 + o_q5 + a_L + 2 * (size_t)k;
+    F.q3 = d_f64 + o_q3 + a_L + 3 * (size_t)k;
+    F.part = d_f64 + o_part + a_part;
+    F.out = d_f64 + o_out + 3 * (size_t)k;
+    cen_off[k] = a_L + (size_t)k;
+    F.cen = (char *)d_u8 + o_cen + cen_off[k];
+    if (constrained[s0 + k]) {
+      memcpy(h8.data() + o_src + a_hcL, cons + (size_t)(s0 + k) * ld, (size_t)L);
+      const size_t o16 = 3 * (a_hcL + 2 * (size_t)a_hc);
+      F.hc.c = (const char *)d_u8 + o_hc + a_hcL + 2 * (size_t)a_hc;
+      F.hc.partner = d_i16 + o16;
+      F.hc.encl = d_i16 + o16 + (size_t)L + 2;
+      a_hcL += (size_t)L;
+      a_hc++;
+    }
+    a_tri += SF_LONG_TRI(L);
+    a_L += (size_t)L;
+    a_part += 2 * (size_t)pfl_prob_waves(L, lanes);
+  }
+  HIPCHK(hipMemcpyAsync(d_u8, h8.data(), h8.size(), hipMemcpyHostToDevice, g.stream));
+  HIPCHK(hipMemcpyAsync(d_f64 + o_hp, hhp.data(), hhp.size() * sizeof(double), hipMemcpyHostToDevice, g.stream));
+  HIPCHK(hipMemcpyAsync(d_F, hF.data(), (size_t)n * sizeof(SfPfLong), hipMemcpyHostToDevice, g.stream));
+  a_hcL = 0;
+  for (int k = 0; k < n; k++) {  // the bracket partners and enclosing pairs of every constrained row
+    if (!constrained[s0 + k]) continue;
+    const SfPfLong &F = hF[k];
+    SF_LAUNCH(sf_long_hc_kernel, 1, 64, 0, g.stream, (const char *)d_u8 + o_src + a_hcL, F.L, (char *)F.hc.c,
+              (int16_t *)F.hc.partner, (int16_t *)F.hc.encl, (int16_t *)F.hc.encl + (size_t)F.L + 2, (int *)g.status.p);
+    a_hcL += (size_t)F.L;
+  }
+  HIPCHK(hipGetLastError());
+
+  for (auto &e : B.ev) HIPCHK(hipEventCreate(&e));
+  const SfDevParams *D = (const SfDevParams *)g.dP;
+  const SfDevParamsPF *X = (const SfDevParamsPF *)g.dX;
+  const int threads = SF_PFLONGB_THREADS;
+  const uint8_t *d_act = d_u8 + o_act;
+  // workgroups per row on diagonal d when the longest live row has Ltop nt: what sf_pf_long would give that row, cut down
+  // until the whole launch fits the batch's budget (at least one).  It orders no sum: a group walks more cells instead.
+  auto blocks_per_row = [&](int Ltop, int d) {
+    const size_t cells = (size_t)(Ltop - d);
+    const size_t want = std::min(cells * (size_t)pfl_group(1, d, lanes), lanes);
+    size_t bps = (want + threads - 1) / threads;
+    const size_t fit = budget / ((size_t)n * threads);
+    return (int)std::max<size_t>(1, std::min(bps, fit));
+  };
+
+  // 0: waits for an inside pass; 1: in range, waits for the outside pass; 2: done
+  enum { PENDING = 0, READY = 1, DONE = 2 };
+  std::vector<int> state((size_t)n, PENDING), attempts((size_t)n, 0);
+  std::vector<double> lns((size_t)n), lz((size_t)n, 0.0);
+  std::vector<uint8_t> act((size_t)n);
+  for (int k = 0; k < n; k++) lns[k] = pfl_first_lns(hint && hint[s0 + k] != SF_PF_LONG_NO_HINT ? &hint[s0 + k] : nullptr, kT, len[s0 + k]);
+  int n_done = 0;
+  float ms = 0;
+  while (n_done < n) {
+    // inside passes until every row that is not done is in range; only the rows out of range repeat
+    for (;;) {
+      int Ltop = 0;
+      for (int k = 0; k < n; k++) {
+        act[k] = state[k] == PENDING;
+        if (!act[k]) continue;
+        if (attempts[k] >= SF_PFLONG_MAX_ATTEMPTS) return SF_ERR_RANGE;
+        attempts[k]++;
+        const int L = len[s0 + k];
+        Ltop = std::max(Ltop, L);
+        pfl_scale_powers(lns[k], ln_mlbase, L, hpow.data() + pow_off[k], hpow.data() + pow_off[k] + (size_t)L + 2);
+      }
+      if (!Ltop) break;
+      // (the rows that keep their scale keep their powers: the copy writes them the values they have)
+      HIPCHK(hipMemcpyAsync(d_f64 + o_pow, hpow.data(), n_pow * sizeof(double), hipMemcpyHostToDevice, g.stream));
+      HIPCHK(hipMemcpyAsync(d_u8 + o_act, act.data(), (size_t)n, hipMemcpyHostToDevice, g.stream));
+      HIPCHK(hipEventRecord(B.ev[0], g.stream));
+      for (int d = 0; d < Ltop; d++) {
+        const int bps = blocks_per_row(Ltop, d);
+        SF_LAUNCH(sf_pflongb_inside_kernel, n * bps, threads, 0, g.stream, (const SfPfLong *)d_F, d_act, d, bps, (int)lanes, D, X);
+      }
+      HIPCHK(hipGetLastError());
+      SF_LAUNCH(sf_pflongb_exterior_kernel, n, 64, 0, g.stream, (const SfPfLong *)d_F, d_act, D, X);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipEventRecord(B.ev[1], g.stream));
+      HIPCHK(hipMemcpyAsync(hout.data(), d_f64 + o_out, 3 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, g.stream));
+      HIPCHK(hipStreamSynchronize(g.stream));
+      HIPCHK(hipEventElapsedTime(&ms, B.ev[0], B.ev[1]));
+      ms_out[0] += ms;
+      (*passes)++;
+      for (int k = 0; k < n; k++) {
+        if (!act[k]) continue;
+        lz[k] = hout[3 * (size_t)k];
+        if (!isfinite(lz[k]) || fabs(lz[k]) > SF_PF_LNZ_MAX) lns[k] = pfl_next_lns(lns[k], lz[k], len[s0 + k]);
+        else state[k] = READY;
+      }
+    }
+    // the outside pass, the probabilities and their sums of every row in range
+    int Ltop = 0;
+    for (int k = 0; k < n; k++) {
+      act[k] = state[k] == READY;
+      if (act[k]) Ltop = std::max(Ltop, (int)len[s0 + k]);
+    }
+    HIPCHK(hipMemcpyAsync(d_u8 + o_act, act.data(), (size_t)n, hipMemcpyHostToDevice, g.stream));
+    HIPCHK(hipMemsetAsync(d_u8 + o_cen, '.', n_L + (size_t)n, g.stream));  // (the rows done before are on the host already)
+    HIPCHK(hipEventRecord(B.ev[2], g.stream));
+    for (int d = Ltop - 1; d >= SFD_TURN + 1; d--) {
+      const int bps = blocks_per_row(Ltop, d);
+      SF_LAUNCH(sf_pflongb_outside_kernel, n * bps, threads, 0, g.stream, (const SfPfLong *)d_F, d_act, d, bps, (int)lanes, D, X);
+    }
+    HIPCHK(hipGetLastError());
+    const int pbps = (wmax + threads / 64 - 1) / (threads / 64);
+    SF_LAUNCH(sf_pflongb_prob_kernel, n * pbps, threads, 0, g.stream, (const SfPfLong *)d_F, d_act, pbps, (int)lanes);
+    SF_LAUNCH(sf_pflongb_finish_kernel, n, 64, 0, g.stream, (const SfPfLong *)d_F, d_act, (int)lanes);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(B.ev[3], g.stream));
+    HIPCHK(hipMemcpyAsync(hout.data(), d_f64 + o_out, 3 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipMemcpyAsync(hcen.data(), d_u8 + o_cen, n_L + (size_t)n, hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipStreamSynchronize(g.stream));
+    HIPCHK(hipEventElapsedTime(&ms, B.ev[2], B.ev[3]));
+    ms_out[1] += ms;
+    for (int k = 0; k < n; k++) {
+      if (!act[k]) continue;
+      const int L = len[s0 + k];
+      const double *res = hout.data() + 3 * (size_t)k;
+      if (isfinite(res[1]) && isfinite(res[2])) {
+        const double dG = -(res[0] + (double)L * lns[k]) * kT / 1000.0;
+        if (!isfinite(dG)) return SF_ERR_RANGE;
+        sf_pf_long_row &r = rows_host[s0 + k];
+        r.ens_dG = dG;
+        r.mean_bp_dist = res[1];
+        r.centroid_dist = res[2];
+        r.lns = lns[k];
+        r.attempts = attempts[k];
+        r.reserved = 0;
+        if (cen_host) {
+          memcpy(cen_host + cen_off[k], hcen.data() + cen_off[k], (size_t)L);
+          cen_host[cen_off[k] + (size_t)L] = 0;
+        }
+        state[k] = DONE;
+        n_done++;
+      } else {
+        if (fabs(lz[k]) < 1.0) return SF_ERR_RANGE;  // Z_s is centred and the outside tables still leave the range
+        lns[k] += lz[k] / L;
+        state[k] = PENDING;
+      }
+    }
+  }
+  return read_status(g.stream, false);
+}
+}  // namespace
+
+extern "C" {
+
+int sf_pf_long_batch(const uint8_t *seqs, int n, int ld, const int32_t *len, const char *cons, const int32_t *mfe_dcal_hint,
+                     sf_pf_long_row *out, char *centroid_out) {
+  int rc = check_ready();
+  if (rc) return rc;
+  if (n < 0 || (n > 0 && (!seqs || !len))) return SF_ERR_BAD_ARG;
+  for (int k = 0; k < n; k++)
+    if (len[k] < 1 || len[k] > SF_MAX_LONG || len[k] > ld) return SF_ERR_BAD_ARG;
+  if (n == 0) {
+    g_pflb_ms[0] = g_pflb_ms[1] = 0.0;
+    g_pflb_chunks = g_pflb_passes = 0;
+    return SF_OK;
+  }
+  // every constraint row is looked at before anything is launched: a row of dots is no constraint
+  std::vector<char> constrained((size_t)n, 0);
+  if (cons)
+    for (int k = 0; k < n; k++) {
+      const char *c = cons + (size_t)k * ld;
+      bool any = false, noncanonical = false;
+      for (int x = 0; x < len[k] && !any; x++) any = c[x] != '.';
+      if (!any) continue;
+      if ((rc = scan_constraints(seqs + (size_t)k * ld, c, 1, len[k], &noncanonical))) return rc;
+      constrained[k] = 1;
+    }
+  // results are staged and handed over only when every chunk has succeeded (they outlive the chunks' device buffers)
+  std::vector<sf_pf_long_row> rows_host((size_t)n);
+  std::vector<char> cen_host;
+  if (centroid_out) {
+    size_t total = 0;
+    for (int k = 0; k < n; k++) total += (size_t)len[k] + 1;
+    cen_host.resize(total);
+  }
+  double ms[2] = {0, 0};
+  int chunks = 0, passes = 0;
+  size_t cen_off = 0;
+  for (int s0 = 0; s0 < n;) {
+    size_t bytes = 0, cen_bytes = 0;
+    int m = 0;
+    while (s0 + m < n && m < kLongBatchMaxSeqs) {
+      const size_t b = SF_PFLONG_BYTES(len[s0 + m]);
+      if (m > 0 && bytes + b > g_longb_bytes) break;
+      bytes += b;
+      cen_bytes += (size_t)len[s0 + m] + 1;
+      m++;
+    }
+    if ((rc = pf_long_batch_chunk(seqs, ld, len, cons, constrained, mfe_dcal_hint, s0, m, rows_host.data(),
+                                  centroid_out ? cen_host.data() + cen_off : nullptr, ms, &passes)))
+      return rc;
+    cen_off += cen_bytes;
+    s0 += m;
+    chunks++;
+  }
+  if (out) memcpy(out, rows_host.data(), (size_t)n * sizeof(sf_pf_long_row));
+  if (centroid_out) {
+    size_t off = 0;
+    for (int k = 0; k < n; k++) {
+      memcpy(centroid_out + (size_t)k * ((size_t)ld + 1), cen_host.data() + off, (size_t)len[k] + 1);
+      off += (size_t)len[k] + 1;
+    }
+  }
+  g_pflb_ms[0] = ms[0];
+  g_pflb_ms[1] = ms[1];
+  g_pflb_chunks = chunks;
+  g_pflb_passes = passes;
+  return SF_OK;
+}
+
+int sf_pf_long_batch_times(double *inside_ms, double *outside_ms, int *chunks, int *inside_passes) {
+  SF_ENTER();
+  if (inside_ms) *inside_ms = g_pflb_ms[0];
+  if (outside_ms) *outside_ms = g_pflb_ms[1];
+  if (chunks) *chunks = g_pflb_chunks;
+  if (inside_passes) *inside_passes = g_pflb_passes;
   return SF_OK;
 }
 

@@ -20,7 +20,7 @@
 // Launches.  One launch per anti-diagonal d = j - i, ascending for the inside pass and descending for the outside pass: all
 // ordering between workgroups comes from kernel boundaries (no grid barrier, no floating-point atomics).  A cell is handled
 // by a group of G lanes (a power of two <= 64) which take its terms round-robin and add their partial sums in a butterfly of
-// __shfl_xor.  The host sizes G so that cells * G fills the lane budget of the device (SF_PFLONG_LANES_PER_CU per compute unit: a
+// __shfl_xor.  pfl_group below (host and device: sf_pf_long_batch.hip.h calls it per row) sizes G so that cells * G fills the lane budget of the device (SF_PFLONG_LANES_PER_CU per compute unit: a
 // compile-time figure, smaller in the CPU emulation build of the tests, which pays per lane) and lets a group walk several cells where the diagonal has more
 // cells than the budget has groups.  G is a function of L, d and the device's number of compute units only, so two calls on the same input on
 // the same device add in the same order and return bit-identical doubles.  q5 / q3 are sequential in j / i: one wave each, reducing over the other index.
@@ -87,13 +87,28 @@ __device__ __forceinline__ double sfpl_group_sum(double v, int G) {
   return v;
 }
 
-// Diagonal d of the inside pass.  Lane r = t % G of group t / G; a group takes cells group, group + ngroups, ...
-__global__ void sf_pflong_inside_kernel(SfPfLong F, int d, int G, const SfDevParams *__restrict__ D,
-                                     const SfDevParamsPF *__restrict__ X) {
+// lanes per cell of a diagonal with `cells` cells whose longest sum has `terms` terms: fill the lane budget, at most one wave,
+// and no more lanes than leave each some sixteen terms (four lanes for the interior loops of a short diagonal).  The host
+// (sf_pf_long) and the batched kernels (sf_pf_long_batch.hip.h) both size a group with this one function.
+__host__ __device__ inline int pfl_group(size_t cells, int terms, size_t lanes) {
+  int G = 1;
+  while (G < 64 && (size_t)(2 * G) * cells <= lanes && 32 * G <= (terms > 64 ? terms : 64)) G *= 2;
+  return G;
+}
+// waves of the probability pass of a sequence of L nt under a budget of `lanes` lanes: one per row of the triangle at most
+__host__ __device__ inline int pfl_prob_waves(int L, size_t lanes) {
+  return (size_t)L < lanes / 64 ? L : (int)(lanes / 64);
+}
+
+// The five passes below are functions of (F, the lane's position gt within its sequence's share of the launch, the share's
+// size nl): the kernels of this file give a sequence the whole launch, those of sf_pf_long_batch.hip.h a run of workgroups.
+
+// Diagonal d of the inside pass.  Lane r = gt % G of group gt / G; a group takes cells group, group + ngroups, ...
+__device__ __forceinline__ void sfpl_inside(const SfPfLong &F, int d, int G, size_t gt, size_t nl, const SfDevParams *__restrict__ D,
+                                            const SfDevParamsPF *__restrict__ X) {
   const int L = F.L;
-  const size_t gt = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int r = (int)(gt % (size_t)G);
-  const size_t group = gt / (size_t)G, ngroups = (size_t)gridDim.x * blockDim.x / (size_t)G;
+  const size_t group = gt / (size_t)G, ngroups = nl / (size_t)G;
   const size_t ncell = (size_t)(L - d);
   const size_t rounds = (ncell + ngroups - 1) / ngroups;  // the same for every lane: the butterflies stay convergent
   for (size_t it = 0; it < rounds; it++) {
@@ -173,10 +188,15 @@ __global__ void sf_pflong_inside_kernel(SfPfLong F, int d, int G, const SfDevPar
     }
   }
 }
+__global__ void sf_pflong_inside_kernel(SfPfLong F, int d, int G, const SfDevParams *__restrict__ D,
+                                     const SfDevParamsPF *__restrict__ X) {
+  sfpl_inside(F, d, G, (size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x, D, X);
+}
 
 // q5[j] = q5[j-1] / s + sum_i q5[i-1] qb[i][j] ext(i, j), then q3 mirrored; one wave, which reads column j (row i) of qb
 // contiguously and adds in a butterfly.  out[0] = ln Z_s.
-__global__ void sf_pflong_exterior_kernel(SfPfLong F, const SfDevParams *__restrict__ D, const SfDevParamsPF *__restrict__ X) {
+__device__ __forceinline__ void sfpl_exterior(const SfPfLong &F, const SfDevParams *__restrict__ D,
+                                              const SfDevParamsPF *__restrict__ X) {
   const int tid = threadIdx.x, nt = blockDim.x, L = F.L;  // nt == 64
   if (tid == 0) { F.q5[0] = 1.0; F.q3[L + 1] = 1.0; }
   __syncthreads();
@@ -208,14 +228,16 @@ __global__ void sf_pflong_exterior_kernel(SfPfLong F, const SfDevParams *__restr
   }
   if (tid == 0) F.out[0] = log(F.q5[L]);
 }
+__global__ void sf_pflong_exterior_kernel(SfPfLong F, const SfDevParams *__restrict__ D, const SfDevParamsPF *__restrict__ X) {
+  sfpl_exterior(F, D, X);
+}
 
 // Diagonal d of the outside pass (d descending from L-1 to TURN+1); groups and rounds as in the inside pass.
-__global__ void sf_pflong_outside_kernel(SfPfLong F, int d, int G, const SfDevParams *__restrict__ D,
-                                      const SfDevParamsPF *__restrict__ X) {
+__device__ __forceinline__ void sfpl_outside(const SfPfLong &F, int d, int G, size_t gt, size_t nl, const SfDevParams *__restrict__ D,
+                                             const SfDevParamsPF *__restrict__ X) {
   const int L = F.L;
-  const size_t gt = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int r = (int)(gt % (size_t)G);
-  const size_t group = gt / (size_t)G, ngroups = (size_t)gridDim.x * blockDim.x / (size_t)G;
+  const size_t group = gt / (size_t)G, ngroups = nl / (size_t)G;
   const size_t ncell = (size_t)(L - d);
   const size_t rounds = (ncell + ngroups - 1) / ngroups;
   const int mpd = D->max_pair_dist;
@@ -299,12 +321,15 @@ __global__ void sf_pflong_outside_kernel(SfPfLong F, int d, int G, const SfDevPa
     }
   }
 }
+__global__ void sf_pflong_outside_kernel(SfPfLong F, int d, int G, const SfDevParams *__restrict__ D,
+                                      const SfDevParamsPF *__restrict__ X) {
+  sfpl_outside(F, d, G, (size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x, D, X);
+}
 
 // p = ob qb / Z_s over every cell: the centroid's pairs (p > 0.5) and each wave's share of sum p(1-p) and of the centroid
 // distance, into part[2 * wave]; a wave takes rows wave, wave + nwaves, ... and reads them contiguously.
-__global__ void sf_pflong_prob_kernel(SfPfLong F) {
+__device__ __forceinline__ void sfpl_prob(const SfPfLong &F, size_t wave, size_t nwaves) {
   const int L = F.L, lane = threadIdx.x & 63;
-  const size_t wave = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = ((size_t)gridDim.x * blockDim.x) >> 6;
   const double Z = F.q5[L];
   double mbd = 0.0, cd = 0.0;
   for (size_t i = wave + 1; i <= (size_t)L; i += nwaves) {
@@ -325,9 +350,12 @@ __global__ void sf_pflong_prob_kernel(SfPfLong F) {
   cd = sfpl_group_sum(cd, 64);
   if (lane == 0) { F.part[2 * wave] = mbd; F.part[2 * wave + 1] = cd; }
 }
+__global__ void sf_pflong_prob_kernel(SfPfLong F) {
+  sfpl_prob(F, ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, ((size_t)gridDim.x * blockDim.x) >> 6);
+}
 
 // The partial sums in wave order; one wave.
-__global__ void sf_pflong_finish_kernel(SfPfLong F, int nwaves) {
+__device__ __forceinline__ void sfpl_finish(const SfPfLong &F, int nwaves) {
   const int tid = threadIdx.x;
   double mbd = 0.0, cd = 0.0;
   for (int w = tid; w < nwaves; w += 64) { mbd += F.part[2 * w]; cd += F.part[2 * w + 1]; }
@@ -335,3 +363,4 @@ __global__ void sf_pflong_finish_kernel(SfPfLong F, int nwaves) {
   cd = sfpl_group_sum(cd, 64);
   if (tid == 0) { F.out[1] = 2.0 * mbd; F.out[2] = cd; }
 }
+__global__ void sf_pflong_finish_kernel(SfPfLong F, int nwaves) { sfpl_finish(F, nwaves); }

@@ -163,8 +163,9 @@ def global_refold(seq, name, outname, temperature, dbn_file_path="AllDBN-global_
     there, so no constraint) to the record's length.
     The engine's model (base-pair span, temperature, and the RNA facade's record of the span) is put back exactly as it
     was, also when a fold raises: the stages after this one, and the next records, fold as they would without the flag.
-    ensemble (--global_ensemble, not upstream): the partition function of the same three folds (Engine.pf_long, scaled from
-    each fold's MFE) into `<outname>.<dbn_file_path minus .txt>.ensemble.txt`, three records of a header line (ensemble free
+    ensemble (--global_ensemble, not upstream): the partition function of the same three folds (one Engine.pf_long_batch
+    call past SF_MAX_W where the library has it, else Engine.pf_long three times: the same numbers; scaled from each fold's
+    MFE) into `<outname>.<dbn_file_path minus .txt>.ensemble.txt`, three records of a header line (ensemble free
     energy, ED = mean base-pair distance to 2 decimals, centroid distance), the sequence and the centroid."""
     from . import RNA
     md = RNA.md()
@@ -188,7 +189,10 @@ def global_refold(seq, name, outname, temperature, dbn_file_path="AllDBN-global_
         s2, e2 = fc.mfe()
         s0, e0 = RNA.fold_compound(seq, md).mfe()
         ens = []
-        if ensemble:
+        if ensemble and len(seq) > _lib.SF_MAX_W and eng.has_pf_long_batch():
+            # the three ensembles in the same launches; each row is pf_long's bit for bit
+            ens = eng.pf_long_batch([seq] * 3, [None, cons[0], cons[1]], [int(round(e * 100)) for e in (e0, e1, e2)])
+        elif ensemble:
             for c, e in ((None, e0), (cons[0], e1), (cons[1], e2)):
                 if len(seq) > _lib.SF_MAX_W:
                     ens.append(eng.pf_long(seq, c, mfe_hint=int(round(e * 100))))
