@@ -1104,6 +1104,155 @@ int long_group(int d) {
   while (G < 64 && G * 64 < d) G *= 2;
   return G;
 }
+
+// What sf_fold_long_batch and sf_pf_long_batch share: the rows of a call, their checks, the walk over chunks, and the head
+// of a chunk's byte block.
+const size_t kLongBatchBytesDefault = (size_t)8 << 30;  // device memory one chunk's tables may take
+const int kLongBatchMaxSeqs = 1 << 15;                  // sequences per chunk: keeps every grid far inside an int
+size_t g_longb_bytes = kLongBatchBytesDefault;
+
+// The rows of one batched call.
+struct LongRows {
+  const uint8_t *seqs;
+  int n, ld;
+  const int32_t *len;
+  const char *cons;               // NULL, or n rows of ld characters
+  const char *who;                // the entry point the caller used
+  std::vector<char> constrained;  // per row: it has a constraint (made by long_rows_check)
+};
+
+// The argument checks both batch entry points make, and a look at every constraint row before anything is launched: a row of
+// dots is no constraint.
+int long_rows_check(LongRows &R) {
+  if (R.n < 0 || (R.n > 0 && (!R.seqs || !R.len))) return SF_ERR_BAD_ARG;
+  for (int k = 0; k < R.n; k++)
+    if (R.len[k] < 1 || R.len[k] > SF_MAX_LONG || R.len[k] > R.ld) return SF_ERR_BAD_ARG;
+  R.constrained.assign((size_t)R.n, 0);
+  if (R.cons)
+    for (int k = 0; k < R.n; k++) {
+      const char *c = R.cons + (size_t)k * R.ld;
+      bool any = false, noncanonical = false;  // (a type-7 bracket pair needs nothing special here: the tables carry it)
+      for (int x = 0; x < R.len[k] && !any; x++) any = c[x] != '.';
+      if (!any) continue;
+      const int rc = scan_constraints(R.seqs + (size_t)k * R.ld, c, 1, R.len[k], &noncanonical);
+      if (rc) return rc;
+      R.constrained[k] = 1;
+    }
+  return SF_OK;
+}
+
+// Walks the rows in chunks: as many consecutive rows as fit the byte budget at row_bytes(L) each, always at least one.
+// chunk(s0, m, str) works on rows s0 .. s0 + m - 1 and leaves their strings (structures, centroids) back to back at str,
+// L + 1 bytes each; str is NULL when str_out is.  The strings are staged here (they outlive the chunks' device buffers) and
+// reach str_out, n rows of ld + 1 bytes, only when every chunk has succeeded.
+template <class Chunk>
+int long_for_chunks(const LongRows &R, size_t (*row_bytes)(int), char *str_out, int *chunks, Chunk chunk) {
+  std::vector<char> str;
+  if (str_out) {
+    size_t total = 0;
+    for (int k = 0; k < R.n; k++) total += (size_t)R.len[k] + 1;
+    str.resize(total);
+  }
+  size_t off = 0;
+  *chunks = 0;
+  for (int s0 = 0; s0 < R.n;) {
+    size_t bytes = 0, str_bytes = 0;
+    int m = 0;
+    while (s0 + m < R.n && m < kLongBatchMaxSeqs) {
+      const size_t b = row_bytes(R.len[s0 + m]);
+      if (m > 0 && bytes + b > g_longb_bytes) break;
+      bytes += b;
+      str_bytes += (size_t)R.len[s0 + m] + 1;
+      m++;
+    }
+    const int rc = chunk(s0, m, str_out ? str.data() + off : nullptr);
+    if (rc) return rc;
+    off += str_bytes;
+    s0 += m;
+    (*chunks)++;
+  }
+  off = 0;
+  if (str_out)
+    for (int k = 0; k < R.n; k++) {
+      memcpy(str_out + (size_t)k * ((size_t)R.ld + 1), str.data() + off, (size_t)R.len[k] + 1);
+      off += (size_t)R.len[k] + 1;
+    }
+  return SF_OK;
+}
+
+// The head of a chunk's byte block, the same in both families: every row's sequence (codes, zero on both sides: L + 2 bytes),
+// then the constraint rows as given, then their parsed form (L + 2 each); a family's own bytes follow from o_end.
+struct LongPack {
+  int Lmax = 0, n_hc = 0;
+  size_t n_L = 0, n_hcL = 0;  // nucleotides of all rows, of the constrained rows
+  size_t o_src, o_hc, o_end;
+  std::vector<uint8_t> h8;    // sequences and constraint rows, copied up in one piece
+};
+
+LongPack long_pack(const LongRows &R, int s0, int n) {
+  LongPack K;
+  for (int k = 0; k < n; k++) {
+    const int L = R.len[s0 + k];
+    K.Lmax = std::max(K.Lmax, L);
+    K.n_L += (size_t)L;
+    if (R.constrained[s0 + k]) { K.n_hc++; K.n_hcL += (size_t)L; }
+  }
+  K.o_src = K.n_L + 2 * (size_t)n;
+  K.o_hc = K.o_src + K.n_hcL;
+  K.o_end = K.o_hc + K.n_hcL + 2 * (size_t)K.n_hc;
+  K.h8.assign(K.o_hc, 0);
+  size_t a_L = 0, a_hcL = 0;
+  for (int k = 0; k < n; k++) {
+    const int L = R.len[s0 + k];
+    const uint8_t *row = R.seqs + (size_t)(s0 + k) * R.ld;
+    uint8_t *hS = K.h8.data() + a_L + 2 * (size_t)k;
+    for (int x = 0; x < L; x++) hS[x + 1] = sf_encode_nt(row[x]);
+    if (R.constrained[s0 + k]) {
+      memcpy(K.h8.data() + K.o_src + a_hcL, R.cons + (size_t)(s0 + k) * R.ld, (size_t)L);
+      a_hcL += (size_t)L;
+    }
+    a_L += (size_t)L;
+  }
+  return K;
+}
+
+// Clears the chunk's row states (SfLong or SfPfLong) and sets what both have: L, S and hc.  Copies the packed bytes to
+// d_u8, allocates the int16 block of the constrained rows (bracket partners, enclosing pairs, parse stack: L + 2 each) and
+// parses each of them on the device.
+template <class State>
+int long_bind_rows(LongBufs &B, const LongPack &K, const LongRows &R, int s0, uint8_t *d_u8, std::vector<State> &hF) {
+  int16_t *d_i16 = nullptr;
+  if (K.n_hc) {
+    void *p;
+    const int rc = B.alloc(&p, 3 * (K.n_hcL + 2 * (size_t)K.n_hc) * sizeof(int16_t), "bracket partners");
+    if (rc) return rc;
+    d_i16 = (int16_t *)p;
+  }
+  HIPCHK(hipMemcpyAsync(d_u8, K.h8.data(), K.h8.size(), hipMemcpyHostToDevice, g.stream));
+  size_t a_L = 0, a_hcL = 0;
+  int a_hc = 0;
+  for (size_t k = 0; k < hF.size(); k++) {
+    const int L = R.len[s0 + k];
+    State &F = hF[k];
+    memset(&F, 0, sizeof F);
+    F.L = L;
+    F.S = d_u8 + a_L + 2 * k;
+    if (R.constrained[s0 + k]) {
+      int16_t *partner = d_i16 + 3 * (a_hcL + 2 * (size_t)a_hc), *encl = partner + (size_t)L + 2, *stack = encl + (size_t)L + 2;
+      char *c = (char *)d_u8 + K.o_hc + a_hcL + 2 * (size_t)a_hc;
+      SF_LAUNCH(sf_long_hc_kernel, 1, 64, 0, g.stream, (const char *)d_u8 + K.o_src + a_hcL, L, c, partner, encl, stack,
+                (int *)g.status.p);
+      F.hc.c = c;
+      F.hc.partner = partner;
+      F.hc.encl = encl;
+      a_hcL += (size_t)L;
+      a_hc++;
+    }
+    a_L += (size_t)L;
+  }
+  HIPCHK(hipGetLastError());
+  return SF_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1209,49 +1358,39 @@ int sf_fold_long_times(double *fill_ms, double *f5_ms, double *trace_ms) {
 
 // ---------------- many whole-record folds at once (sf_mfe_long_batch.hip.h) ----------------
 namespace {
-const size_t kLongBatchBytesDefault = (size_t)8 << 30;  // device memory one chunk's tables may take
-const int kLongBatchMaxSeqs = 1 << 15;                  // sequences per chunk: keeps every grid far inside an int
-size_t g_longb_bytes = kLongBatchBytesDefault;
 double g_longb_ms[3] = {0, 0, 0};  // fill, f5, traceback of the last sf_fold_long_batch, summed over its chunks
 int g_longb_chunks = 0;
 
 size_t long_batch_seq_bytes(int L) { return 12 * SF_LONG_TRI(L) + 80 * (size_t)L; }
 
-// Sequences s0 .. s0 + n - 1 of the batch as one chunk.  e_host / db_host: the caller's staging buffers (the chunk's energies
-// at e_host[s0 ..], its structures back to back, L + 1 bytes each, from db_host[db_off]); they hold the results once the
-// stream has drained, which read_status below waits for.
-int long_batch_chunk(const uint8_t *seqs, int ld, const int32_t *len, const char *cons, const std::vector<char> &constrained,
-                     int s0, int n, int32_t *e_host, char *db_host, double ms_out[3]) {
+// Sequences s0 .. s0 + n - 1 as one chunk.  e_host / db_host: the caller's staging buffers (the chunk's energies at
+// e_host[s0 ..], its structures back to back, L + 1 bytes each, at db_host, or NULL: no traceback); they hold the results
+// once the stream has drained, which read_status below waits for.
+int long_batch_chunk(const LongRows &R, int s0, int n, int32_t *e_host, char *db_host, double ms_out[3]) {
   int rc;
   const sf_params_blob *P = (const sf_params_blob *)g.slot[g.cur].src.data();  // the resident set as it was handed in
-  int Lmax = 0, n_hc = 0;
-  size_t tri = 0, n_L = 0, n_hcL = 0, n_stk = 0;
+  const LongPack K = long_pack(R, s0, n);
+  const int Lmax = K.Lmax;
+  const size_t n_L = K.n_L;
+  size_t tri = 0, n_stk = 0;
   for (int k = 0; k < n; k++) {
-    const int L = len[s0 + k];
-    Lmax = std::max(Lmax, L);
-    tri += SF_LONG_TRI(L);
-    n_L += (size_t)L;
-    n_stk += SF_LONG_STACK_INTS(L);
-    if (constrained[s0 + k]) { n_hc++; n_hcL += (size_t)L; }
+    tri += SF_LONG_TRI(R.len[s0 + k]);
+    n_stk += SF_LONG_STACK_INTS(R.len[s0 + k]);
   }
   const bool trace = db_host != nullptr;
-  // slices of the int32 / int16 / byte allocations, in elements
+  // slices of the int32 allocation, in elements; the structures follow the packed rows in the byte block
   const size_t o_hp = 0, o_mfe = o_hp + (size_t)Lmax + 1, o_f5 = o_mfe + (size_t)n, o_stk = o_f5 + n_L + (size_t)n;
   const size_t n_i32 = o_stk + (trace ? n_stk : 0);
-  const size_t n_i16 = 3 * (n_hcL + 2 * (size_t)n_hc);                     // partner, encl, stack: L + 2 each
-  const size_t o_S = 0, o_src = o_S + n_L + 2 * (size_t)n, o_hc = o_src + n_hcL, o_db = o_hc + n_hcL + 2 * (size_t)n_hc;
-  const size_t n_u8 = o_db + (trace ? n_L + (size_t)n : 0);
+  const size_t o_db = K.o_end, n_u8 = o_db + (trace ? n_L + (size_t)n : 0);
 
-  std::vector<uint8_t> h8(o_hc, 0);  // sequences (codes, zero on both sides) and constraint rows, copied up in one piece
   std::vector<int32_t> hhp((size_t)Lmax + 1);
   for (int s = 0; s <= Lmax; s++) hhp[s] = (s <= 30) ? P->hairpin[s] : P->hairpin[30] + (int)(P->lxc * log(s / 30.));
   std::vector<SfLong> hF((size_t)n);
 
   LongBufs B;
-  B.who = "sf_fold_long_batch";
+  B.who = R.who;
   void *p;
   int32_t *d_c, *d_fML, *d_fMLt, *d_dml, *d_i32;
-  int16_t *d_i16 = nullptr;
   uint8_t *d_u8;
   SfLong *d_F;
   if ((rc = B.alloc(&p, tri * sizeof(int32_t), "c"))) return rc;
@@ -1264,26 +1403,16 @@ int long_batch_chunk(const uint8_t *seqs, int ld, const int32_t *len, const char
   d_dml = (int32_t *)p;
   if ((rc = B.alloc(&p, n_i32 * sizeof(int32_t), "hairpin table, energies, f5, traceback stacks"))) return rc;
   d_i32 = (int32_t *)p;
-  if (n_i16) {
-    if ((rc = B.alloc(&p, n_i16 * sizeof(int16_t), "bracket partners"))) return rc;
-    d_i16 = (int16_t *)p;
-  }
   if ((rc = B.alloc(&p, n_u8, "sequences, constraints, structures"))) return rc;
   d_u8 = (uint8_t *)p;
   if ((rc = B.alloc(&p, (size_t)n * sizeof(SfLong), "fold states"))) return rc;
   d_F = (SfLong *)p;
+  if ((rc = long_bind_rows(B, K, R, s0, d_u8, hF))) return rc;
 
-  size_t a_tri = 0, a_L = 0, a_hcL = 0, a_stk = 0;
-  int a_hc = 0;
+  size_t a_tri = 0, a_L = 0, a_stk = 0;
   for (int k = 0; k < n; k++) {
-    const int L = len[s0 + k];
-    const uint8_t *row = seqs + (size_t)(s0 + k) * ld;
-    uint8_t *hS = h8.data() + o_S + a_L + 2 * (size_t)k;
-    for (int x = 0; x < L; x++) hS[x + 1] = sf_encode_nt(row[x]);
+    const int L = R.len[s0 + k];
     SfLong &F = hF[k];
-    memset(&F, 0, sizeof F);
-    F.L = L;
-    F.S = d_u8 + o_S + a_L + 2 * (size_t)k;
     F.hp = d_i32 + o_hp;
     F.c = d_c + a_tri;
     F.fML = d_fML + a_tri;
@@ -1295,31 +1424,12 @@ int long_batch_chunk(const uint8_t *seqs, int ld, const int32_t *len, const char
       F.stk = d_i32 + o_stk + a_stk;
       F.db = (char *)d_u8 + o_db + a_L + (size_t)k;
     }
-    if (constrained[s0 + k]) {
-      memcpy(h8.data() + o_src + a_hcL, cons + (size_t)(s0 + k) * ld, (size_t)L);
-      const size_t o16 = 3 * (a_hcL + 2 * (size_t)a_hc);
-      F.hc.c = (const char *)d_u8 + o_hc + a_hcL + 2 * (size_t)a_hc;
-      F.hc.partner = d_i16 + o16;
-      F.hc.encl = d_i16 + o16 + (size_t)L + 2;
-      a_hcL += (size_t)L;
-      a_hc++;
-    }
     a_tri += SF_LONG_TRI(L);
     a_L += (size_t)L;
     a_stk += SF_LONG_STACK_INTS(L);
   }
-  HIPCHK(hipMemcpyAsync(d_u8, h8.data(), h8.size(), hipMemcpyHostToDevice, g.stream));
   HIPCHK(hipMemcpyAsync(d_i32 + o_hp, hhp.data(), hhp.size() * sizeof(int32_t), hipMemcpyHostToDevice, g.stream));
   HIPCHK(hipMemcpyAsync(d_F, hF.data(), (size_t)n * sizeof(SfLong), hipMemcpyHostToDevice, g.stream));
-  a_hcL = 0;
-  for (int k = 0; k < n; k++) {  // the bracket partners and enclosing pairs of every constrained row
-    if (!constrained[s0 + k]) continue;
-    const SfLong &F = hF[k];
-    SF_LAUNCH(sf_long_hc_kernel, 1, 64, 0, g.stream, (const char *)d_u8 + o_src + a_hcL, F.L, (char *)F.hc.c,
-              (int16_t *)F.hc.partner, (int16_t *)F.hc.encl, (int16_t *)F.hc.encl + (size_t)F.L + 2, (int *)g.status.p);
-    a_hcL += (size_t)F.L;
-  }
-  HIPCHK(hipGetLastError());
 
   for (auto &e : B.ev) HIPCHK(hipEventCreate(&e));
   const SfDevParams *D = (const SfDevParams *)g.dP;
@@ -1359,61 +1469,18 @@ extern "C" {
 int sf_fold_long_batch(const uint8_t *seqs, int n, int ld, const int32_t *len, const char *cons, int32_t *mfe_out, char *db_out) {
   int rc = check_ready();
   if (rc) return rc;
-  if (n < 0 || (n > 0 && (!seqs || !len || !mfe_out))) return SF_ERR_BAD_ARG;
-  for (int k = 0; k < n; k++)
-    if (len[k] < 1 || len[k] > SF_MAX_LONG || len[k] > ld) return SF_ERR_BAD_ARG;
-  if (n == 0) {
-    for (int k = 0; k < 3; k++) g_longb_ms[k] = 0.0;
-    g_longb_chunks = 0;
-    return SF_OK;
-  }
-  // every constraint row is looked at before anything is launched: a row of dots is no constraint
-  std::vector<char> constrained((size_t)n, 0);
-  if (cons)
-    for (int k = 0; k < n; k++) {
-      const char *c = cons + (size_t)k * ld;
-      bool any = false, noncanonical = false;
-      for (int x = 0; x < len[k] && !any; x++) any = c[x] != '.';
-      if (!any) continue;
-      if ((rc = scan_constraints(seqs + (size_t)k * ld, c, 1, len[k], &noncanonical))) return rc;
-      constrained[k] = 1;
-    }
-  // results are staged and handed over only when every chunk has succeeded (they outlive the chunks' device buffers)
+  if (n > 0 && !mfe_out) return SF_ERR_BAD_ARG;
+  LongRows R = {seqs, n, ld, len, cons, "sf_fold_long_batch"};
+  if ((rc = long_rows_check(R))) return rc;
+  // the energies are staged and handed over, like the structures, only when every chunk has succeeded
   std::vector<int32_t> e_host((size_t)n);
-  std::vector<char> db_host;
-  if (db_out) {
-    size_t total = 0;
-    for (int k = 0; k < n; k++) total += (size_t)len[k] + 1;
-    db_host.resize(total);
-  }
   double ms[3] = {0, 0, 0};
-  int chunks = 0;
-  size_t db_off = 0;
-  for (int s0 = 0; s0 < n;) {
-    size_t bytes = 0, db_bytes = 0;
-    int m = 0;
-    while (s0 + m < n && m < kLongBatchMaxSeqs) {
-      const size_t b = long_batch_seq_bytes(len[s0 + m]);
-      if (m > 0 && bytes + b > g_longb_bytes) break;
-      bytes += b;
-      db_bytes += (size_t)len[s0 + m] + 1;
-      m++;
-    }
-    if ((rc = long_batch_chunk(seqs, ld, len, cons, constrained, s0, m, e_host.data(), db_out ? db_host.data() + db_off : nullptr,
-                               ms)))
-      return rc;
-    db_off += db_bytes;
-    s0 += m;
-    chunks++;
-  }
-  memcpy(mfe_out, e_host.data(), (size_t)n * sizeof(int32_t));
-  if (db_out) {
-    size_t off = 0;
-    for (int k = 0; k < n; k++) {
-      memcpy(db_out + (size_t)k * ((size_t)ld + 1), db_host.data() + off, (size_t)len[k] + 1);
-      off += (size_t)len[k] + 1;
-    }
-  }
+  int chunks;
+  rc = long_for_chunks(R, long_batch_seq_bytes, db_out, &chunks, [&](int s0, int m, char *db_host) {
+    return long_batch_chunk(R, s0, m, e_host.data(), db_host, ms);
+  });
+  if (rc) return rc;  // (n == 0: no chunk)
+  if (n) memcpy(mfe_out, e_host.data(), (size_t)n * sizeof(int32_t));
   for (int k = 0; k < 3; k++) g_longb_ms[k] = ms[k];
   g_longb_chunks = chunks;
   return SF_OK;
@@ -1634,52 +1701,51 @@ namespace {
 double g_pflb_ms[2] = {0, 0};  // inside passes (q5 / q3 included), outside and probability passes of the last sf_pf_long_batch
 int g_pflb_chunks = 0, g_pflb_passes = 0;
 
-// Rows s0 .. s0 + n - 1 of the batch as one chunk.  rows_host / cen_host: the caller's staging buffers (the chunk's records at
-// rows_host[s0 ..], its centroids back to back, L + 1 bytes each, from cen_host).  ms_out: inside, outside; *passes: inside
-// passes run.  A fixed number of device allocations whatever n is; all freed on return.
-int pf_long_batch_chunk(const uint8_t *seqs, int ld, const int32_t *len, const char *cons, const std::vector<char> &constrained,
-                        const int32_t *hint, int s0, int n, sf_pf_long_row *rows_host, char *cen_host, double ms_out[2],
-                        int *passes) {
+size_t pf_long_row_bytes(int L) { return SF_PFLONG_BYTES(L); }
+
+// Rows s0 .. s0 + n - 1 as one chunk.  hint: NULL, or one value per row of the call (SF_PF_LONG_NO_HINT: none).  rows_host /
+// cen_host: the caller's staging buffers (the chunk's records at rows_host[s0 ..], its centroids back to back, L + 1 bytes
+// each, at cen_host, or NULL).  ms_out: inside, outside; *passes: inside passes run.  A fixed number of device allocations
+// whatever n is; all freed on return.
+int pf_long_batch_chunk(const LongRows &R, const int32_t *hint, int s0, int n, sf_pf_long_row *rows_host, char *cen_host,
+                        double ms_out[2], int *passes) {
   int rc;
   const sf_params_blob *P = (const sf_params_blob *)g.slot[g.cur].src.data();  // the resident set as it was handed in
-  const Ctx::ModelSlot &M = g.slot[g.cur];
+  const Ctx::ModelSlot &M = g.slot[g.cur];  // its host copies of kT, MLbase and the hairpin initiation weight at 30
   const double kT = M.pf_kT, ln_mlbase = log(M.pf_MLbase);
   // the budget of ONE sf_pf_long call: it sizes every row's lane groups and probability waves, whatever the batch holds
   const size_t lanes = (size_t)(g.n_cu > 0 ? g.n_cu : 1) * SF_PFLONG_LANES_PER_CU;
-  const size_t budget = (size_t)(g.n_cu > 0 ? g.n_cu : 1) * SF_PFLONGB_LANES_PER_CU;  // the batch's own, per launch
-  int Lmax = 0, n_hc = 0, wmax = 0;
-  size_t tri = 0, n_L = 0, n_hcL = 0, n_part = 0;
+  const size_t budget = (size_t)(g.n_cu > 0 ? g.n_cu : 1) * SF_PFLONGB_LANES_PER_CU;  // the chunk's own, per launch
+  const LongPack K = long_pack(R, s0, n);
+  const int Lmax = K.Lmax;
+  const size_t n_L = K.n_L;
+  int wmax = 0;
+  size_t tri = 0, n_part = 0;
   for (int k = 0; k < n; k++) {
-    const int L = len[s0 + k];
-    Lmax = std::max(Lmax, L);
+    const int L = R.len[s0 + k];
     tri += SF_LONG_TRI(L);
-    n_L += (size_t)L;
     const int w = pfl_prob_waves(L, lanes);
     wmax = std::max(wmax, w);
     n_part += 2 * (size_t)w;
-    if (constrained[s0 + k]) { n_hc++; n_hcL += (size_t)L; }
   }
-  // slices of the FP64 / int16 / byte allocations, in elements.  FP64: the results first (one copy reads every row's), then
-  // the powers of every row's scale (one copy writes them), the shared hairpin table, q5, q3 and the partial sums.
+  // slices of the FP64 allocation, in elements: the results first (one copy reads every row's), then the powers of every
+  // row's scale (one copy writes them), the shared hairpin table, q5, q3 and the partial sums.  The centroids and the row
+  // marks follow the packed rows in the byte block.
   const size_t o_out = 0, o_pow = o_out + 3 * (size_t)n, n_pow = 2 * (n_L + 2 * (size_t)n), o_hp = o_pow + n_pow;
   const size_t o_q5 = o_hp + (size_t)Lmax + 1, o_q3 = o_q5 + n_L + 2 * (size_t)n, o_part = o_q3 + n_L + 3 * (size_t)n;
   const size_t n_f64 = o_part + n_part;
-  const size_t n_i16 = 3 * (n_hcL + 2 * (size_t)n_hc);  // partner, encl, stack: L + 2 each
-  const size_t o_S = 0, o_src = o_S + n_L + 2 * (size_t)n, o_hc = o_src + n_hcL, o_cen = o_hc + n_hcL + 2 * (size_t)n_hc;
-  const size_t o_act = o_cen + n_L + (size_t)n, n_u8 = o_act + (size_t)n;
+  const size_t o_cen = K.o_end, o_act = o_cen + n_L + (size_t)n, n_u8 = o_act + (size_t)n;
 
-  std::vector<uint8_t> h8(o_hc, 0);  // sequences (codes, zero on both sides) and constraint rows, copied up in one piece
   std::vector<double> hhp((size_t)Lmax + 1), hpow(n_pow), hout(3 * (size_t)n);
-  for (int s = 0; s <= Lmax; s++)  // (read only past the resident table: sf_pf_long's own extrapolation, the same for every L)
+  for (int s = 0; s <= Lmax; s++)  // (read only past the resident table, SF_MAX_W + 1: build_dev_params' extrapolation)
     hhp[s] = (s <= 30) ? 0.0 : M.pf_hp30 * exp(-(P->lxc * log(s / 30.)) * 10. / kT);
   std::vector<SfPfLong> hF((size_t)n);
   std::vector<char> hcen(n_L + (size_t)n);
 
   LongBufs B;
-  B.who = "sf_pf_long_batch";
+  B.who = R.who;
   void *p;
   double *d_tri[SF_PFLONG_NTRI], *d_f64;
-  int16_t *d_i16 = nullptr;
   uint8_t *d_u8;
   SfPfLong *d_F;
   static const char *const tri_names[SF_PFLONG_NTRI] = {"qb", "qb transposed / A0", "qm", "qm transposed", "qm1 / w", "ob", "A1"};
@@ -1689,27 +1755,17 @@ int pf_long_batch_chunk(const uint8_t *seqs, int ld, const int32_t *len, const c
   }
   if ((rc = B.alloc(&p, n_f64 * sizeof(double), "results, scale powers, hairpin weights, q5, q3, partial sums"))) return rc;
   d_f64 = (double *)p;
-  if (n_i16) {
-    if ((rc = B.alloc(&p, n_i16 * sizeof(int16_t), "bracket partners"))) return rc;
-    d_i16 = (int16_t *)p;
-  }
   if ((rc = B.alloc(&p, n_u8, "sequences, constraints, centroids, row marks"))) return rc;
   d_u8 = (uint8_t *)p;
   if ((rc = B.alloc(&p, (size_t)n * sizeof(SfPfLong), "partition function states"))) return rc;
   d_F = (SfPfLong *)p;
+  if ((rc = long_bind_rows(B, K, R, s0, d_u8, hF))) return rc;
 
   std::vector<size_t> pow_off((size_t)n), cen_off((size_t)n);
-  size_t a_tri = 0, a_L = 0, a_hcL = 0, a_part = 0;
-  int a_hc = 0;
+  size_t a_tri = 0, a_L = 0, a_part = 0;
   for (int k = 0; k < n; k++) {
-    const int L = len[s0 + k];
-    const uint8_t *row = seqs + (size_t)(s0 + k) * ld;
-    uint8_t *hS = h8.data() + o_S + a_L + 2 * (size_t)k;
-    for (int x = 0; x < L; x++) hS[x + 1] = sf_encode_nt(row[x]);
+    const int L = R.len[s0 + k];
     SfPfLong &F = hF[k];
-    memset(&F, 0, sizeof F);
-    F.L = L;
-    F.S = d_u8 + o_S + a_L + 2 * (size_t)k;
     F.hpx = d_f64 + o_hp;
     pow_off[k] = 2 * (a_L + 2 * (size_t)k);
     F.sc = d_f64 + o_pow + pow_off[k];
@@ -1724,31 +1780,12 @@ int pf_long_batch_chunk(const uint8_t *seqs, int ld, const int32_t *len, const c
     F.out = d_f64 + o_out + 3 * (size_t)k;
     cen_off[k] = a_L + (size_t)k;
     F.cen = (char *)d_u8 + o_cen + cen_off[k];
-    if (constrained[s0 + k]) {
-      memcpy(h8.data() + o_src + a_hcL, cons + (size_t)(s0 + k) * ld, (size_t)L);
-      const size_t o16 = 3 * (a_hcL + 2 * (size_t)a_hc);
-      F.hc.c = (const char *)d_u8 + o_hc + a_hcL + 2 * (size_t)a_hc;
-      F.hc.partner = d_i16 + o16;
-      F.hc.encl = d_i16 + o16 + (size_t)L + 2;
-      a_hcL += (size_t)L;
-      a_hc++;
-    }
     a_tri += SF_LONG_TRI(L);
     a_L += (size_t)L;
     a_part += 2 * (size_t)pfl_prob_waves(L, lanes);
   }
-  HIPCHK(hipMemcpyAsync(d_u8, h8.data(), h8.size(), hipMemcpyHostToDevice, g.stream));
   HIPCHK(hipMemcpyAsync(d_f64 + o_hp, hhp.data(), hhp.size() * sizeof(double), hipMemcpyHostToDevice, g.stream));
   HIPCHK(hipMemcpyAsync(d_F, hF.data(), (size_t)n * sizeof(SfPfLong), hipMemcpyHostToDevice, g.stream));
-  a_hcL = 0;
-  for (int k = 0; k < n; k++) {  // the bracket partners and enclosing pairs of every constrained row
-    if (!constrained[s0 + k]) continue;
-    const SfPfLong &F = hF[k];
-    SF_LAUNCH(sf_long_hc_kernel, 1, 64, 0, g.stream, (const char *)d_u8 + o_src + a_hcL, F.L, (char *)F.hc.c,
-              (int16_t *)F.hc.partner, (int16_t *)F.hc.encl, (int16_t *)F.hc.encl + (size_t)F.L + 2, (int *)g.status.p);
-    a_hcL += (size_t)F.L;
-  }
-  HIPCHK(hipGetLastError());
 
   for (auto &e : B.ev) HIPCHK(hipEventCreate(&e));
   const SfDevParams *D = (const SfDevParams *)g.dP;
@@ -1770,7 +1807,8 @@ int pf_long_batch_chunk(const uint8_t *seqs, int ld, const int32_t *len, const c
   std::vector<int> state((size_t)n, PENDING), attempts((size_t)n, 0);
   std::vector<double> lns((size_t)n), lz((size_t)n, 0.0);
   std::vector<uint8_t> act((size_t)n);
-  for (int k = 0; k < n; k++) lns[k] = pfl_first_lns(hint && hint[s0 + k] != SF_PF_LONG_NO_HINT ? &hint[s0 + k] : nullptr, kT, len[s0 + k]);
+  for (int k = 0; k < n; k++)
+    lns[k] = pfl_first_lns(hint && hint[s0 + k] != SF_PF_LONG_NO_HINT ? &hint[s0 + k] : nullptr, kT, R.len[s0 + k]);
   int n_done = 0;
   float ms = 0;
   while (n_done < n) {
@@ -1782,7 +1820,7 @@ int pf_long_batch_chunk(const uint8_t *seqs, int ld, const int32_t *len, const c
         if (!act[k]) continue;
         if (attempts[k] >= SF_PFLONG_MAX_ATTEMPTS) return SF_ERR_RANGE;
         attempts[k]++;
-        const int L = len[s0 + k];
+        const int L = R.len[s0 + k];
         Ltop = std::max(Ltop, L);
         pfl_scale_powers(lns[k], ln_mlbase, L, hpow.data() + pow_off[k], hpow.data() + pow_off[k] + (size_t)L + 2);
       }
@@ -1807,7 +1845,7 @@ int pf_long_batch_chunk(const uint8_t *seqs, int ld, const int32_t *len, const c
       for (int k = 0; k < n; k++) {
         if (!act[k]) continue;
         lz[k] = hout[3 * (size_t)k];
-        if (!isfinite(lz[k]) || fabs(lz[k]) > SF_PF_LNZ_MAX) lns[k] = pfl_next_lns(lns[k], lz[k], len[s0 + k]);
+        if (!isfinite(lz[k]) || fabs(lz[k]) > SF_PF_LNZ_MAX) lns[k] = pfl_next_lns(lns[k], lz[k], R.len[s0 + k]);
         else state[k] = READY;
       }
     }
@@ -1815,7 +1853,7 @@ int pf_long_batch_chunk(const uint8_t *seqs, int ld, const int32_t *len, const c
     int Ltop = 0;
     for (int k = 0; k < n; k++) {
       act[k] = state[k] == READY;
-      if (act[k]) Ltop = std::max(Ltop, (int)len[s0 + k]);
+      if (act[k]) Ltop = std::max(Ltop, (int)R.len[s0 + k]);
     }
     HIPCHK(hipMemcpyAsync(d_u8 + o_act, act.data(), (size_t)n, hipMemcpyHostToDevice, g.stream));
     HIPCHK(hipMemsetAsync(d_u8 + o_cen, '.', n_L + (size_t)n, g.stream));  // (the rows done before are on the host already)
@@ -1837,7 +1875,7 @@ int pf_long_batch_chunk(const uint8_t *seqs, int ld, const int32_t *len, const c
     ms_out[1] += ms;
     for (int k = 0; k < n; k++) {
       if (!act[k]) continue;
-      const int L = len[s0 + k];
+      const int L = R.len[s0 + k];
       const double *res = hout.data() + 3 * (size_t)k;
       if (isfinite(res[1]) && isfinite(res[2])) {
         const double dG = -(res[0] + (double)L * lns[k]) * kT / 1000.0;
@@ -1872,61 +1910,17 @@ int sf_pf_long_batch(const uint8_t *seqs, int n, int ld, const int32_t *len, con
                      sf_pf_long_row *out, char *centroid_out) {
   int rc = check_ready();
   if (rc) return rc;
-  if (n < 0 || (n > 0 && (!seqs || !len))) return SF_ERR_BAD_ARG;
-  for (int k = 0; k < n; k++)
-    if (len[k] < 1 || len[k] > SF_MAX_LONG || len[k] > ld) return SF_ERR_BAD_ARG;
-  if (n == 0) {
-    g_pflb_ms[0] = g_pflb_ms[1] = 0.0;
-    g_pflb_chunks = g_pflb_passes = 0;
-    return SF_OK;
-  }
-  // every constraint row is looked at before anything is launched: a row of dots is no constraint
-  std::vector<char> constrained((size_t)n, 0);
-  if (cons)
-    for (int k = 0; k < n; k++) {
-      const char *c = cons + (size_t)k * ld;
-      bool any = false, noncanonical = false;
-      for (int x = 0; x < len[k] && !any; x++) any = c[x] != '.';
-      if (!any) continue;
-      if ((rc = scan_constraints(seqs + (size_t)k * ld, c, 1, len[k], &noncanonical))) return rc;
-      constrained[k] = 1;
-    }
-  // results are staged and handed over only when every chunk has succeeded (they outlive the chunks' device buffers)
+  LongRows R = {seqs, n, ld, len, cons, "sf_pf_long_batch"};
+  if ((rc = long_rows_check(R))) return rc;
+  // the records are staged and handed over, like the centroids, only when every chunk has succeeded
   std::vector<sf_pf_long_row> rows_host((size_t)n);
-  std::vector<char> cen_host;
-  if (centroid_out) {
-    size_t total = 0;
-    for (int k = 0; k < n; k++) total += (size_t)len[k] + 1;
-    cen_host.resize(total);
-  }
   double ms[2] = {0, 0};
-  int chunks = 0, passes = 0;
-  size_t cen_off = 0;
-  for (int s0 = 0; s0 < n;) {
-    size_t bytes = 0, cen_bytes = 0;
-    int m = 0;
-    while (s0 + m < n && m < kLongBatchMaxSeqs) {
-      const size_t b = SF_PFLONG_BYTES(len[s0 + m]);
-      if (m > 0 && bytes + b > g_longb_bytes) break;
-      bytes += b;
-      cen_bytes += (size_t)len[s0 + m] + 1;
-      m++;
-    }
-    if ((rc = pf_long_batch_chunk(seqs, ld, len, cons, constrained, mfe_dcal_hint, s0, m, rows_host.data(),
-                                  centroid_out ? cen_host.data() + cen_off : nullptr, ms, &passes)))
-      return rc;
-    cen_off += cen_bytes;
-    s0 += m;
-    chunks++;
-  }
-  if (out) memcpy(out, rows_host.data(), (size_t)n * sizeof(sf_pf_long_row));
-  if (centroid_out) {
-    size_t off = 0;
-    for (int k = 0; k < n; k++) {
-      memcpy(centroid_out + (size_t)k * ((size_t)ld + 1), cen_host.data() + off, (size_t)len[k] + 1);
-      off += (size_t)len[k] + 1;
-    }
-  }
+  int chunks, passes = 0;
+  rc = long_for_chunks(R, pf_long_row_bytes, centroid_out, &chunks, [&](int s0, int m, char *cen_host) {
+    return pf_long_batch_chunk(R, mfe_dcal_hint, s0, m, rows_host.data(), cen_host, ms, &passes);
+  });
+  if (rc) return rc;  // (n == 0: no chunk)
+  if (out && n > 0) memcpy(out, rows_host.data(), (size_t)n * sizeof(sf_pf_long_row));
   g_pflb_ms[0] = ms[0];
   g_pflb_ms[1] = ms[1];
   g_pflb_chunks = chunks;

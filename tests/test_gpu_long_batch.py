@@ -13,6 +13,7 @@ from scanfold_amd import _lib, functions, params
 from scanfold_amd import scanfold as sfd
 from long_util import rand_seq, with_oracle_constraint
 from test_gpu_long_fold import model_at, span
+import test_long_batch
 from test_long_batch import expected_zscore_file, seq_bytes
 from test_long_fold import constraint_string, planted_stem
 
@@ -167,3 +168,13 @@ def test_combined_driver_global_zscore(gpu_engine, oracle, tmp_path, monkeypatch
     for f in plain:
         assert z[f] == plain[f], f
     assert z[base + ".global_zscore.txt"].decode() == expected_zscore_file(oracle, seq, "whole", 6, "di", 5)
+
+
+# ---- the single call beside the batch: test_long_batch's checks at the product's lane budgets ----
+
+def test_a_single_call_is_one_chunk_under_any_byte_budget(gpu_engine):
+    test_long_batch.check_a_single_call_is_one_chunk_under_any_byte_budget(gpu_engine)
+
+
+def test_the_two_time_records_stay_apart(gpu_engine):
+    test_long_batch.check_the_two_time_records_stay_apart(gpu_engine)

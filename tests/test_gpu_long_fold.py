@@ -15,6 +15,7 @@ from conftest import random_seqs
 from long_util import (formed_type7, hairpin_record, hairpin_rich, lengths_summing_to, multiloop_rich, separated_record,
                        short_hairpin_params, with_oracle_constraint)
 from test_gpu_parity import PF_TOL
+import test_long_fold
 from test_long_fold import constraint_string, expected_refold, planted_stem, rand_seq
 
 pytestmark = pytest.mark.gpu
@@ -314,3 +315,17 @@ def test_alphabet_and_energy_only_call(gpu_engine, oracle):
     assert gpu_engine.fold_long(codes) == (e, db)
     assert gpu_engine.fold_long(raw, structure=False) == (e, None)
     assert gpu_engine.fold_long_times()[2] == 0
+
+
+# ---- the single call beside the batch: test_long_fold's checks at the product's lane budgets ----
+
+def test_a_constraint_of_dots_is_no_constraint(gpu_engine):
+    test_long_fold.check_a_constraint_of_dots_is_no_constraint(gpu_engine)
+
+
+def test_energy_only_and_null_outputs(gpu_engine):
+    test_long_fold.check_energy_only_and_null_outputs(gpu_engine)
+
+
+def test_the_shortest_records(gpu_engine, oracle):
+    test_long_fold.check_the_shortest_records(gpu_engine, oracle)

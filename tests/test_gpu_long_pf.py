@@ -12,6 +12,7 @@ from long_pf_util import (KEYS, assert_carries_weight, assert_close, block_recor
                           gc_only, nested_record, oracle_pf)  # (forget_cubic_references: an autouse fixture)
 from long_util import hairpin_record, hairpin_rich, pair_table, rand_seq
 from test_gpu_long_fold import assert_windows_equal_oracle, balanced, model_at, span, synthetic_set, viral_like
+import test_long_pf
 from test_long_fold import constraint_string, params_in, planted_stem
 
 pytestmark = pytest.mark.gpu
@@ -288,3 +289,13 @@ def test_mfe_hint(gpu_engine, oracle):
         if hint == e:
             assert t["attempts"] == 1
     assert_windows_equal_oracle(gpu_engine, oracle)
+
+
+# ---- the single call beside the batch: test_long_pf's checks at the product's lane budgets ----
+
+def test_a_constraint_of_dots_is_no_constraint(gpu_engine):
+    test_long_pf.check_a_constraint_of_dots_is_no_constraint(gpu_engine)
+
+
+def test_the_shortest_records(gpu_engine, oracle):
+    test_long_pf.check_the_shortest_records(gpu_engine, oracle)

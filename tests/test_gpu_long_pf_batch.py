@@ -16,6 +16,7 @@ from long_pf_util import (KEYS, assert_carries_weight, assert_close, cubic_refer
 from long_util import rand_seq
 from test_gpu_long_fold import span
 from test_long_fold import constraint_string, params_in, planted_stem
+import test_long_pf_batch
 from test_long_pf_batch import pf_bytes, single
 
 pytestmark = pytest.mark.gpu
@@ -239,3 +240,17 @@ def test_combined_driver_global_ensemble(gpu_engine, tmp_path, monkeypatch):
         head, s, cen = lines[3 * k:3 * k + 3]
         assert head.startswith(">myrna\t") and s == seq and cen == r["centroid"]
         assert head.endswith("ensemble dG=%.2f ED=%.2f centroid distance=%.2f" % (r["dG"], r["mean_bp_dist"], r["centroid_dist"]))
+
+
+# ---- the single call beside the batch: test_long_pf_batch's checks at the product's lane budgets ----
+
+def test_a_single_call_is_one_chunk_under_any_byte_budget(gpu_engine):
+    test_long_pf_batch.check_a_single_call_is_one_chunk_under_any_byte_budget(gpu_engine)
+
+
+def test_the_two_time_records_stay_apart(gpu_engine):
+    test_long_pf_batch.check_the_two_time_records_stay_apart(gpu_engine)
+
+
+def test_row_state_survives_a_retry_in_the_one_row_case(gpu_engine, oracle):
+    test_long_pf_batch.check_row_state_survives_a_retry_in_the_one_row_case(gpu_engine, oracle)

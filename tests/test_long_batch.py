@@ -250,3 +250,37 @@ def test_global_zscore_refuses_a_record_past_the_limit_before_the_scan(emul, tmp
     with pytest.raises(ValueError, match="global_zscore"):
         sfd.main(["in.fa", "-w", "40", "-s", "20", "-r", "3", "--global_zscore"])
     assert os.listdir(tmp_path) == ["in.fa"]
+
+
+# ---- what a single call must not share with a batch: the byte budget, the time records (run again on the GPU in test_gpu_long_batch.py) ----
+
+def check_a_single_call_is_one_chunk_under_any_byte_budget(engine):
+    s = rand_seq(np.random.default_rng(100 + 433), 433)
+    rows = [rand_seq(np.random.default_rng(100 + 57), 57)] * 5
+    whole = engine.fold_long(s)
+    try:
+        engine.set_long_batch_bytes(1)
+        assert engine.fold_long(s) == whole
+        engine.fold_long_batch(rows)
+        assert engine.fold_long_batch_times()["chunks"] == 5  # the setting itself still works
+    finally:
+        engine.set_long_batch_bytes(0)
+
+
+def check_the_two_time_records_stay_apart(engine):
+    a, b, c = (rand_seq(np.random.default_rng(100 + L), L) for L in (57, 120, 150))
+    engine.fold_long_batch([a, b], structure=True)
+    batch = engine.fold_long_batch_times()
+    engine.fold_long(c)
+    assert engine.fold_long_batch_times() == batch
+    single = engine.fold_long_times()
+    engine.fold_long_batch([b, c, a], structure=True)
+    assert engine.fold_long_times() == single
+
+
+def test_a_single_call_is_one_chunk_under_any_byte_budget(emul):
+    check_a_single_call_is_one_chunk_under_any_byte_budget(emul)
+
+
+def test_the_two_time_records_stay_apart(emul):
+    check_the_two_time_records_stay_apart(emul)

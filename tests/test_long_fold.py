@@ -281,3 +281,43 @@ def test_global_refold_leaves_every_other_output_unchanged(emul, tmp_path, monke
     assert lines[1] == recs[0] and len(lines[5]) == len(recs[0])  # the whole record, past the last window
     for f in plain:
         assert refold[f] == plain[f], f
+
+
+# ---- sf_fold_long and a batch of one row: dots as a constraint, NULL outputs, L = 1 (run again on the GPU in test_gpu_long_fold.py) ----
+
+def check_a_constraint_of_dots_is_no_constraint(engine):
+    """a constraint of dots folds like no constraint at all (a batch does not even set up the arrays for such a row)"""
+    for L in (57, 433):
+        s = rand_seq(np.random.default_rng(100 + L), L)
+        assert engine.fold_long(s, "." * L) == engine.fold_long(s), L
+        e, db = engine.fold_long_batch([s], ["." * L], structure=True)  # a batch of one row: the same bytes
+        assert (int(e[0]), db[0]) == engine.fold_long(s), L
+
+
+def check_energy_only_and_null_outputs(engine):
+    s = b"ACGU" * 10
+    assert engine.lib.sf_fold_long(s, 40, None, None, None) == 0  # mfe_dcal_out may be NULL too
+    assert engine.fold_long_times()[2] == 0                       # no traceback, no traceback time
+
+
+def check_the_shortest_records(engine, oracle):
+    """L = 1: no diagonal past d = 0"""
+    for L in (1, 4):
+        s = rand_seq(np.random.default_rng(100 + L), L)
+        db, e = oracle.mfe(s)
+        assert engine.fold_long(s) == (e, db), L
+        assert engine.fold_long(s, structure=False) == (e, None), L
+        eb, dbb = engine.fold_long_batch([s], structure=True)
+        assert (int(eb[0]), dbb[0]) == (e, db), L
+
+
+def test_a_constraint_of_dots_is_no_constraint(emul):
+    check_a_constraint_of_dots_is_no_constraint(emul)
+
+
+def test_energy_only_and_null_outputs(emul):
+    check_energy_only_and_null_outputs(emul)
+
+
+def test_the_shortest_records(emul, oracle):
+    check_the_shortest_records(emul, oracle)

@@ -253,3 +253,36 @@ def test_unspanned_nested_record(emul, oracle):
     ref = cubic_reference(oracle, seq, params.default_params())
     assert_carries_weight(ref, outer, branches, 600)
     assert_close(emul.pf_long(seq), ref, "nested 600", ref["bpp"])
+
+
+# ---- sf_pf_long and a batch of one row: dots as a constraint, L = 1 (run again on the GPU in test_gpu_long_pf.py) ----
+
+def check_a_constraint_of_dots_is_no_constraint(engine):
+    """a constraint of dots gives the bits of no constraint at all (a batch does not even set up the arrays for such a row):
+    `==` on floats and strings, with and without the MFE as a hint"""
+    for L in (57, 433):
+        s = rand_seq(np.random.default_rng(100 + L), L)
+        e, _ = engine.fold_long(s, structure=False)
+        assert engine.pf_long(s, "." * L) == engine.pf_long(s), L
+        assert engine.pf_long(s, "." * L, mfe_hint=e) == engine.pf_long(s, mfe_hint=e), L
+        row, = engine.pf_long_batch([s], ["." * L], mfe_hints=[e])  # a batch of one row: the same bits
+        assert {k: row[k] for k in KEYS + ("centroid",)} == engine.pf_long(s, mfe_hint=e), L
+
+
+def check_the_shortest_records(engine, oracle):
+    """L = 1: no diagonal past d = 0, and no outside launch at all"""
+    for L in (1, 4):
+        s = rand_seq(np.random.default_rng(100 + L), L)
+        ref = oracle.pf(s, want_bpp=True)
+        assert_close(engine.pf_long(s), ref, "L=%d" % L, ref["bpp"])
+        assert engine.pf_long_times()["attempts"] == 1
+        row, = engine.pf_long_batch([s])
+        assert {k: row[k] for k in KEYS + ("centroid",)} == engine.pf_long(s), L
+
+
+def test_a_constraint_of_dots_is_no_constraint(emul):
+    check_a_constraint_of_dots_is_no_constraint(emul)
+
+
+def test_the_shortest_records(emul, oracle):
+    check_the_shortest_records(emul, oracle)

@@ -308,3 +308,59 @@ def test_global_ensemble_runs_on_the_batch(emul, tmp_path, monkeypatch):
     assert calls == [3]
     for a, b in ((".AllDBN-global_refold.ensemble.txt", ".loop.ensemble.txt"), (".AllDBN-global_refold.txt", ".loop.txt")):
         assert (tmp_path / (base + a)).read_bytes() == (tmp_path / (base + b)).read_bytes(), a
+
+
+# ---- what a single call must not share with a batch (byte budget, time records), and a retry in a batch of one row (run again on the GPU in test_gpu_long_pf_batch.py) ----
+
+def check_a_single_call_is_one_chunk_under_any_byte_budget(engine):
+    s = rand_seq(np.random.default_rng(100 + 433), 433)
+    rows = [rand_seq(np.random.default_rng(100 + 57), 57)] * 5
+    whole = engine.pf_long(s)
+    try:
+        engine.set_long_batch_bytes(1)
+        assert engine.pf_long(s) == whole
+        engine.pf_long_batch(rows)
+        assert engine.pf_long_batch_times()["chunks"] == 5  # the setting itself still works
+    finally:
+        engine.set_long_batch_bytes(0)
+
+
+def check_the_two_time_records_stay_apart(engine):
+    a, b, c = (rand_seq(np.random.default_rng(100 + L), L) for L in (57, 120, 150))
+    engine.pf_long_batch([a, b])
+    batch = engine.pf_long_batch_times()
+    engine.pf_long(c)
+    assert engine.pf_long_batch_times() == batch
+    single_times = engine.pf_long_times()
+    assert set(single_times) == {"inside_ms", "outside_ms", "attempts", "lns"}
+    engine.pf_long_batch([b, c, a])
+    assert engine.pf_long_times() == single_times
+
+
+def check_row_state_survives_a_retry_in_the_one_row_case(engine, oracle):
+    """the repeating row of test_a_row_that_repeats_leaves_the_others_alone, alone and as a batch of one row: the same retries"""
+    s = rand_seq(np.random.default_rng(77), 150)
+    e, _ = engine.fold_long(s, structure=False)
+    assert e < -1000
+    got = engine.pf_long(s, mfe_hint=30 * e)
+    t = engine.pf_long_times()
+    assert t["attempts"] > 1
+    row, = engine.pf_long_batch([s], mfe_hints=[30 * e])
+    assert (t["attempts"], t["lns"]) == (row["attempts"], row["lns"])
+    assert got == single(row)
+    assert_close(got, engine.pf_long(s, mfe_hint=e), "wrong hint against the true one")
+    assert engine.pf_long_times()["attempts"] == 1
+    ref = oracle.pf(s, want_bpp=True)
+    assert_close(got, ref, "wrong hint against the oracle", ref["bpp"])
+
+
+def test_a_single_call_is_one_chunk_under_any_byte_budget(emul):
+    check_a_single_call_is_one_chunk_under_any_byte_budget(emul)
+
+
+def test_the_two_time_records_stay_apart(emul):
+    check_the_two_time_records_stay_apart(emul)
+
+
+def test_row_state_survives_a_retry_in_the_one_row_case(emul, oracle):
+    check_row_state_survives_a_retry_in_the_one_row_case(emul, oracle)
