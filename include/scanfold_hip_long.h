@@ -10,7 +10,9 @@
  * diversity) of the same whole record; sf_fold_long_batch is sf_fold_long for many sequences of any lengths side by side
  * (a record and its shuffles: the z-score of a sequence past SF_MAX_W), and sf_pf_long_batch is sf_pf_long for many
  * sequences, constraints and hints side by side (the three ensembles of --global_ensemble; fc.pf() over long fragments),
- * every row bit for bit what sf_pf_long returns for it.  Soft constraints (SHAPE) are not provided past SF_MAX_W.
+ * every row bit for bit what sf_pf_long returns for it.  sf_fold_banded is sf_fold_long under a base-pair span in banded
+ * tables: memory and work linear in the record's length, records up to SF_MAX_BANDED nucleotides, the same bytes.
+ * Soft constraints (SHAPE) are not provided past SF_MAX_W.
  */
 #ifndef SCANFOLD_HIP_LONG_H
 #define SCANFOLD_HIP_LONG_H
@@ -36,6 +38,32 @@ int sf_fold_long(const uint8_t *seq, int L, const char *cons, int32_t *mfe_dcal_
 /* Device-event times (ms) of the phases of the last successful sf_fold_long: the fill of c / fML (one launch per
  * diagonal), the exterior loop f5, and the traceback (0 when it was not asked for).  Any pointer may be NULL. */
 int sf_fold_long_times(double *fill_ms, double *f5_ms, double *trace_ms);
+
+#define SF_MAX_BANDED 4194304 /* longest sequence sf_fold_banded accepts (positions are int32; memory is the real limit) */
+/* device memory of one sf_fold_banded call with band B = min(span, L): three int32 band tables and what is linear in L */
+#define SF_BANDED_BYTES(L, B) (12 * (size_t)(L) * (size_t)(B) + 75 * (size_t)(L) + 4 * (size_t)(B) + 153)
+
+/* sf_fold_long under the resident base-pair span S (sf_set_max_bp_span, S >= 1) with the tables stored as a band:
+ * a cell (i, j) with j - i >= S can neither pair nor be read by a cell that can, so only the B = min(S, L) diagonals
+ * 0 .. B-1 are kept and filled.  Energy and structure are those of sf_fold_long under the same span, byte for byte, at
+ * every length both accept; this call also takes records past SF_MAX_LONG, up to SF_MAX_BANDED (bracket partners of the
+ * constraint are int32 here).  seq, cons, mfe_dcal_out, db_out as for sf_fold_long.  S >= L is legal (B = L: a full fold
+ * in banded storage).  B fill launches, then f5 in O(L B) and the traceback, each in one workgroup.
+ * The tables live in device memory, allocated for the call and freed before it returns: SF_BANDED_BYTES(L, B) bytes, of
+ * which 9 (L + 2) (the constraint's arrays) only with a constraint: 12 L B + 75 L + 4 B + 153
+ * (218 MB at L = 29 903, S = 600; 3.6 GB at L = 500 000, S = 600).
+ * No span set, L < 1, L > SF_MAX_BANDED, seq NULL: SF_ERR_BAD_ARG (without a span, call sf_fold_long).  Unbalanced
+ * brackets: SF_ERR_CONSTRAINT, before anything is launched.  Not enough device memory: SF_ERR_HIP with the text in
+ * sf_last_hip_error().  On any error no output is written. */
+int sf_fold_banded(const uint8_t *seq, int L, const char *cons, int32_t *mfe_dcal_out, char *db_out);
+
+/* Of the last successful sf_fold_banded: device-event times (ms) of the fill, the exterior loop f5 and the traceback (0
+ * when it was not asked for), the band B it ran with and the number of fill launches (= B).  Any pointer may be NULL. */
+int sf_fold_banded_times(double *fill_ms, double *f5_ms, double *trace_ms, int *band, int *fill_launches);
+
+/* What sf_fold_banded would allocate for a record of L nucleotides under the span `span`: SF_BANDED_BYTES(L, min(span, L)).
+ * Needs sf_init only; nothing is allocated.  L < 1, L > SF_MAX_BANDED, span < 1, bytes NULL: SF_ERR_BAD_ARG. */
+int sf_fold_banded_bytes(int L, int span, size_t *bytes);
 
 /* sf_fold_long for n sequences at once.  Row s of seqs (n rows of ld bytes) holds len[s] bytes, 1 <= len[s] <= SF_MAX_LONG
  * and <= ld; the rows may differ in length freely.  cons: NULL, or n rows of ld characters with the meaning of

@@ -9,7 +9,9 @@ fc.hc_add_from_db and fc.sc_add_SHAPE_deigan (ScanFold-Scan.py:410; ScanFold.py:
 sf_fold_constrained.  RNA.duplexfold(s1, s2) (ScanFold.py:785; ScanFoldFunctions.py:824) folds through sf_duplex_batch.
 Not provided: plotting, Zarringhalam soft constraints (upstream's call fails too).
 Sequences longer than SF_MAX_W (400 nt, the window kernels' limit) fold with fc.mfe() / RNA.fold through sf_fold_long
-(whole records up to 32 767 nt: ScanFold.py --global_refold, :1509-1547), hc_add_from_db included.  Their partition
+(whole records up to 32 767 nt: ScanFold.py --global_refold, :1509-1547), hc_add_from_db included; with md.max_bp_span
+set they fold through sf_fold_banded (banded tables, the same bytes) when the record is longer than 32 767 nt (up to
+SF_MAX_BANDED) or at least four spans long.  Their partition
 function, centroid and mean base-pair distance exist in the engine (Engine.pf_long; functions.rna_refold) but this facade
 does not route to them yet: fc.pf() / fc.centroid() / fc.mean_bp_distance() raise NotImplementedError, as does the SHAPE
 term, which does not exist past 400 nt.
@@ -99,7 +101,15 @@ class fold_compound:
             if self._sc is not None:
                 raise NotImplementedError("SHAPE soft constraints on a sequence longer than %d nt: the whole-record fold "
                                           "(sf_fold_long) has no pseudo-energy term" % _lib.SF_MAX_W)
-            e, db = self._eng.fold_long(self.sequence, self._hc)
+            L, span = len(self.sequence), self._eng.max_bp_span
+            if L > _lib.SF_MAX_LONG and span < 1:
+                raise ValueError("a sequence of %d nt folds only under md.max_bp_span (sf_fold_banded): without a span "
+                                 "whole-record folds stop at %d nt" % (L, _lib.SF_MAX_LONG))
+            # under a span the band holds the whole fold: the same bytes from 12 L span bytes of tables (sf_fold_banded)
+            if L > _lib.SF_MAX_LONG or (span > 0 and 4 * span <= L and self._eng.has_fold_banded()):
+                e, db = self._eng.fold_banded(self.sequence, self._hc)
+            else:
+                e, db = self._eng.fold_long(self.sequence, self._hc)
             return db, _f32(e)
         if self._hc is not None or self._sc is not None:
             r = self._eng.fold_constrained([self.sequence], None if self._hc is None else [self._hc],

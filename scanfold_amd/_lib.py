@@ -78,6 +78,9 @@ def _header_define(header, name):
 _LONG_EXPORTS = {
     "sf_fold_long": (ctypes.c_int, [_c_u8p, ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_void_p]),
     "sf_fold_long_times": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double)] * 3),
+    "sf_fold_banded": (ctypes.c_int, [_c_u8p, ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "sf_fold_banded_times": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double)] * 3 + [ctypes.POINTER(ctypes.c_int)] * 2),
+    "sf_fold_banded_bytes": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
     "sf_fold_long_batch": (ctypes.c_int, [_c_u8p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                           ctypes.c_void_p]),
     "sf_fold_long_batch_times": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double)] * 3 + [ctypes.POINTER(ctypes.c_int)]),
@@ -131,6 +134,7 @@ class ScanFoldHipError(RuntimeError):
 
 SF_MAX_W = _header_define("scanfold_hip.h", "SF_MAX_W")  # longest window of the window kernels
 SF_MAX_LONG = _header_define("scanfold_hip_long.h", "SF_MAX_LONG")  # longest sequence of sf_fold_long
+SF_MAX_BANDED = _header_define("scanfold_hip_long.h", "SF_MAX_BANDED")  # longest sequence of sf_fold_banded
 SF_DUPLEX_MAX_LEN = _header_define("scanfold_hip_duplex.h", "SF_DUPLEX_MAX_LEN")  # longest strand of a duplex
 SF_DUPLEX_STRUCT_LEN = _header_define("scanfold_hip_duplex.h", "SF_DUPLEX_STRUCT_LEN")
 SF_DUPLEX_NONE = _header_define("scanfold_hip_duplex.h", "SF_DUPLEX_NONE")  # "energy" of strands that cannot pair
@@ -334,6 +338,49 @@ class Engine:
         t = [ctypes.c_double() for _ in range(3)]
         self._check(self.lib.sf_fold_long_times(*(ctypes.byref(x) for x in t)))
         return tuple(x.value for x in t)
+
+    def has_fold_banded(self):
+        return getattr(self.lib, "sf_fold_banded", None) is not None
+
+    def _need_fold_banded(self):
+        if not self.has_fold_banded():
+            raise ScanFoldHipError("this library (%s) has no sf_fold_banded: whole-record folds under a base-pair span in "
+                                   "banded tables need libscanfold_hip.so" % getattr(self.lib, "_name", "?"))
+
+    def fold_banded(self, seq, cons=None, structure=True):
+        """fold_long under the resident base-pair span (set_max_bp_span(S), S >= 1) in banded tables (sf_fold_banded): ONE
+        sequence of 1..SF_MAX_BANDED nt -> (mfe_dcal, dot-bracket or None), the bytes fold_long returns under the same span,
+        from 12 L min(S, L) bytes of tables and min(S, L) fill launches.  Raises ScanFoldHipError where no span is set, and
+        on a library without the entry point (there is no fallback)."""
+        self._need_fold_banded()
+        s = seq if isinstance(seq, (bytes, bytearray)) else str(seq).encode("ascii")
+        L = len(s)
+        c = None
+        if cons is not None:
+            c = cons if isinstance(cons, (bytes, bytearray)) else str(cons).encode("ascii")
+            if len(c) != L:
+                raise ValueError("constraint string and sequence differ in length")
+        arr = np.frombuffer(bytes(s), dtype=np.uint8) if L else np.zeros(1, dtype=np.uint8)
+        e = np.zeros(1, dtype=np.int32)
+        db = np.zeros(L + 1, dtype=np.uint8) if structure else None
+        self._check(self.lib.sf_fold_banded(arr.ctypes.data, L, None if c is None else bytes(c), e.ctypes.data,
+                                            None if db is None else db.ctypes.data))
+        return int(e[0]), (bytes(db[:L]).decode() if structure else None)
+
+    def fold_banded_times(self):
+        """-> dict(fill_ms, f5_ms, trace_ms, band, fill_launches) of the last fold_banded (device events; band = min(span, L))."""
+        self._need_fold_banded()
+        t = [ctypes.c_double() for _ in range(3)]
+        b, n = ctypes.c_int(), ctypes.c_int()
+        self._check(self.lib.sf_fold_banded_times(*(ctypes.byref(x) for x in t), ctypes.byref(b), ctypes.byref(n)))
+        return dict(fill_ms=t[0].value, f5_ms=t[1].value, trace_ms=t[2].value, band=b.value, fill_launches=n.value)
+
+    def fold_banded_bytes(self, L, span):
+        """the device memory fold_banded would allocate for L nucleotides under `span` (sf_fold_banded_bytes)"""
+        self._need_fold_banded()
+        n = ctypes.c_size_t()
+        self._check(self.lib.sf_fold_banded_bytes(int(L), int(span), ctypes.byref(n)))
+        return int(n.value)
 
     def has_fold_long_batch(self):
         return getattr(self.lib, "sf_fold_long_batch", None) is not None

@@ -21,6 +21,7 @@
 #include "sf_mfe_fast.hip.h"
 #include "sf_mfe_long.hip.h"
 #include "sf_mfe_long_batch.hip.h"
+#include "sf_mfe_banded.hip.h"
 #include "sf_pf.hip.h"
 #include "sf_pf_long.hip.h"
 #include "sf_pf_long_batch.hip.h"
@@ -1351,6 +1352,172 @@ int sf_fold_long_times(double *fill_ms, double *f5_ms, double *trace_ms) {
   if (fill_ms) *fill_ms = g_long_ms[0];
   if (f5_ms) *f5_ms = g_long_ms[1];
   if (trace_ms) *trace_ms = g_long_ms[2];
+  return SF_OK;
+}
+
+}  // extern "C"
+
+// ---------------- whole-record folds under a span in banded tables (sf_mfe_banded.hip.h) ----------------
+namespace {
+double g_band_ms[3] = {0, 0, 0};  // fill, f5, traceback of the last sf_fold_banded
+int g_band_B = 0, g_band_launches = 0;
+
+// Lanes per cell of diagonal d of a banded fill: as many as it takes to fill the device with the diagonal's cells (a
+// quarter of the lanes it holds at once: the diagonals follow each other closely), but no more than the cell has work for
+// (d split terms and up to 496 interior-loop candidates, eight terms a lane at least); a power of two, at most one wave.
+int band_group(int d, size_t cells) {
+  const int umax = std::min(SFD_MAXLOOP, d - 2 - (SFD_TURN + 1));
+  const int work = std::max(0, d - 2 * SFD_TURN - 2) + (umax >= 0 ? (umax + 1) * (umax + 2) / 2 : 0);
+  const size_t lanes = (size_t)g.n_cu * 512;
+  int G = 1;
+  while (G < 64 && (size_t)G * cells < lanes && G * 8 < work) G *= 2;
+  return G;
+}
+
+size_t band_linear_bytes(int L, int B) {
+  return 3 * ((size_t)L + 2) * 4        // DML ring
+         + ((size_t)L + 1) * 4          // f5
+         + SF_BAND_STACK_INTS(L) * 4    // traceback stack
+         + ((size_t)L + 1)              // structure
+         + ((size_t)L + 2)              // sequence
+         + ((size_t)B + 1) * 4          // hairpin initiation
+         + 4                            // energy
+         + 9 * ((size_t)L + 2);         // constraint: characters, int32 bracket partners and enclosing pairs
+}
+}  // namespace
+
+extern "C" {
+
+int sf_fold_banded_bytes(int L, int span, size_t *bytes) {
+  SF_ENTER();
+  if (L < 1 || L > SF_MAX_BANDED || span < 1 || !bytes) return SF_ERR_BAD_ARG;
+  const int B = std::min(span, L);
+  *bytes = 12 * (size_t)L * (size_t)B + band_linear_bytes(L, B);
+  return SF_OK;
+}
+
+int sf_fold_banded(const uint8_t *seq, int L, const char *cons, int32_t *mfe_out, char *db_out) {
+  int rc = check_ready();
+  if (rc) return rc;
+  if (!seq || L < 1 || L > SF_MAX_BANDED || g.max_bp_span < 1) return SF_ERR_BAD_ARG;
+  const int B = std::min(g.max_bp_span, L);
+  // the constraint, parsed here (sf_hc_parse with int32 positions); unbalanced brackets end the call before any launch
+  std::vector<int32_t> hpart, hencl;
+  std::vector<char> hc;
+  if (cons) {
+    hpart.assign((size_t)L + 2, 0);
+    hencl.assign((size_t)L + 2, 0);
+    hc.assign((size_t)L + 2, 0);
+    std::vector<int32_t> stack;
+    for (int i = 1; i <= L; i++) {
+      const char ch = cons[i - 1];
+      hc[i] = ch;
+      if (ch == ')') {
+        if (stack.empty()) return SF_ERR_CONSTRAINT;
+        const int o = stack.back();
+        stack.pop_back();
+        hpart[o] = i;
+        hpart[i] = o;
+      }
+      hencl[i] = stack.empty() ? 0 : stack.back();
+      if (ch == '(') stack.push_back(i);
+    }
+    if (!stack.empty()) return SF_ERR_CONSTRAINT;
+  }
+  const sf_params_blob *P = (const sf_params_blob *)g.slot[g.cur].src.data();  // the resident set as it was handed in
+  std::vector<uint8_t> hS((size_t)L + 2, 0);
+  for (int x = 0; x < L; x++) hS[x + 1] = sf_encode_nt(seq[x]);
+  std::vector<int32_t> hhp((size_t)B + 1);
+  for (int s = 0; s <= B; s++) hhp[s] = (s <= 30) ? P->hairpin[s] : P->hairpin[30] + (int)(P->lxc * log(s / 30.));
+
+  int32_t e = 0;  // (these outlive Bf: the copies into them are drained by its destructor on an early return)
+  std::vector<char> hdb(db_out ? (size_t)L + 1 : 0);
+  const size_t band = (size_t)L * (size_t)B;
+  LongBufs Bf;
+  Bf.who = "sf_fold_banded";
+  SfBand F;
+  memset(&F, 0, sizeof F);
+  F.L = L;
+  F.B = B;
+  void *p;
+  if ((rc = Bf.alloc(&p, band * sizeof(int32_t), "c"))) return rc;
+  F.c = (int32_t *)p;
+  if ((rc = Bf.alloc(&p, band * sizeof(int32_t), "fML"))) return rc;
+  F.fML = (int32_t *)p;
+  if ((rc = Bf.alloc(&p, band * sizeof(int32_t), "fML transposed"))) return rc;
+  F.fMLt = (int32_t *)p;
+  if ((rc = Bf.alloc(&p, 3 * ((size_t)L + 2) * sizeof(int32_t), "DML ring"))) return rc;
+  F.dml = (int32_t *)p;
+  if ((rc = Bf.alloc(&p, ((size_t)L + 1) * sizeof(int32_t), "f5"))) return rc;
+  F.f5 = (int32_t *)p;
+  if ((rc = Bf.alloc(&p, SF_BAND_STACK_INTS(L) * sizeof(int32_t), "traceback stack"))) return rc;
+  F.stk = (int32_t *)p;
+  if ((rc = Bf.alloc(&p, (size_t)L + 1, "structure"))) return rc;
+  F.db = (char *)p;
+  if ((rc = Bf.alloc(&p, (size_t)L + 2, "sequence"))) return rc;
+  F.S = (const uint8_t *)p;
+  HIPCHK(hipMemcpyAsync(p, hS.data(), (size_t)L + 2, hipMemcpyHostToDevice, g.stream));
+  if ((rc = Bf.alloc(&p, ((size_t)B + 1) * sizeof(int32_t), "hairpin table"))) return rc;
+  F.hp = (const int32_t *)p;
+  HIPCHK(hipMemcpyAsync(p, hhp.data(), ((size_t)B + 1) * sizeof(int32_t), hipMemcpyHostToDevice, g.stream));
+  if ((rc = Bf.alloc(&p, sizeof(int32_t), "energy"))) return rc;
+  int32_t *d_mfe = (int32_t *)p;
+  F.status = (int *)g.status.p;
+  if (cons) {
+    void *dc, *part, *encl;
+    if ((rc = Bf.alloc(&dc, (size_t)L + 2, "constraint"))) return rc;
+    if ((rc = Bf.alloc(&part, ((size_t)L + 2) * sizeof(int32_t), "bracket partners"))) return rc;
+    if ((rc = Bf.alloc(&encl, ((size_t)L + 2) * sizeof(int32_t), "enclosing pairs"))) return rc;
+    HIPCHK(hipMemcpyAsync(dc, hc.data(), (size_t)L + 2, hipMemcpyHostToDevice, g.stream));
+    HIPCHK(hipMemcpyAsync(part, hpart.data(), ((size_t)L + 2) * sizeof(int32_t), hipMemcpyHostToDevice, g.stream));
+    HIPCHK(hipMemcpyAsync(encl, hencl.data(), ((size_t)L + 2) * sizeof(int32_t), hipMemcpyHostToDevice, g.stream));
+    F.hc.c = (const char *)dc;
+    F.hc.partner = (const int32_t *)part;
+    F.hc.encl = (const int32_t *)encl;
+  }
+  for (auto &ev : Bf.ev) HIPCHK(hipEventCreate(&ev));
+  const SfDevParams *D = (const SfDevParams *)g.dP;
+  const int threads = 256;
+  int launches = 0;
+  HIPCHK(hipEventRecord(Bf.ev[0], g.stream));
+  for (int d = 0; d < B; d++) {
+    const size_t cells = (size_t)(L - d);
+    const int G = band_group(d, cells);
+    const int grid = (int)((cells * (size_t)G + threads - 1) / threads);
+    SF_LAUNCH(sf_band_fill_kernel, grid, threads, 0, g.stream, F, d, G, D);
+    launches++;
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(Bf.ev[1], g.stream));
+  SF_LAUNCH(sf_band_f5_kernel, 1, B <= 256 ? 64 : threads, 0, g.stream, F, D, d_mfe);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(Bf.ev[2], g.stream));
+  if (db_out) {
+    SF_LAUNCH(sf_band_trace_kernel, 1, threads, 0, g.stream, F, D);
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipEventRecord(Bf.ev[3], g.stream));
+  HIPCHK(hipMemcpyAsync(&e, d_mfe, sizeof e, hipMemcpyDeviceToHost, g.stream));
+  if (db_out) HIPCHK(hipMemcpyAsync(hdb.data(), F.db, (size_t)L + 1, hipMemcpyDeviceToHost, g.stream));
+  if ((rc = read_status(g.stream, false))) return rc;
+  if (mfe_out) *mfe_out = e;
+  if (db_out) memcpy(db_out, hdb.data(), (size_t)L + 1);
+  float ms[3] = {0, 0, 0};
+  for (int k = 0; k < 3; k++) HIPCHK(hipEventElapsedTime(&ms[k], Bf.ev[k], Bf.ev[k + 1]));
+  for (int k = 0; k < 3; k++) g_band_ms[k] = ms[k];
+  if (!db_out) g_band_ms[2] = 0.0;
+  g_band_B = B;
+  g_band_launches = launches;
+  return SF_OK;
+}
+
+int sf_fold_banded_times(double *fill_ms, double *f5_ms, double *trace_ms, int *band, int *fill_launches) {
+  SF_ENTER();
+  if (fill_ms) *fill_ms = g_band_ms[0];
+  if (f5_ms) *f5_ms = g_band_ms[1];
+  if (trace_ms) *trace_ms = g_band_ms[2];
+  if (band) *band = g_band_B;
+  if (fill_launches) *fill_launches = g_band_launches;
   return SF_OK;
 }
 

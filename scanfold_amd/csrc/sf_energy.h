@@ -230,6 +230,23 @@ __device__ __forceinline__ int sf_hc_type8(const SfHc8 &h, int t, int i, int j, 
   return t;
 }
 
+// The same for records of any length (sf_mfe_banded.hip.h): positions past 32 767 need int32 partners.  The host parses the
+// constraint (it walks every row for balance anyway) and uploads the three arrays, filled for 1..L.
+struct SfHc32 {
+  const char *c;           // 1-based (c[1..L]); null: no constraint
+  const int32_t *partner;  // 0: none
+  const int32_t *encl;     // 0: none
+};
+__device__ __forceinline__ int sf_hc_type32(const SfHc32 &h, int t, int i, int j, bool span_ok) {
+  if (!h.c) return t;
+  const int pi = h.partner[i], pj = h.partner[j];
+  if (pi || pj) return (pi == j && span_ok) ? (t ? t : 7) : 0;
+  const char ci = h.c[i], cj = h.c[j];
+  if (ci == 'x' || cj == 'x' || ci == '>' || cj == '<') return 0;
+  if (h.encl[i] != h.encl[j]) return 0;  // would cross a bracket pair
+  return t;
+}
+
 // ASCII or code -> code 0..4 (N,A,C,G,U)
 __device__ __host__ inline uint8_t sf_encode_nt(uint8_t c) {
   if (c <= 4) return c;

@@ -152,7 +152,7 @@ def read_reactivities(path):
     return vec
 
 
-def global_refold(seq, name, outname, temperature, dbn_file_path="AllDBN-global_refold.txt", ensemble=False):
+def global_refold(seq, name, outname, temperature, dbn_file_path="AllDBN-global_refold.txt", ensemble=False, span=0):
     """ScanFold.py:1509-1547 (--global_refold): a fresh RNA.md() at md.temperature = int(-t) — no --span, exactly as
     upstream — folds the whole record unconstrained and with line 3 of `<outname>.ScanFold.-1.dbn` / `.-2.dbn` as
     hc_add_from_db constraint, and writes the three records to `<outname>.<dbn_file_path>`; `<outname>.AllDBN.txt` is the
@@ -166,10 +166,14 @@ def global_refold(seq, name, outname, temperature, dbn_file_path="AllDBN-global_
     ensemble (--global_ensemble, not upstream): the partition function of the same three folds (one Engine.pf_long_batch
     call past SF_MAX_W where the library has it, else Engine.pf_long three times: the same numbers; scaled from each fold's
     MFE) into `<outname>.<dbn_file_path minus .txt>.ensemble.txt`, three records of a header line (ensemble free
-    energy, ED = mean base-pair distance to 2 decimals, centroid distance), the sequence and the centroid."""
+    energy, ED = mean base-pair distance to 2 decimals, centroid distance), the sequence and the centroid.
+    span (--global_span N, not upstream): the three folds run under max_bp_span = N in banded tables (Engine.fold_banded:
+    memory and work linear in the record's length, records past SF_MAX_LONG), and the header lines gain " span=N"."""
     from . import RNA
     md = RNA.md()
     md.temperature = int(temperature)
+    span = int(span or 0)
+    tail = " span=%d" % span if span > 0 else ""
     cons = []
     for tag in ("-1", "-2"):
         with open(outname + ".ScanFold." + tag + ".dbn") as f:
@@ -179,15 +183,20 @@ def global_refold(seq, name, outname, temperature, dbn_file_path="AllDBN-global_
     span0, params0 = eng.max_bp_span, eng.params
     had_facade_span, facade_span0 = hasattr(eng, "_span"), getattr(eng, "_span", 0)
     try:
-        eng.set_max_bp_span(0)  # (the scan's --span is engine state; the fresh md has none)
-        eng._span = 0
-        fc = RNA.fold_compound(seq, md)
-        fc.hc_add_from_db(cons[0])
-        s1, e1 = fc.mfe()
-        fc = RNA.fold_compound(seq, md)
-        fc.hc_add_from_db(cons[1])
-        s2, e2 = fc.mfe()
-        s0, e0 = RNA.fold_compound(seq, md).mfe()
+        eng.set_max_bp_span(span)  # (the scan's --span is engine state; the fresh md has none, or --global_span's)
+        eng._span = span
+        if span > 0:
+            eng.set_temperature(float(md.temperature))
+            (e1, s1), (e2, s2), (e0, s0) = (eng.fold_banded(seq, c) for c in (cons[0], cons[1], None))
+            e1, e2, e0 = RNA._f32(e1), RNA._f32(e2), RNA._f32(e0)
+        else:
+            fc = RNA.fold_compound(seq, md)
+            fc.hc_add_from_db(cons[0])
+            s1, e1 = fc.mfe()
+            fc = RNA.fold_compound(seq, md)
+            fc.hc_add_from_db(cons[1])
+            s2, e2 = fc.mfe()
+            s0, e0 = RNA.fold_compound(seq, md).mfe()
         ens = []
         if ensemble and len(seq) > _lib.SF_MAX_W and eng.has_pf_long_batch():
             # the three ensembles in the same launches; each row is pf_long's bit for bit
@@ -209,9 +218,9 @@ def global_refold(seq, name, outname, temperature, dbn_file_path="AllDBN-global_
         else:
             del eng._span
     with open(outname + "." + dbn_file_path, "w") as w:
-        w.write(">" + str(name) + "\tGlobal Full MFE=" + str(e0) + "\n" + seq + "\n" + s0 + "\n")
-        w.write(">" + str(name) + "\tRefolded with -1 constraints MFE=" + str(e1) + "\n" + seq + "\n" + s1 + "\n")
-        w.write(">" + str(name) + "\tRefolded with -2 constraints MFE=" + str(e2) + "\n" + seq + "\n" + s2 + "\n")
+        w.write(">" + str(name) + "\tGlobal Full MFE=" + str(e0) + tail + "\n" + seq + "\n" + s0 + "\n")
+        w.write(">" + str(name) + "\tRefolded with -1 constraints MFE=" + str(e1) + tail + "\n" + seq + "\n" + s1 + "\n")
+        w.write(">" + str(name) + "\tRefolded with -2 constraints MFE=" + str(e2) + tail + "\n" + seq + "\n" + s2 + "\n")
     if ensemble:
         stem = dbn_file_path[:-4] if dbn_file_path.endswith(".txt") else dbn_file_path
         with open(outname + "." + stem + ".ensemble.txt", "w") as w:
@@ -289,6 +298,9 @@ def build_parser():
                    help='Global refold option. Refold full sequence using Zavg <-1 and <-2 base pairs')
     p.add_argument('--global_ensemble', action='store_true',
                    help='with --global_refold: also write ensemble free energy, ED and centroid of the three whole-record folds')
+    p.add_argument('--global_span', type=int, default=None,
+                   help='not in upstream ScanFold: with --global_refold, fold the whole record under this max bp span in banded '
+                        'tables (memory and time linear in its length; records past 32767 nt)')
     p.add_argument('--global_zscore', action='store_true',
                    help='not in upstream ScanFold: z-score of the whole record (its MFE at -t, no --span, against -r shuffles of '
                         '--type seeded with --seed) into <output prefix>.global_zscore.txt; costs r + 1 whole-record folds')
@@ -317,6 +329,14 @@ def main(argv=None):
         raise ValueError("--global_refold refolds with the -1 / -2 dbn files of the Fold stage: not with -c 0 or --dont_fold")
     if args.global_ensemble and not args.global_refold:
         raise ValueError("--global_ensemble adds the partition function to the folds of --global_refold: give both")
+    if args.global_span is not None and (not args.global_refold or args.global_span < 1):
+        raise ValueError("--global_span N (N >= 1) sets the base-pair span of the folds of --global_refold: give both")
+    if args.global_span is not None and (args.global_ensemble or args.global_zscore):  # refused before any record is scanned
+        for read_name, seq in scanmod.read_fasta(args.filename):
+            if len(seq) > _lib.SF_MAX_LONG:
+                raise ValueError("--global_span: record %s has %d nt; %s has no banded form yet and stops at %d nt"
+                                 % (read_name, len(seq), "--global_ensemble (the partition function)" if args.global_ensemble
+                                    else "--global_zscore (the batched fold of the shuffles)", _lib.SF_MAX_LONG))
     if args.global_zscore and args.lri:
         raise ValueError("--global_zscore z-scores the record of a window scan: not with --lri")
     if args.global_zscore:  # refused before any record is scanned
@@ -392,7 +412,8 @@ def main(argv=None):
                 global_zscore(seq, args.name, outname, args.t, r, args.type, args.seed)
             if args.global_refold:
                 print("Refolding full sequence using ScanFold results as constraints...")
-                global_refold(seq, args.name, outname, args.t, args.dbn_file_path, ensemble=args.global_ensemble)
+                global_refold(seq, args.name, outname, args.t, args.dbn_file_path, ensemble=args.global_ensemble,
+                              span=args.global_span or 0)
             if args.c == 1 and not args.dont_extract:
                 with open(outname + ".ScanFold.-2.dbn") as f:
                     line = f.readlines()[2]
