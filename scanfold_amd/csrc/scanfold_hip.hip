@@ -1254,6 +1254,85 @@ int long_bind_rows(LongBufs &B, const LongPack &K, const LongRows &R, int s0, ui
   HIPCHK(hipGetLastError());
   return SF_OK;
 }
+// Hairpin initiation by loop size 0..n for the whole-record folds (the resident model's table only reaches SF_MAX_W + 1).
+std::vector<int32_t> long_hairpin_table(const sf_params_blob *P, int n) {
+  std::vector<int32_t> hp((size_t)n + 1);
+  for (int s = 0; s <= n; s++) hp[s] = (s <= 30) ? P->hairpin[s] : P->hairpin[30] + (int)(P->lxc * log(s / 30.));
+  return hp;
+}
+
+// One whole-record fold, the host side of sf_fold_long (State = SfLong) and sf_fold_banded (SfBand), after their argument
+// checks.  F comes in zeroed but for L (and B).  Allocates the three tables of `entries` cells and the linear arrays, uploads
+// the sequence and a hairpin table of n_hp + 1 entries, lets bind_hc(B, F) set F.hc, then runs fill(F, D, threads) (the
+// caller's loop over diagonals), f5_kernel in one workgroup of f5_threads and, with db_out, trace_kernel.  Energy and
+// structure reach the caller only when the status word is clean (the structure is staged in host memory until then); ms_out
+// takes the device-event times of the three phases.
+template <class State, class BindHc, class Fill>
+int whole_fold(const char *who, State &F, const uint8_t *seq, size_t entries, int n_hp, BindHc bind_hc, Fill fill,
+               void (*f5_kernel)(State, const SfDevParams *, int32_t *), int f5_threads,
+               void (*trace_kernel)(State, const SfDevParams *), int32_t *mfe_out, char *db_out, double ms_out[3]) {
+  int rc;
+  const int L = F.L;
+  const size_t nL = (size_t)L;
+  std::vector<uint8_t> hS(nL + 2, 0);
+  for (int x = 0; x < L; x++) hS[x + 1] = sf_encode_nt(seq[x]);
+  const std::vector<int32_t> hhp = long_hairpin_table((const sf_params_blob *)g.slot[g.cur].src.data(), n_hp);
+
+  int32_t e = 0;  // (these outlive B: the copies into them are drained by its destructor on an early return)
+  std::vector<char> hdb(db_out ? nL + 1 : 0);
+  LongBufs B;
+  B.who = who;
+  void *p;
+  if ((rc = B.alloc(&p, entries * sizeof(int32_t), "c"))) return rc;
+  F.c = (int32_t *)p;
+  if ((rc = B.alloc(&p, entries * sizeof(int32_t), "fML"))) return rc;
+  F.fML = (int32_t *)p;
+  if ((rc = B.alloc(&p, entries * sizeof(int32_t), "fML transposed"))) return rc;
+  F.fMLt = (int32_t *)p;
+  if ((rc = B.alloc(&p, 3 * (nL + 2) * sizeof(int32_t), "DML ring"))) return rc;
+  F.dml = (int32_t *)p;
+  if ((rc = B.alloc(&p, (nL + 1) * sizeof(int32_t), "f5"))) return rc;
+  F.f5 = (int32_t *)p;
+  if ((rc = B.alloc(&p, SF_LONG_STACK_INTS(L) * sizeof(int32_t), "traceback stack"))) return rc;
+  F.stk = (int32_t *)p;
+  if ((rc = B.alloc(&p, nL + 1, "structure"))) return rc;
+  F.db = (char *)p;
+  if ((rc = B.alloc(&p, nL + 2, "sequence"))) return rc;
+  F.S = (const uint8_t *)p;
+  HIPCHK(hipMemcpyAsync(p, hS.data(), nL + 2, hipMemcpyHostToDevice, g.stream));
+  if ((rc = B.alloc(&p, hhp.size() * sizeof(int32_t), "hairpin table"))) return rc;
+  F.hp = (const int32_t *)p;
+  HIPCHK(hipMemcpyAsync(p, hhp.data(), hhp.size() * sizeof(int32_t), hipMemcpyHostToDevice, g.stream));
+  if ((rc = B.alloc(&p, sizeof(int32_t), "energy"))) return rc;
+  int32_t *d_mfe = (int32_t *)p;
+  F.status = (int *)g.status.p;
+  if ((rc = bind_hc(B, F))) return rc;
+  for (auto &ev : B.ev) HIPCHK(hipEventCreate(&ev));
+  const SfDevParams *D = (const SfDevParams *)g.dP;
+  const int threads = 256;
+  HIPCHK(hipEventRecord(B.ev[0], g.stream));
+  fill(F, D, threads);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(B.ev[1], g.stream));
+  SF_LAUNCH(f5_kernel, 1, f5_threads, 0, g.stream, F, D, d_mfe);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(B.ev[2], g.stream));
+  if (db_out) {
+    SF_LAUNCH(trace_kernel, 1, threads, 0, g.stream, F, D);
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipEventRecord(B.ev[3], g.stream));
+  HIPCHK(hipMemcpyAsync(&e, d_mfe, sizeof e, hipMemcpyDeviceToHost, g.stream));
+  if (db_out) HIPCHK(hipMemcpyAsync(hdb.data(), F.db, nL + 1, hipMemcpyDeviceToHost, g.stream));
+  if ((rc = read_status(g.stream, false))) return rc;
+  if (mfe_out) *mfe_out = e;
+  if (db_out) memcpy(db_out, hdb.data(), nL + 1);
+  float ms[3] = {0, 0, 0};
+  for (int k = 0; k < 3; k++) HIPCHK(hipEventElapsedTime(&ms[k], B.ev[k], B.ev[k + 1]));
+  for (int k = 0; k < 3; k++) ms_out[k] = ms[k];
+  if (!db_out) ms_out[2] = 0.0;
+  return SF_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1264,44 +1343,13 @@ int sf_fold_long(const uint8_t *seq, int L, const char *cons, int32_t *mfe_out, 
   if (!seq || L < 1 || L > SF_MAX_LONG) return SF_ERR_BAD_ARG;
   bool noncanonical = false;  // (a type-7 bracket pair needs nothing special here: the int32 tables carry it)
   if (cons && (rc = scan_constraints(seq, cons, 1, L, &noncanonical))) return rc;
-  const sf_params_blob *P = (const sf_params_blob *)g.slot[g.cur].src.data();  // the resident set as it was handed in
-  std::vector<uint8_t> hS((size_t)L + 2, 0);
-  for (int x = 0; x < L; x++) hS[x + 1] = sf_encode_nt(seq[x]);
-  std::vector<int32_t> hhp((size_t)L + 1);
-  for (int s = 0; s <= L; s++) hhp[s] = (s <= 30) ? P->hairpin[s] : P->hairpin[30] + (int)(P->lxc * log(s / 30.));
-
-  int32_t e = 0;  // (outlives B: the copy into it is drained by B's destructor on an early return)
-  const size_t tri = SF_LONG_TRI(L);
-  LongBufs B;
   SfLong F;
   memset(&F, 0, sizeof F);
   F.L = L;
-  void *p;
-  if ((rc = B.alloc(&p, tri * sizeof(int32_t), "c"))) return rc;
-  F.c = (int32_t *)p;
-  if ((rc = B.alloc(&p, tri * sizeof(int32_t), "fML"))) return rc;
-  F.fML = (int32_t *)p;
-  if ((rc = B.alloc(&p, tri * sizeof(int32_t), "fML transposed"))) return rc;
-  F.fMLt = (int32_t *)p;
-  if ((rc = B.alloc(&p, 3 * ((size_t)L + 2) * sizeof(int32_t), "DML ring"))) return rc;
-  F.dml = (int32_t *)p;
-  if ((rc = B.alloc(&p, ((size_t)L + 1) * sizeof(int32_t), "f5"))) return rc;
-  F.f5 = (int32_t *)p;
-  if ((rc = B.alloc(&p, SF_LONG_STACK_INTS(L) * sizeof(int32_t), "traceback stack"))) return rc;
-  F.stk = (int32_t *)p;
-  if ((rc = B.alloc(&p, (size_t)L + 1, "structure"))) return rc;
-  F.db = (char *)p;
-  if ((rc = B.alloc(&p, (size_t)L + 2, "sequence"))) return rc;
-  F.S = (const uint8_t *)p;
-  HIPCHK(hipMemcpyAsync(p, hS.data(), (size_t)L + 2, hipMemcpyHostToDevice, g.stream));
-  if ((rc = B.alloc(&p, ((size_t)L + 1) * sizeof(int32_t), "hairpin table"))) return rc;
-  F.hp = (const int32_t *)p;
-  HIPCHK(hipMemcpyAsync(p, hhp.data(), ((size_t)L + 1) * sizeof(int32_t), hipMemcpyHostToDevice, g.stream));
-  if ((rc = B.alloc(&p, sizeof(int32_t), "energy"))) return rc;
-  int32_t *d_mfe = (int32_t *)p;
-  F.status = (int *)g.status.p;
-  F.hc.c = nullptr;
-  if (cons) {
+  // the constraint is parsed on the device, into int16 bracket partners and enclosing pairs
+  auto bind_hc = [&](LongBufs &B, SfLong &F) -> int {
+    if (!cons) return SF_OK;
+    int rc;
     void *src, *hc, *part, *encl, *stack;
     if ((rc = B.alloc(&src, (size_t)L, "constraint"))) return rc;
     if ((rc = B.alloc(&hc, (size_t)L + 2, "constraint"))) return rc;
@@ -1315,36 +1363,18 @@ int sf_fold_long(const uint8_t *seq, int L, const char *cons, int32_t *mfe_out, 
     F.hc.c = (const char *)hc;
     F.hc.partner = (const int16_t *)part;
     F.hc.encl = (const int16_t *)encl;
-  }
-  for (auto &e : B.ev) HIPCHK(hipEventCreate(&e));
-  const SfDevParams *D = (const SfDevParams *)g.dP;
-  const int threads = 256;
-  HIPCHK(hipEventRecord(B.ev[0], g.stream));
-  for (int d = 0; d < L; d++) {
-    const int G = long_group(d);
-    const size_t total = (size_t)(L - d) * (size_t)G;
-    const int grid = (int)((total + threads - 1) / threads);
-    SF_LAUNCH(sf_long_fill_kernel, grid, threads, 0, g.stream, F, d, G, D);
-  }
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(B.ev[1], g.stream));
-  SF_LAUNCH(sf_long_f5_kernel, 1, threads, 0, g.stream, F, D, d_mfe);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(B.ev[2], g.stream));
-  if (db_out) {
-    SF_LAUNCH(sf_long_trace_kernel, 1, threads, 0, g.stream, F, D);
-    HIPCHK(hipGetLastError());
-  }
-  HIPCHK(hipEventRecord(B.ev[3], g.stream));
-  HIPCHK(hipMemcpyAsync(&e, d_mfe, sizeof e, hipMemcpyDeviceToHost, g.stream));
-  if (db_out) HIPCHK(hipMemcpyAsync(db_out, F.db, (size_t)L + 1, hipMemcpyDeviceToHost, g.stream));
-  if ((rc = read_status(g.stream, false))) return rc;
-  if (mfe_out) *mfe_out = e;
-  float ms[3] = {0, 0, 0};
-  for (int k = 0; k < 3; k++) HIPCHK(hipEventElapsedTime(&ms[k], B.ev[k], B.ev[k + 1]));
-  for (int k = 0; k < 3; k++) g_long_ms[k] = ms[k];
-  if (!db_out) g_long_ms[2] = 0.0;
-  return SF_OK;
+    return SF_OK;
+  };
+  auto fill = [&](const SfLong &F, const SfDevParams *D, int threads) {
+    for (int d = 0; d < L; d++) {
+      const int G = long_group(d);
+      const size_t total = (size_t)(L - d) * (size_t)G;
+      const int grid = (int)((total + threads - 1) / threads);
+      SF_LAUNCH(sf_long_fill_kernel, grid, threads, 0, g.stream, F, d, G, D);
+    }
+  };
+  return whole_fold("sf_fold_long", F, seq, SF_LONG_TRI(L), L, bind_hc, fill, sf_long_f5_kernel, 256, sf_long_trace_kernel,
+                    mfe_out, db_out, g_long_ms);
 }
 
 int sf_fold_long_times(double *fill_ms, double *f5_ms, double *trace_ms) {
@@ -1377,7 +1407,7 @@ int band_group(int d, size_t cells) {
 size_t band_linear_bytes(int L, int B) {
   return 3 * ((size_t)L + 2) * 4        // DML ring
          + ((size_t)L + 1) * 4          // f5
-         + SF_BAND_STACK_INTS(L) * 4    // traceback stack
+         + SF_LONG_STACK_INTS(L) * 4    // traceback stack
          + ((size_t)L + 1)              // structure
          + ((size_t)L + 2)              // sequence
          + ((size_t)B + 1) * 4          // hairpin initiation
@@ -1424,46 +1454,13 @@ int sf_fold_banded(const uint8_t *seq, int L, const char *cons, int32_t *mfe_out
     }
     if (!stack.empty()) return SF_ERR_CONSTRAINT;
   }
-  const sf_params_blob *P = (const sf_params_blob *)g.slot[g.cur].src.data();  // the resident set as it was handed in
-  std::vector<uint8_t> hS((size_t)L + 2, 0);
-  for (int x = 0; x < L; x++) hS[x + 1] = sf_encode_nt(seq[x]);
-  std::vector<int32_t> hhp((size_t)B + 1);
-  for (int s = 0; s <= B; s++) hhp[s] = (s <= 30) ? P->hairpin[s] : P->hairpin[30] + (int)(P->lxc * log(s / 30.));
-
-  int32_t e = 0;  // (these outlive Bf: the copies into them are drained by its destructor on an early return)
-  std::vector<char> hdb(db_out ? (size_t)L + 1 : 0);
-  const size_t band = (size_t)L * (size_t)B;
-  LongBufs Bf;
-  Bf.who = "sf_fold_banded";
   SfBand F;
   memset(&F, 0, sizeof F);
   F.L = L;
   F.B = B;
-  void *p;
-  if ((rc = Bf.alloc(&p, band * sizeof(int32_t), "c"))) return rc;
-  F.c = (int32_t *)p;
-  if ((rc = Bf.alloc(&p, band * sizeof(int32_t), "fML"))) return rc;
-  F.fML = (int32_t *)p;
-  if ((rc = Bf.alloc(&p, band * sizeof(int32_t), "fML transposed"))) return rc;
-  F.fMLt = (int32_t *)p;
-  if ((rc = Bf.alloc(&p, 3 * ((size_t)L + 2) * sizeof(int32_t), "DML ring"))) return rc;
-  F.dml = (int32_t *)p;
-  if ((rc = Bf.alloc(&p, ((size_t)L + 1) * sizeof(int32_t), "f5"))) return rc;
-  F.f5 = (int32_t *)p;
-  if ((rc = Bf.alloc(&p, SF_BAND_STACK_INTS(L) * sizeof(int32_t), "traceback stack"))) return rc;
-  F.stk = (int32_t *)p;
-  if ((rc = Bf.alloc(&p, (size_t)L + 1, "structure"))) return rc;
-  F.db = (char *)p;
-  if ((rc = Bf.alloc(&p, (size_t)L + 2, "sequence"))) return rc;
-  F.S = (const uint8_t *)p;
-  HIPCHK(hipMemcpyAsync(p, hS.data(), (size_t)L + 2, hipMemcpyHostToDevice, g.stream));
-  if ((rc = Bf.alloc(&p, ((size_t)B + 1) * sizeof(int32_t), "hairpin table"))) return rc;
-  F.hp = (const int32_t *)p;
-  HIPCHK(hipMemcpyAsync(p, hhp.data(), ((size_t)B + 1) * sizeof(int32_t), hipMemcpyHostToDevice, g.stream));
-  if ((rc = Bf.alloc(&p, sizeof(int32_t), "energy"))) return rc;
-  int32_t *d_mfe = (int32_t *)p;
-  F.status = (int *)g.status.p;
-  if (cons) {
+  auto bind_hc = [&](LongBufs &Bf, SfBand &F) -> int {
+    if (!cons) return SF_OK;
+    int rc;
     void *dc, *part, *encl;
     if ((rc = Bf.alloc(&dc, (size_t)L + 2, "constraint"))) return rc;
     if ((rc = Bf.alloc(&part, ((size_t)L + 2) * sizeof(int32_t), "bracket partners"))) return rc;
@@ -1474,40 +1471,21 @@ int sf_fold_banded(const uint8_t *seq, int L, const char *cons, int32_t *mfe_out
     F.hc.c = (const char *)dc;
     F.hc.partner = (const int32_t *)part;
     F.hc.encl = (const int32_t *)encl;
-  }
-  for (auto &ev : Bf.ev) HIPCHK(hipEventCreate(&ev));
-  const SfDevParams *D = (const SfDevParams *)g.dP;
-  const int threads = 256;
-  int launches = 0;
-  HIPCHK(hipEventRecord(Bf.ev[0], g.stream));
-  for (int d = 0; d < B; d++) {
-    const size_t cells = (size_t)(L - d);
-    const int G = band_group(d, cells);
-    const int grid = (int)((cells * (size_t)G + threads - 1) / threads);
-    SF_LAUNCH(sf_band_fill_kernel, grid, threads, 0, g.stream, F, d, G, D);
-    launches++;
-  }
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(Bf.ev[1], g.stream));
-  SF_LAUNCH(sf_band_f5_kernel, 1, B <= 256 ? 64 : threads, 0, g.stream, F, D, d_mfe);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(Bf.ev[2], g.stream));
-  if (db_out) {
-    SF_LAUNCH(sf_band_trace_kernel, 1, threads, 0, g.stream, F, D);
-    HIPCHK(hipGetLastError());
-  }
-  HIPCHK(hipEventRecord(Bf.ev[3], g.stream));
-  HIPCHK(hipMemcpyAsync(&e, d_mfe, sizeof e, hipMemcpyDeviceToHost, g.stream));
-  if (db_out) HIPCHK(hipMemcpyAsync(hdb.data(), F.db, (size_t)L + 1, hipMemcpyDeviceToHost, g.stream));
-  if ((rc = read_status(g.stream, false))) return rc;
-  if (mfe_out) *mfe_out = e;
-  if (db_out) memcpy(db_out, hdb.data(), (size_t)L + 1);
-  float ms[3] = {0, 0, 0};
-  for (int k = 0; k < 3; k++) HIPCHK(hipEventElapsedTime(&ms[k], Bf.ev[k], Bf.ev[k + 1]));
-  for (int k = 0; k < 3; k++) g_band_ms[k] = ms[k];
-  if (!db_out) g_band_ms[2] = 0.0;
+    return SF_OK;
+  };
+  auto fill = [&](const SfBand &F, const SfDevParams *D, int threads) {
+    for (int d = 0; d < B; d++) {
+      const size_t cells = (size_t)(L - d);
+      const int G = band_group(d, cells);
+      const int grid = (int)((cells * (size_t)G + threads - 1) / threads);
+      SF_LAUNCH(sf_band_fill_kernel, grid, threads, 0, g.stream, F, d, G, D);
+    }
+  };
+  rc = whole_fold("sf_fold_banded", F, seq, (size_t)L * (size_t)B, B, bind_hc, fill, sf_band_f5_kernel, B <= 256 ? 64 : 256,
+                  sf_band_trace_kernel, mfe_out, db_out, g_band_ms);
+  if (rc) return rc;
   g_band_B = B;
-  g_band_launches = launches;
+  g_band_launches = B;  // one fill launch per diagonal
   return SF_OK;
 }
 
@@ -1550,8 +1528,7 @@ int long_batch_chunk(const LongRows &R, int s0, int n, int32_t *e_host, char *db
   const size_t n_i32 = o_stk + (trace ? n_stk : 0);
   const size_t o_db = K.o_end, n_u8 = o_db + (trace ? n_L + (size_t)n : 0);
 
-  std::vector<int32_t> hhp((size_t)Lmax + 1);
-  for (int s = 0; s <= Lmax; s++) hhp[s] = (s <= 30) ? P->hairpin[s] : P->hairpin[30] + (int)(P->lxc * log(s / 30.));
+  const std::vector<int32_t> hhp = long_hairpin_table(P, Lmax);
   std::vector<SfLong> hF((size_t)n);
 
   LongBufs B;

@@ -220,7 +220,9 @@ __device__ inline int sf_hc_parse8(int W, const char *c, uint8_t *partner, uint8
   }
   return bad || top != 0;
 }
-__device__ __forceinline__ int sf_hc_type8(const SfHc8 &h, int t, int i, int j, bool span_ok) {
+// sf_hc_type for SfHc8 and for SfHc32 below (H: either).  SfHc keeps its own: in this form it compiles to other code.
+template <class H>
+__device__ __forceinline__ int sf_hc_type_of(const H &h, int t, int i, int j, bool span_ok) {
   if (!h.c) return t;
   const int pi = h.partner[i], pj = h.partner[j];
   if (pi || pj) return (pi == j && span_ok) ? (t ? t : 7) : 0;
@@ -237,15 +239,6 @@ struct SfHc32 {
   const int32_t *partner;  // 0: none
   const int32_t *encl;     // 0: none
 };
-__device__ __forceinline__ int sf_hc_type32(const SfHc32 &h, int t, int i, int j, bool span_ok) {
-  if (!h.c) return t;
-  const int pi = h.partner[i], pj = h.partner[j];
-  if (pi || pj) return (pi == j && span_ok) ? (t ? t : 7) : 0;
-  const char ci = h.c[i], cj = h.c[j];
-  if (ci == 'x' || cj == 'x' || ci == '>' || cj == '<') return 0;
-  if (h.encl[i] != h.encl[j]) return 0;  // would cross a bracket pair
-  return t;
-}
 
 // ASCII or code -> code 0..4 (N,A,C,G,U)
 __device__ __host__ inline uint8_t sf_encode_nt(uint8_t c) {

@@ -527,7 +527,7 @@ __device__ __forceinline__ void sf_fast_cell(const SfFastCtx &X, const int d, co
     // The pairs enclosed by (i,j) keep their sequence-only types in the candidate look-ups: a pair the constraint
     // forbids has c = "none" and never wins.  A bracket pair of non-complementary bases (type 7) has no row in the int16
     // tables: such a fold goes to the exact kernel through the overflow list (the host routes those windows there anyway).
-    type = sf_hc_type8(X.hc, type, i, j, d <= X.maxd);
+    type = sf_hc_type_of(X.hc, type, i, j, d <= X.maxd);
     if (type == 7) { type = 0; ovf = 1; }
   }
   const int si1 = S[i + 1], sj1 = S[j - 1];

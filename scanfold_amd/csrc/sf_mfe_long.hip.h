@@ -10,8 +10,8 @@
 // ordering between workgroups comes from kernel boundaries (no grid barrier).  A cell is handled by a group of G lanes
 // (G a power of two <= 64, chosen per diagonal by the host: 1 lane while the split is short, up to a whole wave on the late,
 // short diagonals whose cells have up to L split terms each); the group's minimum is a butterfly of __shfl_xor inside the wave.
-// Then f5 (sequential in j) in one workgroup that reduces over i for each j, then the traceback in one workgroup, which
-// searches each step's candidates in parallel and takes the first one in the oracle's order.
+// Then f5 (sequential in j) in one workgroup that reduces over i for each j, then the traceback in one workgroup: sft_trace
+// of sf_mfe_trace.hip.h, which the banded fold instantiates too; the energy helpers of a cell (sft_*) live there as well.
 //
 // Layout (int32, 64-bit offsets throughout; a triangle holds L(L+1)/2 entries):
 //   fML   row-major upper triangle: row i holds j = i..L        FR(i, j) = (i-1)L - (i-1)(i-2)/2 + (j-i)
@@ -23,10 +23,9 @@
 // Device memory of one call (bytes):  12 * L(L+1)/2  (c, fML, fMLt)  +  12 (L+2)  (DML ring)  +  ~68 L  (sequence, hairpin
 // initiation, constraint arrays, f5, traceback stack, structure).  L = 29 903: 5.37 GB; L = 32 767: 6.44 GB.
 #pragma once
-#include "sf_mfe_full.hip.h"
+#include "sf_mfe_trace.hip.h"
 
 #define SF_LONG_TRI(L) ((size_t)(L) * ((size_t)(L) + 1) / 2)
-#define SF_LONG_STACK_INTS(L) (3 * (4 * (size_t)(L) + 8))
 
 __device__ __forceinline__ size_t sfl_row(int L, int i, int j) {  // row-major triangle (fML)
   const size_t a = (size_t)(i - 1);
@@ -48,28 +47,16 @@ struct SfLong {
   int *status;
 };
 
-__device__ __forceinline__ int sfl_type(const SfDevParams *D, const SfLong &F, int a, int b) {
+// the layout as sf_mfe_trace.hip.h's templates see it
+__device__ __forceinline__ int sft_type(const SfDevParams *D, const SfLong &F, int a, int b) {
   const bool ok = b - a <= D->max_pair_dist;
   return sf_hc_type(F.hc, ok ? D->pair[F.S[a]][F.S[b]] : 0, a, b, ok);
 }
-__device__ __forceinline__ int sfl_hairpin(const SfDevParams *D, const SfLong &F, int i, int j, int type) {
-  const int size = j - i - 1;
-  if (size <= SF_MAX_W + 1) return sfd_hairpin(D, F.S, i, j, type);
-  return F.hp[size] + D->P.mismatchH[type][F.S[i + 1]][F.S[j - 1]];  // (no special hairpin is that long)
-}
-__device__ __forceinline__ int sfl_ext(const SfDevParams *D, const SfLong &F, int type, int i, int j) {
-  return sfd_extloop(D, type, i > 1 ? F.S[i - 1] : -1, j < F.L ? F.S[j + 1] : -1);
-}
-__device__ __forceinline__ int sfl_mlstem_out(const SfDevParams *D, const SfLong &F, int type, int i, int j) {
-  return sfd_mlstem(D, type, i > 1 ? F.S[i - 1] : -1, j < F.L ? F.S[j + 1] : -1);
-}
-// interior loop (i, j) -> (p, q) with u1 / u2 unpaired bases; SFD_INF if (p, q) cannot pair
-__device__ __forceinline__ int sfl_intloop(const SfDevParams *D, const SfLong &F, int i, int j, int type, int u1, int u2) {
-  const int p = i + 1 + u1, q = j - 1 - u2;
-  const int t2 = sfl_type(D, F, p, q);
-  if (!t2) return SFD_INF;
-  return sfd_intloop(D, u1, u2, type, sfd_rtype(t2), F.S[i + 1], F.S[j - 1], F.S[p - 1], F.S[q + 1]) + F.c[sfl_col(q, p)];
-}
+__device__ __forceinline__ size_t sft_row(const SfLong &F, int i, int j) { return sfl_row(F.L, i, j); }
+__device__ __forceinline__ size_t sft_col(const SfLong &, int j, int i) { return sfl_col(j, i); }
+__device__ __forceinline__ const int32_t *sft_colp(const SfLong &, const int32_t *t, int j) { return t + sfl_col(j, 1) - 1; }
+__device__ __forceinline__ int sft_lo(const SfLong &, int) { return 1; }
+__device__ __forceinline__ bool sft_in(const SfLong &, int, int) { return true; }
 
 // The bracket partners and enclosing pairs of the constraint (sf_hc_parse) into device memory; one thread.
 __global__ void sf_long_hc_kernel(const char *src, int L, char *c, int16_t *partner, int16_t *encl, int16_t *stack, int *status) {
@@ -95,16 +82,16 @@ __device__ __forceinline__ void sfl_fill_cell(const SfLong &F, int d, int G, int
   const sf_params_blob &P = D->P;
   int type = 0, e = SFD_INF;
   if (valid) {
-    type = sfl_type(D, F, i, j);  // max_bp_span, hard constraint
+    type = sft_type(D, F, i, j);  // max_bp_span, hard constraint
     if (type) {
       if (r == 0) {
-        e = sfl_hairpin(D, F, i, j, type);
+        e = sft_hairpin(D, F, i, j, type);
         const int dml = F.dml[(size_t)((d - 2) % 3) * (size_t)(L + 2) + i + 1];
         if (dml < SFD_INF) e = sfd_min(e, dml + sfd_mlstem(D, sfd_rtype(type), F.S[j - 1], F.S[i + 1]) + P.MLclosing);
       }
       const int umax = sfd_min(SFD_MAXLOOP, d - 2 - (SFD_TURN + 1));
       for (int u1 = 0; u1 <= umax; u1++)
-        for (int u2 = r; u2 <= umax - u1; u2 += G) e = sfd_min(e, sfl_intloop(D, F, i, j, type, u1, u2));
+        for (int u2 = r; u2 <= umax - u1; u2 += G) e = sfd_min(e, sft_intloop(D, F, i, j, type, u1, u2));
     }
   }
   int dec = SFD_INF;
@@ -138,7 +125,7 @@ __device__ __forceinline__ void sfl_fill_cell(const SfLong &F, int d, int G, int
     const int fa = F.fML[sfl_row(L, i + 1, j)], fb = F.fML[sfl_row(L, i, j - 1)];
     if (fa < SFD_INF) f = sfd_min(f, fa + P.MLbase);
     if (fb < SFD_INF) f = sfd_min(f, fb + P.MLbase);
-    if (type) f = sfd_min(f, cij + sfl_mlstem_out(D, F, type, i, j));
+    if (type) f = sfd_min(f, cij + sft_mlstem_out(D, F, type, i, j));
     dml_d[i] = dec;
     f = sfd_min(f, dec);
     F.fML[sfl_row(L, i, j)] = f;
@@ -162,8 +149,8 @@ __device__ __forceinline__ void sfl_f5(const SfLong &F, const SfDevParams *__res
     int v = SFD_INF;
     const int32_t *cj = F.c + sfl_col(j, 1);  // cj[i - 1] = c[i][j]
     for (int i = tid + 1; i + SFD_TURN + 1 <= j; i += blockDim.x) {
-      const int type = sfl_type(D, F, i, j);
-      if (type) v = sfd_min(v, F.f5[i - 1] + cj[i - 1] + sfl_ext(D, F, type, i, j));
+      const int type = sft_type(D, F, i, j);
+      if (type) v = sfd_min(v, F.f5[i - 1] + cj[i - 1] + sft_ext(D, F, type, i, j));
     }
     v = sf_block_min(v, red);
     if (tid == 0) F.f5[j] = sfd_min(F.f5[j - 1], v);
@@ -172,131 +159,4 @@ __device__ __forceinline__ void sfl_f5(const SfLong &F, const SfDevParams *__res
   if (tid == 0 && mfe_out) *mfe_out = F.f5[L];
 }
 __global__ void sf_long_f5_kernel(SfLong F, const SfDevParams *__restrict__ D, int32_t *mfe_out) { sfl_f5(F, D, mfe_out); }
-
-// Traceback in one workgroup (the oracle's mfe_traceback step by step).  Thread 0 keeps the stack and the nibbling loops; each
-// search over candidates is spread over the workgroup and takes the first match in the oracle's order (a block minimum over
-// the candidate's position in that order).
-__device__ __forceinline__ void sfl_trace(const SfLong &F, const SfDevParams *__restrict__ D) {
-  __shared__ int red[16];
-  __shared__ int sh_i, sh_j, sh_ml, sh_s, sh_bad, sh_pair;
-  const int tid = threadIdx.x, nt = blockDim.x, L = F.L;
-  const sf_params_blob &P = D->P;
-  const int32_t *f5 = F.f5;
-  int32_t *stk = F.stk;
-  for (int x = tid; x < L; x += nt) F.db[x] = '.';
-  if (tid == 0) {
-    F.db[L] = 0;
-    stk[0] = 1; stk[1] = L; stk[2] = 0;
-    sh_s = 1;
-    sh_bad = 0;
-  }
-  __syncthreads();
-  for (;;) {
-    if (sh_s == 0 || sh_bad) break;
-    __syncthreads();  // (every thread has read sh_s / sh_bad before thread 0 changes them)
-    if (tid == 0) {
-      const int s = --sh_s;
-      int i = stk[3 * s], j = stk[3 * s + 1];
-      const int ml = stk[3 * s + 2];
-      int pair = 0;
-      if (ml == 0) {
-        while (j > 0 && f5[j] == f5[j - 1]) j--;  // 3' end unpaired
-      } else if (j - i < SFD_TURN + 1) {
-        sh_bad = 1;
-      } else {
-        while (j - i > SFD_TURN + 1 && F.fML[sfl_row(L, i, j - 1)] < SFD_INF &&
-               F.fML[sfl_row(L, i, j)] == F.fML[sfl_row(L, i, j - 1)] + P.MLbase) j--;
-        while (j - i > SFD_TURN + 1 && F.fML[sfl_row(L, i + 1, j)] < SFD_INF &&
-               F.fML[sfl_row(L, i, j)] == F.fML[sfl_row(L, i + 1, j)] + P.MLbase) i++;
-        const int type = sfl_type(D, F, i, j);
-        pair = type && F.fML[sfl_row(L, i, j)] == F.c[sfl_col(j, i)] + sfl_mlstem_out(D, F, type, i, j);
-      }
-      sh_i = i; sh_j = j; sh_ml = ml; sh_pair = pair;
-    }
-    __syncthreads();
-    if (sh_bad) break;
-    int i = sh_i, j = sh_j;
-    const int ml = sh_ml;
-    bool have_pair = sh_pair != 0;
-    if (ml == 0) {
-      if (j < SFD_TURN + 2) continue;
-      // exterior stem (k, j): k from j-TURN-1 downwards, the first match = the largest k
-      const int fij = f5[j];
-      const int32_t *cj = F.c + sfl_col(j, 1);
-      int best = SFD_INF;
-      for (int k = j - SFD_TURN - 1 - tid; k >= 1; k -= nt) {
-        const int type = sfl_type(D, F, k, j);
-        if (type && fij == f5[k - 1] + cj[k - 1] + sfl_ext(D, F, type, k, j)) { best = -k; break; }
-      }
-      best = sf_block_min(best, red);
-      if (best == SFD_INF) { if (tid == 0) sh_bad = 1; __syncthreads(); break; }
-      const int k = -best;
-      if (tid == 0) {
-        const int s = sh_s++;
-        stk[3 * s] = 1; stk[3 * s + 1] = k - 1; stk[3 * s + 2] = 0;
-      }
-      i = k;
-      have_pair = true;
-    } else if (!have_pair) {
-      // split of fML[i][j] with ascending k
-      const int fij = F.fML[sfl_row(L, i, j)];
-      const int32_t *a = F.fML + sfl_row(L, i, i), *b = F.fMLt + sfl_col(j, 1);
-      int best = SFD_INF;
-      for (int k = i + SFD_TURN + 1 + tid; k <= j - SFD_TURN - 2; k += nt) {
-        const int x = a[k - i], y = b[k];
-        if (x < SFD_INF && y < SFD_INF && fij == x + y) { best = k; break; }
-      }
-      best = sf_block_min(best, red);
-      if (best == SFD_INF) { if (tid == 0) sh_bad = 1; __syncthreads(); break; }
-      if (tid == 0) {
-        const int s = sh_s;
-        stk[3 * s] = i; stk[3 * s + 1] = best; stk[3 * s + 2] = 1;
-        stk[3 * s + 3] = best + 1; stk[3 * s + 4] = j; stk[3 * s + 5] = 1;
-        sh_s = s + 2;
-      }
-      __syncthreads();
-      continue;
-    }
-    while (have_pair) {
-      if (tid == 0) { F.db[i - 1] = '('; F.db[j - 1] = ')'; }
-      const int type = sfl_type(D, F, i, j);
-      const int cij = F.c[sfl_col(j, i)];
-      if (cij == sfl_hairpin(D, F, i, j, type)) break;
-      // interior loops: p ascending, then q descending = (u1, u2) in lexicographic order
-      const int d = j - i;
-      const int umax = sfd_min(SFD_MAXLOOP, d - 2 - (SFD_TURN + 1));
-      int best = SFD_INF;
-      for (int t = tid; t < 32 * 32; t += nt) {
-        const int u1 = t >> 5, u2 = t & 31;
-        if (u1 + u2 > umax) continue;
-        if (cij == sfl_intloop(D, F, i, j, type, u1, u2)) { best = t; break; }
-      }
-      best = sf_block_min(best, red);
-      if (best != SFD_INF) {
-        i = i + 1 + (best >> 5);
-        j = j - 1 - (best & 31);
-        continue;
-      }
-      // multiloop closed by (i, j): split of fML[i+1][j-1] with ascending k
-      const int mm = P.MLclosing + sfd_mlstem(D, sfd_rtype(type), F.S[j - 1], F.S[i + 1]);
-      const int32_t *a = F.fML + sfl_row(L, i + 1, i + 1), *b = F.fMLt + sfl_col(j - 1, 1);
-      for (int k = i + 1 + SFD_TURN + 1 + tid; k <= j - 1 - SFD_TURN - 2; k += nt) {
-        const int x = a[k - i - 1], y = b[k];
-        if (x < SFD_INF && y < SFD_INF && cij == x + y + mm) { best = k; break; }
-      }
-      best = sf_block_min(best, red);
-      if (best == SFD_INF) {
-        if (tid == 0) sh_bad = 1;
-      } else if (tid == 0) {
-        const int s = sh_s;
-        stk[3 * s] = i + 1; stk[3 * s + 1] = best; stk[3 * s + 2] = 1;
-        stk[3 * s + 3] = best + 1; stk[3 * s + 4] = j - 1; stk[3 * s + 5] = 1;
-        sh_s = s + 2;
-      }
-      break;
-    }
-    __syncthreads();
-  }
-  if (tid == 0 && sh_bad) atomicOr(F.status, 1);
-}
-__global__ void sf_long_trace_kernel(SfLong F, const SfDevParams *__restrict__ D) { sfl_trace(F, D); }
+__global__ void sf_long_trace_kernel(SfLong F, const SfDevParams *__restrict__ D) { sft_trace(F, D); }

@@ -3,8 +3,8 @@
 // device idle — a diagonal of a 1 000-nt fold has at most 1 000 x G lanes of work.
 //
 // State: a device array of SfLong, one per sequence of the chunk; its tables are slices of a few allocations the host makes
-// per chunk.  Cell body, f5 and traceback are sf_mfe_long.hip.h's own functions (sfl_fill_cell, sfl_f5, sfl_trace), so
-// energies and structures are sf_fold_long's, byte for byte.
+// per chunk.  Cell body and f5 are sf_mfe_long.hip.h's own functions (sfl_fill_cell, sfl_f5), the traceback is
+// sf_mfe_trace.hip.h's sft_trace as sf_fold_long instantiates it, so energies and structures are sf_fold_long's, byte for byte.
 //
 // Fill: one launch per diagonal d = 0 .. Lmax - 1 covers every sequence.  The grid stays one-dimensional: with
 // bps = ceil((Lmax - d) G / 256) workgroups per sequence, workgroup b works on sequence b / bps, so every lane of a wave
@@ -39,5 +39,5 @@ __global__ void sf_longb_f5_kernel(const SfLong *__restrict__ Fs, const SfDevPar
 
 __global__ void sf_longb_trace_kernel(const SfLong *__restrict__ Fs, const SfDevParams *__restrict__ D) {
   const SfLong F = Fs[blockIdx.x];
-  sfl_trace(F, D);
+  sft_trace(F, D);
 }

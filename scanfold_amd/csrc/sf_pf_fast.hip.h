@@ -81,7 +81,7 @@ __global__ __launch_bounds__(NT, 2) void sf_pf_fast_kernel(const uint8_t *__rest
 // triangular, diagonal-major: diagonal d holds the cells i = 1..W-d
 #define PT(tab, d, i) tab[(d)*W - ((d) * ((d)-1)) / 2 + (i)-1]
 // the pair type of a cell's OWN pair (a, b): sequence, max_bp_span and — HC — the fold's constraint
-#define OWNT(Dp, a, b) (HC ? sf_hc_type8(hc, ((b) - (a) <= (Dp)->max_pair_dist ? (Dp)->pair[S[a]][S[b]] : 0), (a), (b), (b) - (a) <= (Dp)->max_pair_dist) \
+#define OWNT(Dp, a, b) (HC ? sf_hc_type_of(hc, ((b) - (a) <= (Dp)->max_pair_dist ? (Dp)->pair[S[a]][S[b]] : 0), (a), (b), (b) - (a) <= (Dp)->max_pair_dist) \
                            : ((b) - (a) <= (Dp)->max_pair_dist ? (Dp)->pair[S[a]][S[b]] : 0))
   for (int x = threadIdx.x; x <= W + 1; x += NT) mlbS[x] = X->mlbase_pow[x];  // (read with per-lane indices in the cooperative sums)
   const double *mlb = mlbS;

@@ -206,7 +206,7 @@ __global__ __launch_bounds__(SF_PFL_NT) void sf_pf_lds_kernel(const uint8_t *__r
 #define DERP(kind, col) (DER + ((kind)*4 + ((col)&3)) * RP + SF_PFL_PAD)
 #define PAIR(a, b) PT8[(a)*8 + (b)]
 // pair type of the cell itself: none beyond RNA.md().max_bp_span
-#define OWN(a, b) sf_hc_type8(hc, (((b) - (a)) <= maxd ? PAIR(S[a], S[b]) : 0), (a), (b), ((b) - (a)) <= maxd)
+#define OWN(a, b) sf_hc_type_of(hc, (((b) - (a)) <= maxd ? PAIR(S[a], S[b]) : 0), (a), (b), ((b) - (a)) <= maxd)
   const double xTAU = X->TermAU;
   const double xMLbase = X->MLbase;
   const int maxd = D->max_pair_dist;
