@@ -141,6 +141,15 @@ SF_DUPLEX_NONE = _header_define("scanfold_hip_duplex.h", "SF_DUPLEX_NONE")  # "e
 SF_DUPLEX_SKIPPED = _header_value("scanfold_hip_duplex.h", "SF_DUPLEX_SKIPPED")  # dense scan: left out by the distance test
 SF_ERR_DUPLEX_HITS = _header_value("scanfold_hip_duplex.h", "SF_ERR_DUPLEX_HITS")
 
+# Engine._need's arguments: an entry point only libscanfold_hip.so exports, and what needs it
+_FOLD_LONG = ("sf_fold_long", "whole-record folds")
+_FOLD_BANDED = ("sf_fold_banded", "whole-record folds under a base-pair span in banded tables")
+_FOLD_LONG_BATCH = ("sf_fold_long_batch", "folds of sequences past %d nt" % SF_MAX_W)
+_PF_LONG = ("sf_pf_long", "whole-record partition functions")
+_PF_LONG_BATCH = ("sf_pf_long_batch", "partition functions of many sequences past %d nt" % SF_MAX_W)
+_DUPLEX = ("duplex entry points (sf_duplex_batch, sf_lri_scan, sf_lri_background)", "duplex folds and --lri",
+           tuple(_DUPLEX_EXPORTS))
+
 
 def _share_hip_runtime_with_torch():
     """PyTorch wheels bundle their own libamdhip64 (same SONAME, different file name).  Two HIP runtimes in
@@ -190,13 +199,54 @@ def seqs_to_array(seqs, W=None):
         if arr.ndim != 2:
             raise ValueError("sequence array must be 2-D (n, W)")
         return arr
-    seqs = [s if isinstance(s, (bytes, bytearray)) else str(s).encode("ascii") for s in seqs]
+    seqs = [_ascii(s) for s in seqs]
     if not seqs:
         return np.zeros((0, W or 1), dtype=np.uint8)
     W = len(seqs[0])
     if any(len(s) != W for s in seqs):
         raise ValueError("all sequences of one batch must have the same length")
     return np.frombuffer(b"".join(seqs), dtype=np.uint8).reshape(len(seqs), W)
+
+
+def _ascii(s):
+    """str, bytes or bytearray -> the bytes the C ABI reads"""
+    return s if isinstance(s, (bytes, bytearray)) else str(s).encode("ascii")
+
+
+def _record(seq, cons):
+    """one sequence and its constraint string or None -> (uint8 array, L, constraint bytes or None)"""
+    s = _ascii(seq)
+    L = len(s)
+    c = None if cons is None else bytes(_ascii(cons))
+    if c is not None and len(c) != L:
+        raise ValueError("constraint string and sequence differ in length")
+    return (np.frombuffer(bytes(s), dtype=np.uint8) if L else np.zeros(1, dtype=np.uint8)), L, c
+
+
+def _pad(rows, ld, fill=0):
+    """byte strings of any lengths (None: an empty one) -> uint8 (n, ld), every row filled up with `fill`"""
+    arr = np.full((len(rows), ld), fill, dtype=np.uint8)
+    for k, s in enumerate(rows):
+        if s:
+            arr[k, :len(s)] = np.frombuffer(bytes(s), dtype=np.uint8)
+    return arr
+
+
+def _ragged_rows(seqs, cons=None):
+    """sequences of any lengths and None or one constraint item per sequence (a string of its length, or None) ->
+    (uint8 (n, ld), int32 lengths, ld, uint8 (n, ld) of constraint rows filled up with dots, or None where no row has one)"""
+    rows = [_ascii(s) for s in seqs]
+    ld = max([1] + [len(s) for s in rows])
+    c = None
+    if cons is not None:
+        cons = [None if x is None else _ascii(x) for x in cons]
+        if len(cons) != len(rows):
+            raise ValueError("one constraint item (a string or None) per sequence")
+        if any(x is not None and len(x) != len(s) for x, s in zip(cons, rows)):
+            raise ValueError("constraint string and sequence differ in length")
+        if any(x is not None for x in cons):
+            c = _pad(cons, ld, ord("."))
+    return _pad(rows, ld), np.array([len(s) for s in rows], dtype=np.int32), ld, c
 
 
 class Engine:
@@ -217,6 +267,13 @@ class Engine:
             if rc == -6:
                 msg += ": " + self.lib.sf_last_hip_error().decode()
             raise ScanFoldHipError(msg)
+
+    def _need(self, symbol, what, names=None):
+        """Raises ScanFoldHipError on a library without the entry point `symbol` (or without one of `names`, where `symbol`
+        describes several), which `what` need: there is no fallback."""
+        if any(getattr(self.lib, name, None) is None for name in names or (symbol,)):
+            raise ScanFoldHipError("this library (%s) has no %s: %s need libscanfold_hip.so"
+                                   % (getattr(self.lib, "_name", "?"), symbol, what))
 
     def device_name(self):
         buf = ctypes.create_string_buffer(256)
@@ -314,27 +371,20 @@ class Engine:
         """fc = RNA.fold_compound(seq, md); fc.hc_add_from_db(cons); fc.mfe() for ONE sequence of 1..SF_MAX_LONG nt
         (ScanFold.py:1520-1539, --global_refold) -> (mfe_dcal, dot-bracket or None).  Raises ScanFoldHipError on a library
         without the entry point (there is no fallback)."""
-        if not self.has_fold_long():
-            raise ScanFoldHipError("this library (%s) has no sf_fold_long: whole-record folds need libscanfold_hip.so"
-                                   % getattr(self.lib, "_name", "?"))
-        s = seq if isinstance(seq, (bytes, bytearray)) else str(seq).encode("ascii")
-        L = len(s)
-        c = None
-        if cons is not None:
-            c = cons if isinstance(cons, (bytes, bytearray)) else str(cons).encode("ascii")
-            if len(c) != L:
-                raise ValueError("constraint string and sequence differ in length")
-        arr = np.frombuffer(bytes(s), dtype=np.uint8) if L else np.zeros(1, dtype=np.uint8)
+        self._need(*_FOLD_LONG)
+        return self._fold_record(self.lib.sf_fold_long, seq, cons, structure)
+
+    def _fold_record(self, entry, seq, cons, structure):
+        """entry = sf_fold_long or sf_fold_banded -> (mfe_dcal, dot-bracket or None)"""
+        arr, L, c = _record(seq, cons)
         e = np.zeros(1, dtype=np.int32)
         db = np.zeros(L + 1, dtype=np.uint8) if structure else None
-        self._check(self.lib.sf_fold_long(arr.ctypes.data, L, None if c is None else bytes(c), e.ctypes.data,
-                                          None if db is None else db.ctypes.data))
+        self._check(entry(arr.ctypes.data, L, c, e.ctypes.data, None if db is None else db.ctypes.data))
         return int(e[0]), (bytes(db[:L]).decode() if structure else None)
 
     def fold_long_times(self):
         """-> (fill_ms, f5_ms, traceback_ms) of the last fold_long (device events)."""
-        if not self.has_fold_long():
-            raise ScanFoldHipError("this library has no sf_fold_long")
+        self._need(*_FOLD_LONG)
         t = [ctypes.c_double() for _ in range(3)]
         self._check(self.lib.sf_fold_long_times(*(ctypes.byref(x) for x in t)))
         return tuple(x.value for x in t)
@@ -342,34 +392,17 @@ class Engine:
     def has_fold_banded(self):
         return getattr(self.lib, "sf_fold_banded", None) is not None
 
-    def _need_fold_banded(self):
-        if not self.has_fold_banded():
-            raise ScanFoldHipError("this library (%s) has no sf_fold_banded: whole-record folds under a base-pair span in "
-                                   "banded tables need libscanfold_hip.so" % getattr(self.lib, "_name", "?"))
-
     def fold_banded(self, seq, cons=None, structure=True):
         """fold_long under the resident base-pair span (set_max_bp_span(S), S >= 1) in banded tables (sf_fold_banded): ONE
         sequence of 1..SF_MAX_BANDED nt -> (mfe_dcal, dot-bracket or None), the bytes fold_long returns under the same span,
         from 12 L min(S, L) bytes of tables and min(S, L) fill launches.  Raises ScanFoldHipError where no span is set, and
         on a library without the entry point (there is no fallback)."""
-        self._need_fold_banded()
-        s = seq if isinstance(seq, (bytes, bytearray)) else str(seq).encode("ascii")
-        L = len(s)
-        c = None
-        if cons is not None:
-            c = cons if isinstance(cons, (bytes, bytearray)) else str(cons).encode("ascii")
-            if len(c) != L:
-                raise ValueError("constraint string and sequence differ in length")
-        arr = np.frombuffer(bytes(s), dtype=np.uint8) if L else np.zeros(1, dtype=np.uint8)
-        e = np.zeros(1, dtype=np.int32)
-        db = np.zeros(L + 1, dtype=np.uint8) if structure else None
-        self._check(self.lib.sf_fold_banded(arr.ctypes.data, L, None if c is None else bytes(c), e.ctypes.data,
-                                            None if db is None else db.ctypes.data))
-        return int(e[0]), (bytes(db[:L]).decode() if structure else None)
+        self._need(*_FOLD_BANDED)
+        return self._fold_record(self.lib.sf_fold_banded, seq, cons, structure)
 
     def fold_banded_times(self):
         """-> dict(fill_ms, f5_ms, trace_ms, band, fill_launches) of the last fold_banded (device events; band = min(span, L))."""
-        self._need_fold_banded()
+        self._need(*_FOLD_BANDED)
         t = [ctypes.c_double() for _ in range(3)]
         b, n = ctypes.c_int(), ctypes.c_int()
         self._check(self.lib.sf_fold_banded_times(*(ctypes.byref(x) for x in t), ctypes.byref(b), ctypes.byref(n)))
@@ -377,7 +410,7 @@ class Engine:
 
     def fold_banded_bytes(self, L, span):
         """the device memory fold_banded would allocate for L nucleotides under `span` (sf_fold_banded_bytes)"""
-        self._need_fold_banded()
+        self._need(*_FOLD_BANDED)
         n = ctypes.c_size_t()
         self._check(self.lib.sf_fold_banded_bytes(int(L), int(span), ctypes.byref(n)))
         return int(n.value)
@@ -385,38 +418,14 @@ class Engine:
     def has_fold_long_batch(self):
         return getattr(self.lib, "sf_fold_long_batch", None) is not None
 
-    def _need_fold_long_batch(self):
-        if not self.has_fold_long_batch():
-            raise ScanFoldHipError("this library (%s) has no sf_fold_long_batch: folds of sequences past %d nt need "
-                                   "libscanfold_hip.so" % (getattr(self.lib, "_name", "?"), SF_MAX_W))
-
     def fold_long_batch(self, seqs, cons=None, structure=False):
         """fold_long for many sequences of 1..SF_MAX_LONG nt, of any mix of lengths, side by side in the same launches
         (sf_fold_long_batch) -> int32 array of energies (dcal/mol), or (energies, [dot-bracket]) with structure=True.
         cons: None, or one item per sequence, each a constraint string of the sequence's length or None.  Raises
         ScanFoldHipError on a library without the entry point (there is no fallback)."""
-        self._need_fold_long_batch()
-        rows = [s if isinstance(s, (bytes, bytearray)) else str(s).encode("ascii") for s in seqs]
-        n = len(rows)
-        ld = max([1] + [len(s) for s in rows])
-        arr = np.zeros((n, ld), dtype=np.uint8)
-        for k, s in enumerate(rows):
-            arr[k, :len(s)] = np.frombuffer(bytes(s), dtype=np.uint8)
-        lens = np.array([len(s) for s in rows], dtype=np.int32)
-        c = None
-        if cons is not None:
-            cons = list(cons)
-            if len(cons) != n:
-                raise ValueError("one constraint item (a string or None) per sequence")
-            if any(x is not None for x in cons):
-                c = np.full((n, ld), ord("."), dtype=np.uint8)
-                for k, x in enumerate(cons):
-                    if x is None:
-                        continue
-                    x = x if isinstance(x, (bytes, bytearray)) else str(x).encode("ascii")
-                    if len(x) != len(rows[k]):
-                        raise ValueError("constraint string and sequence differ in length")
-                    c[k, :len(x)] = np.frombuffer(bytes(x), dtype=np.uint8)
+        self._need(*_FOLD_LONG_BATCH)
+        arr, lens, ld, c = _ragged_rows(seqs, cons)
+        n = len(lens)
         e = np.zeros(n, dtype=np.int32)
         db = np.zeros((n, ld + 1), dtype=np.uint8) if structure else None
         self._check(self.lib.sf_fold_long_batch(arr.ctypes.data, n, ld, lens.ctypes.data, None if c is None else c.ctypes.data,
@@ -427,7 +436,7 @@ class Engine:
 
     def fold_long_batch_times(self):
         """-> dict(fill_ms, f5_ms, trace_ms, chunks) of the last fold_long_batch (device events, summed over its chunks)."""
-        self._need_fold_long_batch()
+        self._need(*_FOLD_LONG_BATCH)
         t = [ctypes.c_double() for _ in range(3)]
         ch = ctypes.c_int()
         self._check(self.lib.sf_fold_long_batch_times(*(ctypes.byref(x) for x in t), ctypes.byref(ch)))
@@ -435,43 +444,30 @@ class Engine:
 
     def set_long_batch_bytes(self, nbytes):
         """the device memory one chunk of fold_long_batch may take for its tables; 0 restores the default (8 GiB)"""
-        self._need_fold_long_batch()
+        self._need(*_FOLD_LONG_BATCH)
         self._check(self.lib.sf_set_long_batch_bytes(int(nbytes)))
 
     def has_pf_long(self):
         return getattr(self.lib, "sf_pf_long", None) is not None
-
-    def _need_pf_long(self):
-        if not self.has_pf_long():
-            raise ScanFoldHipError("this library (%s) has no sf_pf_long: whole-record partition functions need "
-                                   "libscanfold_hip.so" % getattr(self.lib, "_name", "?"))
 
     def pf_long(self, seq, cons=None, mfe_hint=None):
         """fc.hc_add_from_db(cons); fc.pf(); fc.centroid(); fc.mean_bp_distance() (RNAfold -p -C, ScanFoldFunctions.py:758-772)
         for ONE sequence of 1..SF_MAX_LONG nt -> dict(dG, mean_bp_dist, centroid, centroid_dist), the keys of one pf_batch
         item.  mfe_hint: the sequence's MFE in dcal/mol (fold_long's), which sets the scale of the first attempt.  Raises
         ScanFoldHipError on a library without the entry point (there is no fallback)."""
-        self._need_pf_long()
-        s = seq if isinstance(seq, (bytes, bytearray)) else str(seq).encode("ascii")
-        L = len(s)
-        c = None
-        if cons is not None:
-            c = cons if isinstance(cons, (bytes, bytearray)) else str(cons).encode("ascii")
-            if len(c) != L:
-                raise ValueError("constraint string and sequence differ in length")
-        arr = np.frombuffer(bytes(s), dtype=np.uint8) if L else np.zeros(1, dtype=np.uint8)
+        self._need(*_PF_LONG)
+        arr, L, c = _record(seq, cons)
         hint = None if mfe_hint is None else np.array([int(mfe_hint)], dtype=np.int32)
         out = np.zeros(3)
         cen = np.zeros(L + 1, dtype=np.uint8)
-        self._check(self.lib.sf_pf_long(arr.ctypes.data, L, None if c is None else bytes(c),
-                                        None if hint is None else hint.ctypes.data, out[0:].ctypes.data, out[1:].ctypes.data,
-                                        cen.ctypes.data, out[2:].ctypes.data))
+        self._check(self.lib.sf_pf_long(arr.ctypes.data, L, c, None if hint is None else hint.ctypes.data,
+                                        out[0:].ctypes.data, out[1:].ctypes.data, cen.ctypes.data, out[2:].ctypes.data))
         return dict(dG=float(out[0]), mean_bp_dist=float(out[1]), centroid=bytes(cen[:L]).decode(),
                     centroid_dist=float(out[2]))
 
     def pf_long_times(self):
         """-> dict(inside_ms, outside_ms, attempts, lns) of the last pf_long (device events; lns = the per-nucleotide scale)."""
-        self._need_pf_long()
+        self._need(*_PF_LONG)
         a, b, n, l = ctypes.c_double(), ctypes.c_double(), ctypes.c_int(), ctypes.c_double()
         self._check(self.lib.sf_pf_long_times(ctypes.byref(a), ctypes.byref(b), ctypes.byref(n), ctypes.byref(l)))
         return dict(inside_ms=a.value, outside_ms=b.value, attempts=n.value, lns=l.value)
@@ -479,39 +475,15 @@ class Engine:
     def has_pf_long_batch(self):
         return getattr(self.lib, "sf_pf_long_batch", None) is not None
 
-    def _need_pf_long_batch(self):
-        if not self.has_pf_long_batch():
-            raise ScanFoldHipError("this library (%s) has no sf_pf_long_batch: partition functions of many sequences past "
-                                   "%d nt need libscanfold_hip.so" % (getattr(self.lib, "_name", "?"), SF_MAX_W))
-
     def pf_long_batch(self, seqs, cons=None, mfe_hints=None):
         """pf_long for many sequences of 1..SF_MAX_LONG nt, of any mix of lengths, side by side in the same launches
         (sf_pf_long_batch) -> a list of pf_long's dicts with two more keys, lns (the row's final per-nucleotide scale) and
         attempts (its inside passes).  cons / mfe_hints: None, or one item per sequence, each a constraint string of the
         sequence's length / the sequence's MFE in dcal/mol, or None.  Every row equals pf_long of that row bit for bit.
         Raises ScanFoldHipError on a library without the entry point (there is no fallback)."""
-        self._need_pf_long_batch()
-        rows = [s if isinstance(s, (bytes, bytearray)) else str(s).encode("ascii") for s in seqs]
-        n = len(rows)
-        ld = max([1] + [len(s) for s in rows])
-        arr = np.zeros((n, ld), dtype=np.uint8)
-        for k, s in enumerate(rows):
-            arr[k, :len(s)] = np.frombuffer(bytes(s), dtype=np.uint8)
-        lens = np.array([len(s) for s in rows], dtype=np.int32)
-        c = None
-        if cons is not None:
-            cons = list(cons)
-            if len(cons) != n:
-                raise ValueError("one constraint item (a string or None) per sequence")
-            if any(x is not None for x in cons):
-                c = np.full((n, ld), ord("."), dtype=np.uint8)
-                for k, x in enumerate(cons):
-                    if x is None:
-                        continue
-                    x = x if isinstance(x, (bytes, bytearray)) else str(x).encode("ascii")
-                    if len(x) != len(rows[k]):
-                        raise ValueError("constraint string and sequence differ in length")
-                    c[k, :len(x)] = np.frombuffer(bytes(x), dtype=np.uint8)
+        self._need(*_PF_LONG_BATCH)
+        arr, lens, ld, c = _ragged_rows(seqs, cons)
+        n = len(lens)
         h = None
         if mfe_hints is not None:
             mfe_hints = list(mfe_hints)
@@ -530,7 +502,7 @@ class Engine:
     def pf_long_batch_times(self):
         """-> dict(inside_ms, outside_ms, chunks, inside_passes) of the last pf_long_batch (device events, summed over its
         chunks; inside_passes = chunks when no row needed another scale)."""
-        self._need_pf_long_batch()
+        self._need(*_PF_LONG_BATCH)
         a, b, ch, ps = ctypes.c_double(), ctypes.c_double(), ctypes.c_int(), ctypes.c_int()
         self._check(self.lib.sf_pf_long_batch_times(ctypes.byref(a), ctypes.byref(b), ctypes.byref(ch), ctypes.byref(ps)))
         return dict(inside_ms=a.value, outside_ms=b.value, chunks=ch.value, inside_passes=ps.value)
@@ -539,29 +511,19 @@ class Engine:
     def has_duplex(self):
         return all(getattr(self.lib, name, None) is not None for name in _DUPLEX_EXPORTS)
 
-    def _need_duplex(self):
-        if not self.has_duplex():
-            raise ScanFoldHipError("this library (%s) has no duplex entry points (sf_duplex_batch, sf_lri_scan, "
-                                   "sf_lri_background): duplex folds and --lri need libscanfold_hip.so"
-                                   % getattr(self.lib, "_name", "?"))
-
     def duplex_batch(self, s1, s2, structure=True):
         """RNA.duplexfold(s1[p], s2[p]) for every p (ScanFold.py:785) -> dict(energy int32 dcal/mol or SF_DUPLEX_NONE,
         i, j int32 (duplexT's .i / .j), structure [str] or None).  Strands of 0..SF_DUPLEX_MAX_LEN nucleotides, mixed freely."""
-        self._need_duplex()
-        a = [s if isinstance(s, (bytes, bytearray)) else str(s).encode("ascii") for s in s1]
-        b = [s if isinstance(s, (bytes, bytearray)) else str(s).encode("ascii") for s in s2]
+        self._need(*_DUPLEX)
+        a = [_ascii(s) for s in s1]
+        b = [_ascii(s) for s in s2]
         if len(a) != len(b):
             raise ValueError("one strand 2 per strand 1")
         n = len(a)
         ld = max([1] + [len(s) for s in a] + [len(s) for s in b])
         if ld > SF_DUPLEX_MAX_LEN:
             raise ValueError("a duplex strand is at most %d nucleotides" % SF_DUPLEX_MAX_LEN)
-        m1 = np.zeros((n, ld), dtype=np.uint8)
-        m2 = np.zeros((n, ld), dtype=np.uint8)
-        for p in range(n):
-            m1[p, :len(a[p])] = np.frombuffer(bytes(a[p]), dtype=np.uint8)
-            m2[p, :len(b[p])] = np.frombuffer(bytes(b[p]), dtype=np.uint8)
+        m1, m2 = _pad(a, ld), _pad(b, ld)
         l1 = np.array([len(s) for s in a], dtype=np.int32)
         l2 = np.array([len(s) for s in b], dtype=np.int32)
         e, ri, rj = (np.zeros(n, dtype=np.int32) for _ in range(3))
@@ -574,7 +536,7 @@ class Engine:
 
     def lri_grid(self, L, kmer, step):
         """-> (n_j, n_k): j_win = jx * step, k_win = kx * step of the reference's two loops (ScanFold.py:774,780)"""
-        self._need_duplex()
+        self._need(*_DUPLEX)
         nj, nk = ctypes.c_int32(), ctypes.c_int32()
         self._check(self.lib.sf_lri_grid(int(L), int(kmer), int(step), ctypes.byref(nj), ctypes.byref(nk)))
         return nj.value, nk.value
@@ -583,7 +545,7 @@ class Engine:
         """The all-pairs k-mer duplex scan (ScanFold.py:773-812).  Compacted (default): the pairs with Emin < cutoff_dcal as
         a LRI_HIT_DTYPE array sorted by (j_win, k_win); more than max_hits raises ScanFoldHipError.  dense=True: dict(energy,
         i, j) of int32 (n_j, n_k) arrays, SF_DUPLEX_SKIPPED where the distance test fails (small records: tests)."""
-        self._need_duplex()
+        self._need(*_DUPLEX)
         s = np.frombuffer(seq.encode("ascii") if isinstance(seq, str) else bytes(seq), dtype=np.uint8)
         if dense:
             nj, nk = self.lri_grid(len(s), kmer, step)
@@ -604,7 +566,7 @@ class Engine:
 
     def lri_scan_time(self):
         """-> (ms of the scan kernels of the last lri_scan by device events, duplexes they folded)"""
-        self._need_duplex()
+        self._need(*_DUPLEX)
         ms, nd = ctypes.c_double(), ctypes.c_int64()
         self._check(self.lib.sf_lri_scan_time(ctypes.byref(ms), ctypes.byref(nd)))
         return ms.value, nd.value
@@ -612,7 +574,7 @@ class Engine:
     def lri_background(self, seq, kmer, j_win, k_win, r, kind, seed, rows=False):
         """cofold_energies(frag, [dup_frag] + scramble(dup_frag, r, type)) for every hit (ScanFold.py:813-817) -> int32
         (n_hits, r+1) energies; rows=True: (energies, rows1, rows2), the folded strands as uint8 codes (n_hits, r+1, kmer)."""
-        self._need_duplex()
+        self._need(*_DUPLEX)
         s = np.frombuffer(seq.encode("ascii") if isinstance(seq, str) else bytes(seq), dtype=np.uint8)
         jw = np.ascontiguousarray(j_win, dtype=np.int32)
         kw = np.ascontiguousarray(k_win, dtype=np.int32)

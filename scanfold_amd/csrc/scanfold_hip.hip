@@ -1217,9 +1217,18 @@ LongPack long_pack(const LongRows &R, int s0, int n) {
   return K;
 }
 
+// Parses one constraint on the device and binds it to a fold's state.  src: its L characters as given; c: L + 2 bytes for
+// the parsed characters; i16: 3 (L + 2) int16 for the bracket partners, the enclosing pairs and the parse's stack.
+void long_parse_hc(SfHc &hc, const char *src, int L, char *c, int16_t *i16) {
+  int16_t *encl = i16 + (size_t)L + 2, *stack = encl + (size_t)L + 2;
+  SF_LAUNCH(sf_long_hc_kernel, 1, 64, 0, g.stream, src, L, c, i16, encl, stack, (int *)g.status.p);
+  hc.c = c;
+  hc.partner = i16;
+  hc.encl = encl;
+}
+
 // Clears the chunk's row states (SfLong or SfPfLong) and sets what both have: L, S and hc.  Copies the packed bytes to
-// d_u8, allocates the int16 block of the constrained rows (bracket partners, enclosing pairs, parse stack: L + 2 each) and
-// parses each of them on the device.
+// d_u8, allocates the int16 block of the constrained rows (3 (L + 2) each) and parses each of them on the device.
 template <class State>
 int long_bind_rows(LongBufs &B, const LongPack &K, const LongRows &R, int s0, uint8_t *d_u8, std::vector<State> &hF) {
   int16_t *d_i16 = nullptr;
@@ -1239,13 +1248,8 @@ int long_bind_rows(LongBufs &B, const LongPack &K, const LongRows &R, int s0, ui
     F.L = L;
     F.S = d_u8 + a_L + 2 * k;
     if (R.constrained[s0 + k]) {
-      int16_t *partner = d_i16 + 3 * (a_hcL + 2 * (size_t)a_hc), *encl = partner + (size_t)L + 2, *stack = encl + (size_t)L + 2;
-      char *c = (char *)d_u8 + K.o_hc + a_hcL + 2 * (size_t)a_hc;
-      SF_LAUNCH(sf_long_hc_kernel, 1, 64, 0, g.stream, (const char *)d_u8 + K.o_src + a_hcL, L, c, partner, encl, stack,
-                (int *)g.status.p);
-      F.hc.c = c;
-      F.hc.partner = partner;
-      F.hc.encl = encl;
+      long_parse_hc(F.hc, (const char *)d_u8 + K.o_src + a_hcL, L, (char *)d_u8 + K.o_hc + a_hcL + 2 * (size_t)a_hc,
+                    d_i16 + 3 * (a_hcL + 2 * (size_t)a_hc));
       a_hcL += (size_t)L;
       a_hc++;
     }
@@ -1350,19 +1354,12 @@ int sf_fold_long(const uint8_t *seq, int L, const char *cons, int32_t *mfe_out, 
   auto bind_hc = [&](LongBufs &B, SfLong &F) -> int {
     if (!cons) return SF_OK;
     int rc;
-    void *src, *hc, *part, *encl, *stack;
-    if ((rc = B.alloc(&src, (size_t)L, "constraint"))) return rc;
-    if ((rc = B.alloc(&hc, (size_t)L + 2, "constraint"))) return rc;
-    if ((rc = B.alloc(&part, ((size_t)L + 2) * sizeof(int16_t), "bracket partners"))) return rc;
-    if ((rc = B.alloc(&encl, ((size_t)L + 2) * sizeof(int16_t), "enclosing pairs"))) return rc;
-    if ((rc = B.alloc(&stack, ((size_t)L + 2) * sizeof(int16_t), "bracket stack"))) return rc;
-    HIPCHK(hipMemcpyAsync(src, cons, (size_t)L, hipMemcpyHostToDevice, g.stream));
-    SF_LAUNCH(sf_long_hc_kernel, 1, 64, 0, g.stream, (const char *)src, L, (char *)hc, (int16_t *)part, (int16_t *)encl,
-              (int16_t *)stack, (int *)g.status.p);
+    void *u8, *i16;  // the characters as given and parsed (L, then L + 2); long_parse_hc's int16 block
+    if ((rc = B.alloc(&u8, 2 * (size_t)L + 2, "constraint"))) return rc;
+    if ((rc = B.alloc(&i16, 3 * ((size_t)L + 2) * sizeof(int16_t), "bracket partners"))) return rc;
+    HIPCHK(hipMemcpyAsync(u8, cons, (size_t)L, hipMemcpyHostToDevice, g.stream));
+    long_parse_hc(F.hc, (const char *)u8, L, (char *)u8 + L, (int16_t *)i16);
     HIPCHK(hipGetLastError());
-    F.hc.c = (const char *)hc;
-    F.hc.partner = (const int16_t *)part;
-    F.hc.encl = (const int16_t *)encl;
     return SF_OK;
   };
   auto fill = [&](const SfLong &F, const SfDevParams *D, int threads) {
@@ -1646,14 +1643,14 @@ int sf_set_long_batch_bytes(size_t bytes) {
 
 }  // extern "C"
 
-// ---------------- whole-record partition function (sf_pf_long.hip.h) ----------------
+// ---------------- whole-record partition function (sf_pf_long.hip.h): one host driver, the launches its callers' ----------------
 namespace {
 double g_pfl_ms[2] = {0, 0};  // inside (all attempts, with q5 / q3), outside (with the probabilities) of the last sf_pf_long
 int g_pfl_attempts = 0;
 double g_pfl_lns = 0.0;
 
-// sc[k] = s^-k and mlbs[k] = (MLbase / s)^k, k = 0 .. L + 1, for the per-nucleotide scale s = e^lns.  Made on the host by
-// this one loop for sf_pf_long and for every row of sf_pf_long_batch: a device exp may differ from it in the last bit.
+// sc[k] = s^-k and mlbs[k] = (MLbase / s)^k, k = 0 .. L + 1, for the per-nucleotide scale s = e^lns.  Made on the host: a
+// device exp may differ from it in the last bit.
 void pfl_scale_powers(double lns, double ln_mlbase, int L, double *sc, double *mlbs) {
   for (int k = 0; k <= L + 1; k++) {
     sc[k] = exp(-lns * k);
@@ -1669,220 +1666,50 @@ double pfl_next_lns(double lns, double lz, int L) {
   // (q5[L] = +inf: log = +inf; an underflow to 0: -inf; NaN counts as an overflow)
   return lns + (isfinite(lz) ? lz / L : ((lz < 0 ? -700.0 : 700.0) / L));
 }
-}  // namespace
-
-extern "C" {
-
-int sf_pf_long(const uint8_t *seq, int L, const char *cons, const int32_t *mfe_dcal_hint, double *ens_dG, double *mean_bp_dist,
-               char *centroid_out, double *centroid_dist) {
-  int rc = check_ready();
-  if (rc) return rc;
-  if (!seq || L < 1 || L > SF_MAX_LONG) return SF_ERR_BAD_ARG;
-  bool noncanonical = false;
-  if (cons && (rc = scan_constraints(seq, cons, 1, L, &noncanonical))) return rc;
-  const sf_params_blob *P = (const sf_params_blob *)g.slot[g.cur].src.data();  // the resident set as it was handed in
-  const Ctx::ModelSlot &M = g.slot[g.cur];  // its host copies of kT, MLbase and the hairpin initiation weight at 30
-  const double kT = M.pf_kT;
-  std::vector<uint8_t> hS((size_t)L + 2, 0);
-  for (int x = 0; x < L; x++) hS[x + 1] = sf_encode_nt(seq[x]);
-  std::vector<double> hhp((size_t)L + 1), hsc((size_t)L + 2), hml((size_t)L + 2);
-  for (int s = 0; s <= L; s++)  // (read only past the resident table, SF_MAX_W + 1: build_dev_params' extrapolation)
-    hhp[s] = (s <= 30) ? 0.0 : M.pf_hp30 * exp(-(P->lxc * log(s / 30.)) * 10. / kT);
-
-  const size_t tri = SF_LONG_TRI(L);
-  LongBufs B;
-  B.who = "sf_pf_long";
-  SfPfLong F;
-  memset(&F, 0, sizeof F);
-  F.L = L;
-  void *p;
-  double *triangles[SF_PFLONG_NTRI];
-  static const char *const tri_names[SF_PFLONG_NTRI] = {"qb", "qb transposed / A0", "qm", "qm transposed", "qm1 / w", "ob", "A1"};
-  for (int k = 0; k < SF_PFLONG_NTRI; k++) {
-    if ((rc = B.alloc(&p, tri * sizeof(double), tri_names[k]))) return rc;
-    triangles[k] = (double *)p;
-  }
-  F.qb = triangles[0]; F.qbt = triangles[1]; F.qm = triangles[2]; F.qmt = triangles[3]; F.qm1t = triangles[4];
-  F.ob = triangles[5]; F.a1 = triangles[6];
-  F.a0 = F.qbt;   // (dead after q5)
-  F.wt = F.qm1t;  // (dead after the inside pass)
-  const size_t lanes = (size_t)(g.n_cu > 0 ? g.n_cu : 1) * SF_PFLONG_LANES_PER_CU;
-  const int prob_waves = pfl_prob_waves(L, lanes);
-  double *d_hp, *d_sc, *d_ml;
-  if ((rc = B.alloc(&p, ((size_t)L + 1) * sizeof(double), "hairpin weights"))) return rc;
-  d_hp = (double *)p;
-  if ((rc = B.alloc(&p, ((size_t)L + 2) * sizeof(double), "scale powers"))) return rc;
-  d_sc = (double *)p;
-  if ((rc = B.alloc(&p, ((size_t)L + 2) * sizeof(double), "MLbase powers"))) return rc;
-  d_ml = (double *)p;
-  F.hpx = d_hp; F.sc = d_sc; F.mlbs = d_ml;
-  if ((rc = B.alloc(&p, ((size_t)L + 2) * sizeof(double), "q5"))) return rc;
-  F.q5 = (double *)p;
-  if ((rc = B.alloc(&p, ((size_t)L + 3) * sizeof(double), "q3"))) return rc;
-  F.q3 = (double *)p;
-  if ((rc = B.alloc(&p, 2 * (size_t)prob_waves * sizeof(double), "partial sums"))) return rc;
-  F.part = (double *)p;
-  if ((rc = B.alloc(&p, 3 * sizeof(double), "results"))) return rc;
-  F.out = (double *)p;
-  if ((rc = B.alloc(&p, (size_t)L + 1, "centroid"))) return rc;
-  F.cen = (char *)p;
-  if ((rc = B.alloc(&p, (size_t)L + 2, "sequence"))) return rc;
-  F.S = (const uint8_t *)p;
-  HIPCHK(hipMemcpyAsync(p, hS.data(), (size_t)L + 2, hipMemcpyHostToDevice, g.stream));
-  HIPCHK(hipMemcpyAsync(d_hp, hhp.data(), ((size_t)L + 1) * sizeof(double), hipMemcpyHostToDevice, g.stream));
-  F.hc.c = nullptr;
-  if (cons) {
-    void *src, *hc, *part, *encl, *stack;
-    if ((rc = B.alloc(&src, (size_t)L, "constraint"))) return rc;
-    if ((rc = B.alloc(&hc, (size_t)L + 2, "constraint"))) return rc;
-    if ((rc = B.alloc(&part, ((size_t)L + 2) * sizeof(int16_t), "bracket partners"))) return rc;
-    if ((rc = B.alloc(&encl, ((size_t)L + 2) * sizeof(int16_t), "enclosing pairs"))) return rc;
-    if ((rc = B.alloc(&stack, ((size_t)L + 2) * sizeof(int16_t), "bracket stack"))) return rc;
-    HIPCHK(hipMemcpyAsync(src, cons, (size_t)L, hipMemcpyHostToDevice, g.stream));
-    SF_LAUNCH(sf_long_hc_kernel, 1, 64, 0, g.stream, (const char *)src, L, (char *)hc, (int16_t *)part, (int16_t *)encl,
-              (int16_t *)stack, (int *)g.status.p);
-    HIPCHK(hipGetLastError());
-    F.hc.c = (const char *)hc;
-    F.hc.partner = (const int16_t *)part;
-    F.hc.encl = (const int16_t *)encl;
-    if ((rc = read_status(g.stream, false))) return rc;
-  }
-  for (auto &e : B.ev) HIPCHK(hipEventCreate(&e));
-  const SfDevParams *D = (const SfDevParams *)g.dP;
-  const SfDevParamsPF *X = (const SfDevParamsPF *)g.dX;
-  const int threads = 256;
-  auto diagonal = [&](int d, int *G, int *grid) {
-    const size_t cells = (size_t)(L - d);
-    *G = pfl_group(cells, d, lanes);
-    const size_t total = std::min(cells * (size_t)*G, lanes);
-    *grid = (int)((total + threads - 1) / threads);
-  };
-
-  double lns = pfl_first_lns(mfe_dcal_hint, kT, L);
-  const double ln_mlbase = log(M.pf_MLbase);
-  double res[3] = {0, 0, 0};
-  std::vector<char> cen((size_t)L + 1);
-  double ms_in = 0.0, ms_out = 0.0;
-  int attempt = 0;
-  bool done = false;
-  for (; attempt < SF_PFLONG_MAX_ATTEMPTS && !done; attempt++) {
-    pfl_scale_powers(lns, ln_mlbase, L, hsc.data(), hml.data());
-    HIPCHK(hipMemcpyAsync(d_sc, hsc.data(), ((size_t)L + 2) * sizeof(double), hipMemcpyHostToDevice, g.stream));
-    HIPCHK(hipMemcpyAsync(d_ml, hml.data(), ((size_t)L + 2) * sizeof(double), hipMemcpyHostToDevice, g.stream));
-    HIPCHK(hipEventRecord(B.ev[0], g.stream));
-    for (int d = 0; d < L; d++) {
-      int G, grid;
-      diagonal(d, &G, &grid);
-      SF_LAUNCH(sf_pflong_inside_kernel, grid, threads, 0, g.stream, F, d, G, D, X);
-    }
-    HIPCHK(hipGetLastError());
-    SF_LAUNCH(sf_pflong_exterior_kernel, 1, 64, 0, g.stream, F, D, X);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(B.ev[1], g.stream));
-    HIPCHK(hipMemcpyAsync(res, F.out, sizeof(double), hipMemcpyDeviceToHost, g.stream));
-    HIPCHK(hipStreamSynchronize(g.stream));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, B.ev[0], B.ev[1]));
-    ms_in += ms;
-    const double lz = res[0];
-    if (!isfinite(lz) || fabs(lz) > SF_PF_LNZ_MAX) {
-      lns = pfl_next_lns(lns, lz, L);
-      continue;
-    }
-    HIPCHK(hipMemsetAsync(F.cen, '.', (size_t)L, g.stream));
-    HIPCHK(hipMemsetAsync(F.cen + L, 0, 1, g.stream));
-    HIPCHK(hipEventRecord(B.ev[2], g.stream));
-    for (int d = L - 1; d >= SFD_TURN + 1; d--) {
-      int G, grid;
-      diagonal(d, &G, &grid);
-      SF_LAUNCH(sf_pflong_outside_kernel, grid, threads, 0, g.stream, F, d, G, D, X);
-    }
-    HIPCHK(hipGetLastError());
-    SF_LAUNCH(sf_pflong_prob_kernel, prob_waves, 64, 0, g.stream, F);
-    SF_LAUNCH(sf_pflong_finish_kernel, 1, 64, 0, g.stream, F, prob_waves);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(B.ev[3], g.stream));
-    HIPCHK(hipMemcpyAsync(res, F.out, sizeof res, hipMemcpyDeviceToHost, g.stream));
-    HIPCHK(hipMemcpyAsync(cen.data(), F.cen, (size_t)L + 1, hipMemcpyDeviceToHost, g.stream));
-    HIPCHK(hipStreamSynchronize(g.stream));
-    HIPCHK(hipEventElapsedTime(&ms, B.ev[2], B.ev[3]));
-    ms_out += ms;
-    if (isfinite(res[1]) && isfinite(res[2])) {
-      done = true;
-    } else {
-      if (fabs(lz) < 1.0) break;  // Z_s is centred and the outside tables still leave the range
-      lns += lz / L;
-    }
-  }
-  if ((rc = read_status(g.stream, false))) return rc;
-  g_pfl_ms[0] = ms_in;
-  g_pfl_ms[1] = ms_out;
-  g_pfl_attempts = attempt;
-  g_pfl_lns = lns;
-  if (!done) return SF_ERR_RANGE;
-  const double dG = -(res[0] + (double)L * lns) * kT / 1000.0;
-  if (!isfinite(dG)) return SF_ERR_RANGE;
-  if (ens_dG) *ens_dG = dG;
-  if (mean_bp_dist) *mean_bp_dist = res[1];
-  if (centroid_dist) *centroid_dist = res[2];
-  if (centroid_out) memcpy(centroid_out, cen.data(), (size_t)L + 1);
-  return SF_OK;
+// Hairpin initiation weights by loop size 0..n (read only past the resident table, SF_MAX_W + 1: build_dev_params'
+// extrapolation), from the slot's host copies of kT and the weight at 30 and the set as it was handed in.
+std::vector<double> pfl_hairpin_table(const Ctx::ModelSlot &M, int n) {
+  const sf_params_blob *P = (const sf_params_blob *)M.src.data();
+  std::vector<double> hp((size_t)n + 1);
+  for (int s = 0; s <= n; s++) hp[s] = (s <= 30) ? 0.0 : M.pf_hp30 * exp(-(P->lxc * log(s / 30.)) * 10. / M.pf_kT);
+  return hp;
 }
+// the lane budget of ONE sf_pf_long call: it sizes every row's lane groups and probability waves, whatever a batch holds
+size_t pfl_lanes() { return (size_t)(g.n_cu > 0 ? g.n_cu : 1) * SF_PFLONG_LANES_PER_CU; }
 
-int sf_pf_long_times(double *inside_ms, double *outside_ms, int *attempts, double *lns) {
-  SF_ENTER();
-  if (inside_ms) *inside_ms = g_pfl_ms[0];
-  if (outside_ms) *outside_ms = g_pfl_ms[1];
-  if (attempts) *attempts = g_pfl_attempts;
-  if (lns) *lns = g_pfl_lns;
-  return SF_OK;
-}
-
-}  // extern "C"
-
-// ---------------- many whole-record partition functions at once (sf_pf_long_batch.hip.h) ----------------
-namespace {
-double g_pflb_ms[2] = {0, 0};  // inside passes (q5 / q3 included), outside and probability passes of the last sf_pf_long_batch
-int g_pflb_chunks = 0, g_pflb_passes = 0;
-
-size_t pf_long_row_bytes(int L) { return SF_PFLONG_BYTES(L); }
-
-// Rows s0 .. s0 + n - 1 as one chunk.  hint: NULL, or one value per row of the call (SF_PF_LONG_NO_HINT: none).  rows_host /
-// cen_host: the caller's staging buffers (the chunk's records at rows_host[s0 ..], its centroids back to back, L + 1 bytes
-// each, at cen_host, or NULL).  ms_out: inside, outside; *passes: inside passes run.  A fixed number of device allocations
-// whatever n is; all freed on return.
-int pf_long_batch_chunk(const LongRows &R, const int32_t *hint, int s0, int n, sf_pf_long_row *rows_host, char *cen_host,
-                        double ms_out[2], int *passes) {
+// The partition functions of rows s0 .. s0 + n - 1 of R: the host side of sf_pf_long (its one row) and of one chunk of
+// sf_pf_long_batch, after their argument checks.  hint: NULL, or one value per row of the call (SF_PF_LONG_NO_HINT: none).
+// rows_host / cen_host: the caller's staging buffers (the records at rows_host[s0 ..], the centroids back to back, L + 1
+// bytes each, at cen_host, or NULL); a call that ends in SF_ERR_RANGE still leaves every row's lns and attempts there.
+// ms_out: inside, outside; *passes: inside passes run.  A fixed number of device allocations whatever n is; all freed on
+// return.  The launches are the caller's: launch.bind(B, hF) takes the row states, launch.mark(act) the rows the next
+// launches work on (bytes, one per row), and launch.inside(Ltop, d), exterior(), outside(Ltop, d), prob() and finish() run
+// one pass over the marked rows, the longest of which has Ltop nt.
+template <class Launch>
+int pf_long_rows(const LongRows &R, const int32_t *hint, int s0, int n, Launch &launch, sf_pf_long_row *rows_host,
+                 char *cen_host, double ms_out[2], int *passes) {
   int rc;
-  const sf_params_blob *P = (const sf_params_blob *)g.slot[g.cur].src.data();  // the resident set as it was handed in
   const Ctx::ModelSlot &M = g.slot[g.cur];  // its host copies of kT, MLbase and the hairpin initiation weight at 30
   const double kT = M.pf_kT, ln_mlbase = log(M.pf_MLbase);
-  // the budget of ONE sf_pf_long call: it sizes every row's lane groups and probability waves, whatever the batch holds
-  const size_t lanes = (size_t)(g.n_cu > 0 ? g.n_cu : 1) * SF_PFLONG_LANES_PER_CU;
-  const size_t budget = (size_t)(g.n_cu > 0 ? g.n_cu : 1) * SF_PFLONGB_LANES_PER_CU;  // the chunk's own, per launch
+  const size_t lanes = pfl_lanes();
   const LongPack K = long_pack(R, s0, n);
   const int Lmax = K.Lmax;
   const size_t n_L = K.n_L;
-  int wmax = 0;
   size_t tri = 0, n_part = 0;
   for (int k = 0; k < n; k++) {
-    const int L = R.len[s0 + k];
-    tri += SF_LONG_TRI(L);
-    const int w = pfl_prob_waves(L, lanes);
-    wmax = std::max(wmax, w);
-    n_part += 2 * (size_t)w;
+    tri += SF_LONG_TRI(R.len[s0 + k]);
+    n_part += 2 * (size_t)pfl_prob_waves(R.len[s0 + k], lanes);
   }
   // slices of the FP64 allocation, in elements: the results first (one copy reads every row's), then the powers of every
-  // row's scale (one copy writes them), the shared hairpin table, q5, q3 and the partial sums.  The centroids and the row
-  // marks follow the packed rows in the byte block.
+  // row's scale (one copy writes them), the shared hairpin table, q5, q3 and the partial sums.  The centroids follow the
+  // packed rows in the byte block.
   const size_t o_out = 0, o_pow = o_out + 3 * (size_t)n, n_pow = 2 * (n_L + 2 * (size_t)n), o_hp = o_pow + n_pow;
   const size_t o_q5 = o_hp + (size_t)Lmax + 1, o_q3 = o_q5 + n_L + 2 * (size_t)n, o_part = o_q3 + n_L + 3 * (size_t)n;
   const size_t n_f64 = o_part + n_part;
-  const size_t o_cen = K.o_end, o_act = o_cen + n_L + (size_t)n, n_u8 = o_act + (size_t)n;
+  const size_t o_cen = K.o_end, n_u8 = o_cen + n_L + (size_t)n;
 
-  std::vector<double> hhp((size_t)Lmax + 1), hpow(n_pow), hout(3 * (size_t)n);
-  for (int s = 0; s <= Lmax; s++)  // (read only past the resident table, SF_MAX_W + 1: build_dev_params' extrapolation)
-    hhp[s] = (s <= 30) ? 0.0 : M.pf_hp30 * exp(-(P->lxc * log(s / 30.)) * 10. / kT);
+  const std::vector<double> hhp = pfl_hairpin_table(M, Lmax);
+  std::vector<double> hpow(n_pow), hout(3 * (size_t)n);
   std::vector<SfPfLong> hF((size_t)n);
   std::vector<char> hcen(n_L + (size_t)n);
 
@@ -1891,7 +1718,6 @@ int pf_long_batch_chunk(const LongRows &R, const int32_t *hint, int s0, int n, s
   void *p;
   double *d_tri[SF_PFLONG_NTRI], *d_f64;
   uint8_t *d_u8;
-  SfPfLong *d_F;
   static const char *const tri_names[SF_PFLONG_NTRI] = {"qb", "qb transposed / A0", "qm", "qm transposed", "qm1 / w", "ob", "A1"};
   for (int k = 0; k < SF_PFLONG_NTRI; k++) {
     if ((rc = B.alloc(&p, tri * sizeof(double), tri_names[k]))) return rc;
@@ -1899,10 +1725,8 @@ int pf_long_batch_chunk(const LongRows &R, const int32_t *hint, int s0, int n, s
   }
   if ((rc = B.alloc(&p, n_f64 * sizeof(double), "results, scale powers, hairpin weights, q5, q3, partial sums"))) return rc;
   d_f64 = (double *)p;
-  if ((rc = B.alloc(&p, n_u8, "sequences, constraints, centroids, row marks"))) return rc;
+  if ((rc = B.alloc(&p, n_u8, "sequences, constraints, centroids"))) return rc;
   d_u8 = (uint8_t *)p;
-  if ((rc = B.alloc(&p, (size_t)n * sizeof(SfPfLong), "partition function states"))) return rc;
-  d_F = (SfPfLong *)p;
   if ((rc = long_bind_rows(B, K, R, s0, d_u8, hF))) return rc;
 
   std::vector<size_t> pow_off((size_t)n), cen_off((size_t)n);
@@ -1929,22 +1753,8 @@ int pf_long_batch_chunk(const LongRows &R, const int32_t *hint, int s0, int n, s
     a_part += 2 * (size_t)pfl_prob_waves(L, lanes);
   }
   HIPCHK(hipMemcpyAsync(d_f64 + o_hp, hhp.data(), hhp.size() * sizeof(double), hipMemcpyHostToDevice, g.stream));
-  HIPCHK(hipMemcpyAsync(d_F, hF.data(), (size_t)n * sizeof(SfPfLong), hipMemcpyHostToDevice, g.stream));
-
+  if ((rc = launch.bind(B, hF))) return rc;
   for (auto &e : B.ev) HIPCHK(hipEventCreate(&e));
-  const SfDevParams *D = (const SfDevParams *)g.dP;
-  const SfDevParamsPF *X = (const SfDevParamsPF *)g.dX;
-  const int threads = SF_PFLONGB_THREADS;
-  const uint8_t *d_act = d_u8 + o_act;
-  // workgroups per row on diagonal d when the longest live row has Ltop nt: what sf_pf_long would give that row, cut down
-  // until the whole launch fits the batch's budget (at least one).  It orders no sum: a group walks more cells instead.
-  auto blocks_per_row = [&](int Ltop, int d) {
-    const size_t cells = (size_t)(Ltop - d);
-    const size_t want = std::min(cells * (size_t)pfl_group(1, d, lanes), lanes);
-    size_t bps = (want + threads - 1) / threads;
-    const size_t fit = budget / ((size_t)n * threads);
-    return (int)std::max<size_t>(1, std::min(bps, fit));
-  };
 
   // 0: waits for an inside pass; 1: in range, waits for the outside pass; 2: done
   enum { PENDING = 0, READY = 1, DONE = 2 };
@@ -1953,6 +1763,15 @@ int pf_long_batch_chunk(const LongRows &R, const int32_t *hint, int s0, int n, s
   std::vector<uint8_t> act((size_t)n);
   for (int k = 0; k < n; k++)
     lns[k] = pfl_first_lns(hint && hint[s0 + k] != SF_PF_LONG_NO_HINT ? &hint[s0 + k] : nullptr, kT, R.len[s0 + k]);
+  // every way out once something was launched: the status word is read, and the scales and attempts go with the rows
+  auto leave = [&](int range_rc) {
+    for (int k = 0; k < n; k++) {
+      rows_host[s0 + k].lns = lns[k];
+      rows_host[s0 + k].attempts = attempts[k];
+    }
+    const int status_rc = read_status(g.stream, false);
+    return status_rc ? status_rc : range_rc;
+  };
   int n_done = 0;
   float ms = 0;
   while (n_done < n) {
@@ -1962,7 +1781,7 @@ int pf_long_batch_chunk(const LongRows &R, const int32_t *hint, int s0, int n, s
       for (int k = 0; k < n; k++) {
         act[k] = state[k] == PENDING;
         if (!act[k]) continue;
-        if (attempts[k] >= SF_PFLONG_MAX_ATTEMPTS) return SF_ERR_RANGE;
+        if (attempts[k] >= SF_PFLONG_MAX_ATTEMPTS) return leave(SF_ERR_RANGE);
         attempts[k]++;
         const int L = R.len[s0 + k];
         Ltop = std::max(Ltop, L);
@@ -1971,14 +1790,11 @@ int pf_long_batch_chunk(const LongRows &R, const int32_t *hint, int s0, int n, s
       if (!Ltop) break;
       // (the rows that keep their scale keep their powers: the copy writes them the values they have)
       HIPCHK(hipMemcpyAsync(d_f64 + o_pow, hpow.data(), n_pow * sizeof(double), hipMemcpyHostToDevice, g.stream));
-      HIPCHK(hipMemcpyAsync(d_u8 + o_act, act.data(), (size_t)n, hipMemcpyHostToDevice, g.stream));
+      if ((rc = launch.mark(act.data()))) return rc;
       HIPCHK(hipEventRecord(B.ev[0], g.stream));
-      for (int d = 0; d < Ltop; d++) {
-        const int bps = blocks_per_row(Ltop, d);
-        SF_LAUNCH(sf_pflongb_inside_kernel, n * bps, threads, 0, g.stream, (const SfPfLong *)d_F, d_act, d, bps, (int)lanes, D, X);
-      }
+      for (int d = 0; d < Ltop; d++) launch.inside(Ltop, d);
       HIPCHK(hipGetLastError());
-      SF_LAUNCH(sf_pflongb_exterior_kernel, n, 64, 0, g.stream, (const SfPfLong *)d_F, d_act, D, X);
+      launch.exterior();
       HIPCHK(hipGetLastError());
       HIPCHK(hipEventRecord(B.ev[1], g.stream));
       HIPCHK(hipMemcpyAsync(hout.data(), d_f64 + o_out, 3 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, g.stream));
@@ -1999,17 +1815,13 @@ int pf_long_batch_chunk(const LongRows &R, const int32_t *hint, int s0, int n, s
       act[k] = state[k] == READY;
       if (act[k]) Ltop = std::max(Ltop, (int)R.len[s0 + k]);
     }
-    HIPCHK(hipMemcpyAsync(d_u8 + o_act, act.data(), (size_t)n, hipMemcpyHostToDevice, g.stream));
+    if ((rc = launch.mark(act.data()))) return rc;
     HIPCHK(hipMemsetAsync(d_u8 + o_cen, '.', n_L + (size_t)n, g.stream));  // (the rows done before are on the host already)
     HIPCHK(hipEventRecord(B.ev[2], g.stream));
-    for (int d = Ltop - 1; d >= SFD_TURN + 1; d--) {
-      const int bps = blocks_per_row(Ltop, d);
-      SF_LAUNCH(sf_pflongb_outside_kernel, n * bps, threads, 0, g.stream, (const SfPfLong *)d_F, d_act, d, bps, (int)lanes, D, X);
-    }
+    for (int d = Ltop - 1; d >= SFD_TURN + 1; d--) launch.outside(Ltop, d);
     HIPCHK(hipGetLastError());
-    const int pbps = (wmax + threads / 64 - 1) / (threads / 64);
-    SF_LAUNCH(sf_pflongb_prob_kernel, n * pbps, threads, 0, g.stream, (const SfPfLong *)d_F, d_act, pbps, (int)lanes);
-    SF_LAUNCH(sf_pflongb_finish_kernel, n, 64, 0, g.stream, (const SfPfLong *)d_F, d_act, (int)lanes);
+    launch.prob();
+    launch.finish();
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(B.ev[3], g.stream));
     HIPCHK(hipMemcpyAsync(hout.data(), d_f64 + o_out, 3 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, g.stream));
@@ -2023,13 +1835,11 @@ int pf_long_batch_chunk(const LongRows &R, const int32_t *hint, int s0, int n, s
       const double *res = hout.data() + 3 * (size_t)k;
       if (isfinite(res[1]) && isfinite(res[2])) {
         const double dG = -(res[0] + (double)L * lns[k]) * kT / 1000.0;
-        if (!isfinite(dG)) return SF_ERR_RANGE;
+        if (!isfinite(dG)) return leave(SF_ERR_RANGE);
         sf_pf_long_row &r = rows_host[s0 + k];
         r.ens_dG = dG;
         r.mean_bp_dist = res[1];
         r.centroid_dist = res[2];
-        r.lns = lns[k];
-        r.attempts = attempts[k];
         r.reserved = 0;
         if (cen_host) {
           memcpy(cen_host + cen_off[k], hcen.data() + cen_off[k], (size_t)L);
@@ -2038,14 +1848,139 @@ int pf_long_batch_chunk(const LongRows &R, const int32_t *hint, int s0, int n, s
         state[k] = DONE;
         n_done++;
       } else {
-        if (fabs(lz[k]) < 1.0) return SF_ERR_RANGE;  // Z_s is centred and the outside tables still leave the range
+        if (fabs(lz[k]) < 1.0) return leave(SF_ERR_RANGE);  // Z_s is centred and the outside tables still leave the range
         lns[k] += lz[k] / L;
         state[k] = PENDING;
       }
     }
   }
-  return read_status(g.stream, false);
+  return leave(SF_OK);
 }
+
+// sf_pf_long's launches: the one row's state goes to its kernels by value, so nothing of it lives on the device, and the
+// row is marked whenever the driver launches at all.  The lane groups and the grids are the row's own.
+struct PflSingleLaunch {
+  const size_t lanes = pfl_lanes();
+  const SfDevParams *D = (const SfDevParams *)g.dP;
+  const SfDevParamsPF *X = (const SfDevParamsPF *)g.dX;
+  SfPfLong F;
+  int prob_waves = 0;
+  int bind(LongBufs &, const std::vector<SfPfLong> &hF) {
+    F = hF[0];
+    prob_waves = pfl_prob_waves(F.L, lanes);
+    return SF_OK;
+  }
+  int mark(const uint8_t *) { return SF_OK; }
+  void diagonal(void (*kernel)(SfPfLong, int, int, const SfDevParams *, const SfDevParamsPF *), int d) {
+    const int threads = 256;
+    const size_t cells = (size_t)(F.L - d);
+    const int G = pfl_group(cells, d, lanes);
+    const size_t total = std::min(cells * (size_t)G, lanes);
+    SF_LAUNCH(kernel, (int)((total + threads - 1) / threads), threads, 0, g.stream, F, d, G, D, X);
+  }
+  void inside(int, int d) { diagonal(sf_pflong_inside_kernel, d); }
+  void exterior() { SF_LAUNCH(sf_pflong_exterior_kernel, 1, 64, 0, g.stream, F, D, X); }
+  void outside(int, int d) { diagonal(sf_pflong_outside_kernel, d); }
+  void prob() { SF_LAUNCH(sf_pflong_prob_kernel, prob_waves, 64, 0, g.stream, F); }
+  void finish() { SF_LAUNCH(sf_pflong_finish_kernel, 1, 64, 0, g.stream, F, prob_waves); }
+};
+}  // namespace
+
+extern "C" {
+
+int sf_pf_long(const uint8_t *seq, int L, const char *cons, const int32_t *mfe_dcal_hint, double *ens_dG, double *mean_bp_dist,
+               char *centroid_out, double *centroid_dist) {
+  int rc = check_ready();
+  if (rc) return rc;
+  if (!seq || L < 1 || L > SF_MAX_LONG) return SF_ERR_BAD_ARG;
+  LongRows R = {seq, 1, L, &L, cons, "sf_pf_long"};
+  if ((rc = long_rows_check(R))) return rc;
+  // the record and the centroid are staged: nothing reaches the caller unless the call succeeds
+  sf_pf_long_row row = {};
+  std::vector<char> cen((size_t)L + 1);
+  double ms[2] = {0, 0};
+  int passes = 0;
+  PflSingleLaunch launch;
+  rc = pf_long_rows(R, mfe_dcal_hint, 0, 1, launch, &row, cen.data(), ms, &passes);
+  if (rc && rc != SF_ERR_RANGE) return rc;
+  g_pfl_ms[0] = ms[0];
+  g_pfl_ms[1] = ms[1];
+  g_pfl_attempts = row.attempts;
+  g_pfl_lns = row.lns;
+  if (rc) return rc;
+  if (ens_dG) *ens_dG = row.ens_dG;
+  if (mean_bp_dist) *mean_bp_dist = row.mean_bp_dist;
+  if (centroid_dist) *centroid_dist = row.centroid_dist;
+  if (centroid_out) memcpy(centroid_out, cen.data(), (size_t)L + 1);
+  return SF_OK;
+}
+
+int sf_pf_long_times(double *inside_ms, double *outside_ms, int *attempts, double *lns) {
+  SF_ENTER();
+  if (inside_ms) *inside_ms = g_pfl_ms[0];
+  if (outside_ms) *outside_ms = g_pfl_ms[1];
+  if (attempts) *attempts = g_pfl_attempts;
+  if (lns) *lns = g_pfl_lns;
+  return SF_OK;
+}
+
+}  // extern "C"
+
+// ---------------- many whole-record partition functions at once (sf_pf_long_batch.hip.h) ----------------
+namespace {
+double g_pflb_ms[2] = {0, 0};  // inside passes (q5 / q3 included), outside and probability passes of the last sf_pf_long_batch
+int g_pflb_chunks = 0, g_pflb_passes = 0;
+
+size_t pf_long_row_bytes(int L) { return SF_PFLONG_BYTES(L); }
+
+// A chunk's launches: the row states and the marks of the rows at work in one device allocation, every launch over all rows.
+struct PflBatchLaunch {
+  const size_t lanes = pfl_lanes();
+  const size_t budget = (size_t)(g.n_cu > 0 ? g.n_cu : 1) * SF_PFLONGB_LANES_PER_CU;  // the chunk's own, per launch
+  const SfDevParams *D = (const SfDevParams *)g.dP;
+  const SfDevParamsPF *X = (const SfDevParamsPF *)g.dX;
+  const int threads = SF_PFLONGB_THREADS;
+  int n = 0, wmax = 0;
+  const SfPfLong *d_F = nullptr;
+  uint8_t *d_act = nullptr;
+  int bind(LongBufs &B, const std::vector<SfPfLong> &hF) {
+    n = (int)hF.size();
+    for (const SfPfLong &F : hF) wmax = std::max(wmax, pfl_prob_waves(F.L, lanes));
+    void *p;
+    const int rc = B.alloc(&p, (size_t)n * (sizeof(SfPfLong) + 1), "partition function states, row marks");
+    if (rc) return rc;
+    d_F = (const SfPfLong *)p;
+    d_act = (uint8_t *)p + (size_t)n * sizeof(SfPfLong);
+    HIPCHK(hipMemcpyAsync(p, hF.data(), (size_t)n * sizeof(SfPfLong), hipMemcpyHostToDevice, g.stream));
+    return SF_OK;
+  }
+  int mark(const uint8_t *act) {
+    HIPCHK(hipMemcpyAsync(d_act, act, (size_t)n, hipMemcpyHostToDevice, g.stream));
+    return SF_OK;
+  }
+  // workgroups per row on diagonal d when the longest live row has Ltop nt: what sf_pf_long would give that row, cut down
+  // until the whole launch fits the batch's budget (at least one).  It orders no sum: a group walks more cells instead.
+  int blocks_per_row(int Ltop, int d) const {
+    const size_t cells = (size_t)(Ltop - d);
+    const size_t want = std::min(cells * (size_t)pfl_group(1, d, lanes), lanes);
+    const size_t bps = (want + threads - 1) / threads, fit = budget / ((size_t)n * threads);
+    return (int)std::max<size_t>(1, std::min(bps, fit));
+  }
+  void inside(int Ltop, int d) {
+    const int bps = blocks_per_row(Ltop, d);
+    SF_LAUNCH(sf_pflongb_inside_kernel, n * bps, threads, 0, g.stream, d_F, (const uint8_t *)d_act, d, bps, (int)lanes, D, X);
+  }
+  void exterior() { SF_LAUNCH(sf_pflongb_exterior_kernel, n, 64, 0, g.stream, d_F, (const uint8_t *)d_act, D, X); }
+  void outside(int Ltop, int d) {
+    const int bps = blocks_per_row(Ltop, d);
+    SF_LAUNCH(sf_pflongb_outside_kernel, n * bps, threads, 0, g.stream, d_F, (const uint8_t *)d_act, d, bps, (int)lanes, D, X);
+  }
+  void prob() {
+    const int pbps = (wmax + threads / 64 - 1) / (threads / 64);
+    SF_LAUNCH(sf_pflongb_prob_kernel, n * pbps, threads, 0, g.stream, d_F, (const uint8_t *)d_act, pbps, (int)lanes);
+  }
+  void finish() { SF_LAUNCH(sf_pflongb_finish_kernel, n, 64, 0, g.stream, d_F, (const uint8_t *)d_act, (int)lanes); }
+};
 }  // namespace
 
 extern "C" {
@@ -2061,7 +1996,8 @@ int sf_pf_long_batch(const uint8_t *seqs, int n, int ld, const int32_t *len, con
   double ms[2] = {0, 0};
   int chunks, passes = 0;
   rc = long_for_chunks(R, pf_long_row_bytes, centroid_out, &chunks, [&](int s0, int m, char *cen_host) {
-    return pf_long_batch_chunk(R, mfe_dcal_hint, s0, m, rows_host.data(), cen_host, ms, &passes);
+    PflBatchLaunch launch;
+    return pf_long_rows(R, mfe_dcal_hint, s0, m, launch, rows_host.data(), cen_host, ms, &passes);
   });
   if (rc) return rc;  // (n == 0: no chunk)
   if (out && n > 0) memcpy(out, rows_host.data(), (size_t)n * sizeof(sf_pf_long_row));

@@ -12,7 +12,8 @@
 //     SF_PFLONG_LANES_PER_CU), never the batch's, never Lmax's;
 //   * the probability pass's wave count = pfl_prob_waves(L_s, lanes), a wave taking rows wave, wave + nwaves, ... of the
 //     triangle, and the finish adding the partial sums of that many waves in that order;
-//   * sc / mlbs, the row's own powers of its own scale, made on the host by the loop sf_pf_long runs (pfl_scale_powers).
+//   * sc / mlbs, the row's own powers of its own scale, made on the host by the one loop both entry points run
+//     (pfl_scale_powers in pf_long_rows, scanfold_hip.hip).
 // So a row's doubles are sf_pf_long's bit for bit, whatever else is in the call, in whatever order, however it is chunked.
 // How many workgroups a row gets (bps), hence how many cells a group walks, is free and comes from the batch's own budget.
 //

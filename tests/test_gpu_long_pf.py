@@ -299,3 +299,11 @@ def test_a_constraint_of_dots_is_no_constraint(gpu_engine):
 
 def test_the_shortest_records(gpu_engine, oracle):
     test_long_pf.check_the_shortest_records(gpu_engine, oracle)
+
+
+def test_failure_leaves_the_callers_buffers_alone(gpu_engine):
+    test_long_pf.check_failure_leaves_the_callers_buffers_alone(gpu_engine)
+
+
+def test_one_row_is_the_batchs_row_with_a_retry(gpu_engine):
+    test_long_pf.check_one_row_is_the_batchs_row_with_a_retry(gpu_engine)

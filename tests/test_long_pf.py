@@ -280,8 +280,45 @@ def check_the_shortest_records(engine, oracle):
         assert {k: row[k] for k in KEYS + ("centroid",)} == engine.pf_long(s), L
 
 
+def check_failure_leaves_the_callers_buffers_alone(engine):
+    """unbalanced brackets end sf_pf_long with SF_ERR_CONSTRAINT and not one byte of the caller's four buffers written; the
+    same call without the constraint fills them"""
+    s = b"ACGU" * 10
+    out = np.frombuffer(b"\x5a" * 24, dtype=np.float64).copy()
+    cen = np.frombuffer(b"?" * 41, dtype=np.uint8).copy()
+    a = [out[0:].ctypes.data, out[1:].ctypes.data, cen.ctypes.data, out[2:].ctypes.data]
+    assert engine.lib.sf_pf_long(s, 40, b"((((" + b"." * 36, None, *a) == -9
+    assert out.tobytes() == b"\x5a" * 24 and cen.tobytes() == b"?" * 41
+    assert engine.lib.sf_pf_long(s, 40, None, None, *a) == 0
+    assert np.isfinite(out).all() and cen[40] == 0 and set(bytes(cen[:40])) <= set(b"().")
+
+
+def check_one_row_is_the_batchs_row_with_a_retry(engine):
+    """the 150-nt row of test_long_pf_batch.test_a_row_that_repeats_leaves_the_others_alone, whose hint is thirty times its
+    MFE, folded alone: the single launches repeat the inside pass in the shared loop and end on the bits, the attempts and
+    the scale of the batch of that one row"""
+    s = rand_seq(np.random.default_rng(77), 150)
+    e, _ = engine.fold_long(s, structure=False)
+    assert e < -1000
+    h = 30 * e
+    got = engine.pf_long(s, mfe_hint=h)
+    t = engine.pf_long_times()
+    assert t["attempts"] > 1
+    row, = engine.pf_long_batch([s], mfe_hints=[h])
+    assert {k: row[k] for k in KEYS + ("centroid",)} == got
+    assert (row["attempts"], row["lns"]) == (t["attempts"], t["lns"])
+
+
 def test_a_constraint_of_dots_is_no_constraint(emul):
     check_a_constraint_of_dots_is_no_constraint(emul)
+
+
+def test_failure_leaves_the_callers_buffers_alone(emul):
+    check_failure_leaves_the_callers_buffers_alone(emul)
+
+
+def test_one_row_is_the_batchs_row_with_a_retry(emul):
+    check_one_row_is_the_batchs_row_with_a_retry(emul)
 
 
 def test_the_shortest_records(emul, oracle):
