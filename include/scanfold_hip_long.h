@@ -11,7 +11,8 @@
  * (a record and its shuffles: the z-score of a sequence past SF_MAX_W), and sf_pf_long_batch is sf_pf_long for many
  * sequences, constraints and hints side by side (the three ensembles of --global_ensemble; fc.pf() over long fragments),
  * every row bit for bit what sf_pf_long returns for it.  sf_fold_banded is sf_fold_long under a base-pair span in banded
- * tables: memory and work linear in the record's length, records up to SF_MAX_BANDED nucleotides, the same bytes.
+ * tables: memory and work linear in the record's length, records up to SF_MAX_BANDED nucleotides, the same bytes;
+ * sf_pf_banded is sf_pf_long under a span in banded tables likewise, to rounding.
  * Soft constraints (SHAPE) are not provided past SF_MAX_W.
  */
 #ifndef SCANFOLD_HIP_LONG_H
@@ -107,6 +108,41 @@ int sf_pf_long(const uint8_t *seq, int L, const char *cons, const int32_t *mfe_d
  * outside pass with the probabilities, the number of attempts, and the final per-nucleotide scale ln s.  Any pointer may be
  * NULL. */
 int sf_pf_long_times(double *inside_ms, double *outside_ms, int *attempts, double *lns);
+
+/* device memory of one sf_pf_banded call with band B = min(span, L): seven FP64 band tables and what is linear in L and B
+ * (mantissas and exponents of q5 / q3, sequence, centroid, the constraint's 9 (L + 2); the powers of the scale and the
+ * hairpin weights up to B; 64 KiB of partial sums) */
+#define SF_PF_BANDED_BYTES(L, B) (56 * (size_t)(L) * (size_t)(B) + 35 * (size_t)(L) + 24 * (size_t)(B) + 65677)
+
+/* sf_pf_long under the resident base-pair span S (sf_set_max_bp_span, S >= 1) with the tables stored as a band of
+ * B = min(S, L) diagonals: a cell (i, j) with j - i >= S cannot pair, and no cell inside the band reads one outside it, so
+ * the band holds the same sums as sf_pf_long's triangles.  Arguments, outputs and staging as for sf_pf_long (any output
+ * pointer may be NULL; nothing reaches the caller unless the call succeeds); limits and argument errors as for
+ * sf_fold_banded: 1 <= L <= SF_MAX_BANDED, S >= L is legal (B = L), the constraint's bracket partners are int32.
+ * Memory is SF_PF_BANDED_BYTES(L, B) (1.0 GB at L = 29 903, S = 600, where sf_pf_long takes 25 GB; 16.8 GB at L = 500 000) and a pass costs about
+ * L B^2 / 2 terms in B launches, where sf_pf_long's costs L^3 / 6.
+ * The exterior loop (q5 / q3) carries a binary exponent per position, so it does not depend on one scale holding for L
+ * nucleotides: records whose composition changes along their length, and records past SF_MAX_LONG, work.  The band tables
+ * keep one per-nucleotide scale ln s: the first from mfe_dcal_hint as in sf_pf_long; an inside pass whose ln Z_s / L = eps
+ * has |eps| B > 300 is repeated with ln s + eps (exact: the exterior loop cannot leave the range), one whose tables left
+ * FP64 with ln s +- 700 / B; non-finite outputs of the outside pass re-centre once.  After 6 attempts: SF_ERR_RANGE, and no
+ * output is written.  Known limit: the band tables need |g - ln s| B <~ 700 for the local growth g of ln Z per nucleotide,
+ * everywhere along the record; a strongly heterogeneous record under a span of several thousand can end in SF_ERR_RANGE.
+ * Two calls with the same arguments on the same device return bit-identical results; agreement with sf_pf_long under the
+ * same span is to rounding (sums in another order), not bit for bit.
+ * No span set, L < 1, L > SF_MAX_BANDED, seq NULL: SF_ERR_BAD_ARG.  Unbalanced brackets: SF_ERR_CONSTRAINT, before anything
+ * is launched.  Not enough device memory: SF_ERR_HIP with the text in sf_last_hip_error(). */
+int sf_pf_banded(const uint8_t *seq, int L, const char *cons, const int32_t *mfe_dcal_hint, double *ens_dG, double *mean_bp_dist,
+                 char *centroid_out, double *centroid_dist);
+
+/* Of the last sf_pf_banded that ran: device-event times (ms) of the inside passes (all attempts, q5 / q3 included) and of
+ * the outside passes with the probabilities, the number of attempts, the final per-nucleotide scale ln s, the band B, and
+ * the number of diagonal launches over all attempts (B per inside pass, B - 4 per outside pass).  Any pointer may be NULL. */
+int sf_pf_banded_times(double *inside_ms, double *outside_ms, int *attempts, double *lns, int *band, int *launches);
+
+/* What sf_pf_banded would allocate for a record of L nucleotides under the span `span`: SF_PF_BANDED_BYTES(L, min(span, L)).
+ * Needs sf_init only; nothing is allocated.  L < 1, L > SF_MAX_BANDED, span < 1, bytes NULL: SF_ERR_BAD_ARG. */
+int sf_pf_banded_bytes(int L, int span, size_t *bytes);
 
 /* One row of sf_pf_long_batch: sf_pf_long's three numbers, the final per-nucleotide scale ln s and the number of inside
  * passes the row took (what sf_pf_long_times reports for the row folded alone). */

@@ -89,6 +89,11 @@ _LONG_EXPORTS = {
                                   ctypes.c_void_p, ctypes.c_void_p]),
     "sf_pf_long_times": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                         ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)]),
+    "sf_pf_banded": (ctypes.c_int, [_c_u8p, ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                    ctypes.c_void_p, ctypes.c_void_p]),
+    "sf_pf_banded_times": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double)] * 2 + [ctypes.POINTER(ctypes.c_int),
+                                          ctypes.POINTER(ctypes.c_double)] + [ctypes.POINTER(ctypes.c_int)] * 2),
+    "sf_pf_banded_bytes": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
     "sf_pf_long_batch": (ctypes.c_int, [_c_u8p, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 5),
     "sf_pf_long_batch_times": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                               ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
@@ -146,6 +151,7 @@ _FOLD_LONG = ("sf_fold_long", "whole-record folds")
 _FOLD_BANDED = ("sf_fold_banded", "whole-record folds under a base-pair span in banded tables")
 _FOLD_LONG_BATCH = ("sf_fold_long_batch", "folds of sequences past %d nt" % SF_MAX_W)
 _PF_LONG = ("sf_pf_long", "whole-record partition functions")
+_PF_BANDED = ("sf_pf_banded", "whole-record partition functions under a base-pair span in banded tables")
 _PF_LONG_BATCH = ("sf_pf_long_batch", "partition functions of many sequences past %d nt" % SF_MAX_W)
 _DUPLEX = ("duplex entry points (sf_duplex_batch, sf_lri_scan, sf_lri_background)", "duplex folds and --lri",
            tuple(_DUPLEX_EXPORTS))
@@ -471,6 +477,41 @@ class Engine:
         a, b, n, l = ctypes.c_double(), ctypes.c_double(), ctypes.c_int(), ctypes.c_double()
         self._check(self.lib.sf_pf_long_times(ctypes.byref(a), ctypes.byref(b), ctypes.byref(n), ctypes.byref(l)))
         return dict(inside_ms=a.value, outside_ms=b.value, attempts=n.value, lns=l.value)
+
+    def has_pf_banded(self):
+        return getattr(self.lib, "sf_pf_banded", None) is not None
+
+    def pf_banded(self, seq, cons=None, mfe_hint=None):
+        """pf_long under the resident base-pair span (set_max_bp_span(S), S >= 1) in banded tables (sf_pf_banded): ONE
+        sequence of 1..SF_MAX_BANDED nt -> pf_long's dict, equal to pf_long's under the same span to rounding, from
+        56 L min(S, L) bytes of tables.  The exterior loop carries its own exponents, so records past SF_MAX_LONG and
+        records whose composition changes along their length work.  Raises ScanFoldHipError where no span is set, and on a
+        library without the entry point (there is no fallback)."""
+        self._need(*_PF_BANDED)
+        arr, L, c = _record(seq, cons)
+        hint = None if mfe_hint is None else np.array([int(mfe_hint)], dtype=np.int32)
+        out = np.zeros(3)
+        cen = np.zeros(L + 1, dtype=np.uint8)
+        self._check(self.lib.sf_pf_banded(arr.ctypes.data, L, c, None if hint is None else hint.ctypes.data,
+                                          out[0:].ctypes.data, out[1:].ctypes.data, cen.ctypes.data, out[2:].ctypes.data))
+        return dict(dG=float(out[0]), mean_bp_dist=float(out[1]), centroid=bytes(cen[:L]).decode(),
+                    centroid_dist=float(out[2]))
+
+    def pf_banded_times(self):
+        """-> dict(inside_ms, outside_ms, attempts, lns, band, launches) of the last pf_banded (device events; lns = the band
+        tables' per-nucleotide scale, band = min(span, L), launches = diagonal launches over all attempts)."""
+        self._need(*_PF_BANDED)
+        a, b, n, l, bd, ln = (ctypes.c_double(), ctypes.c_double(), ctypes.c_int(), ctypes.c_double(), ctypes.c_int(),
+                              ctypes.c_int())
+        self._check(self.lib.sf_pf_banded_times(*(ctypes.byref(x) for x in (a, b, n, l, bd, ln))))
+        return dict(inside_ms=a.value, outside_ms=b.value, attempts=n.value, lns=l.value, band=bd.value, launches=ln.value)
+
+    def pf_banded_bytes(self, L, span):
+        """the device memory pf_banded would allocate for L nucleotides under `span` (sf_pf_banded_bytes)"""
+        self._need(*_PF_BANDED)
+        n = ctypes.c_size_t()
+        self._check(self.lib.sf_pf_banded_bytes(int(L), int(span), ctypes.byref(n)))
+        return int(n.value)
 
     def has_pf_long_batch(self):
         return getattr(self.lib, "sf_pf_long_batch", None) is not None

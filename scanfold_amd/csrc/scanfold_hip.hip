@@ -25,6 +25,7 @@
 #include "sf_pf.hip.h"
 #include "sf_pf_long.hip.h"
 #include "sf_pf_long_batch.hip.h"
+#include "sf_pf_banded.hip.h"
 #include "sf_pf_fast.hip.h"
 #include "sf_pf_lds.hip.h"
 #include "sf_shuffle.hip.h"
@@ -1401,6 +1402,50 @@ int band_group(int d, size_t cells) {
   return G;
 }
 
+// A constraint of any length, parsed on the host (sf_hc_parse with int32 positions) for sf_fold_banded and sf_pf_banded:
+// the host walks the row for balance anyway, and positions pass 32 767.
+struct BandHc {
+  std::vector<int32_t> part, encl;
+  std::vector<char> c;
+  // SF_ERR_CONSTRAINT for unbalanced brackets
+  int parse(const char *cons, int L) {
+    part.assign((size_t)L + 2, 0);
+    encl.assign((size_t)L + 2, 0);
+    c.assign((size_t)L + 2, 0);
+    std::vector<int32_t> stack;
+    for (int i = 1; i <= L; i++) {
+      const char ch = cons[i - 1];
+      c[i] = ch;
+      if (ch == ')') {
+        if (stack.empty()) return SF_ERR_CONSTRAINT;
+        const int o = stack.back();
+        stack.pop_back();
+        part[o] = i;
+        part[i] = o;
+      }
+      encl[i] = stack.empty() ? 0 : stack.back();
+      if (ch == '(') stack.push_back(i);
+    }
+    return stack.empty() ? SF_OK : SF_ERR_CONSTRAINT;
+  }
+  // uploads the three arrays (9 (L + 2) bytes) into allocations of Bf and binds them
+  int bind(LongBufs &Bf, SfHc32 &hc) const {
+    int rc;
+    void *dc, *dp, *de;
+    const size_t n = c.size();
+    if ((rc = Bf.alloc(&dc, n, "constraint"))) return rc;
+    if ((rc = Bf.alloc(&dp, n * sizeof(int32_t), "bracket partners"))) return rc;
+    if ((rc = Bf.alloc(&de, n * sizeof(int32_t), "enclosing pairs"))) return rc;
+    HIPCHK(hipMemcpyAsync(dc, c.data(), n, hipMemcpyHostToDevice, g.stream));
+    HIPCHK(hipMemcpyAsync(dp, part.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, g.stream));
+    HIPCHK(hipMemcpyAsync(de, encl.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, g.stream));
+    hc.c = (const char *)dc;
+    hc.partner = (const int32_t *)dp;
+    hc.encl = (const int32_t *)de;
+    return SF_OK;
+  }
+};
+
 size_t band_linear_bytes(int L, int B) {
   return 3 * ((size_t)L + 2) * 4        // DML ring
          + ((size_t)L + 1) * 4          // f5
@@ -1429,47 +1474,13 @@ int sf_fold_banded(const uint8_t *seq, int L, const char *cons, int32_t *mfe_out
   if (!seq || L < 1 || L > SF_MAX_BANDED || g.max_bp_span < 1) return SF_ERR_BAD_ARG;
   const int B = std::min(g.max_bp_span, L);
   // the constraint, parsed here (sf_hc_parse with int32 positions); unbalanced brackets end the call before any launch
-  std::vector<int32_t> hpart, hencl;
-  std::vector<char> hc;
-  if (cons) {
-    hpart.assign((size_t)L + 2, 0);
-    hencl.assign((size_t)L + 2, 0);
-    hc.assign((size_t)L + 2, 0);
-    std::vector<int32_t> stack;
-    for (int i = 1; i <= L; i++) {
-      const char ch = cons[i - 1];
-      hc[i] = ch;
-      if (ch == ')') {
-        if (stack.empty()) return SF_ERR_CONSTRAINT;
-        const int o = stack.back();
-        stack.pop_back();
-        hpart[o] = i;
-        hpart[i] = o;
-      }
-      hencl[i] = stack.empty() ? 0 : stack.back();
-      if (ch == '(') stack.push_back(i);
-    }
-    if (!stack.empty()) return SF_ERR_CONSTRAINT;
-  }
+  BandHc H;
+  if (cons && (rc = H.parse(cons, L))) return rc;
   SfBand F;
   memset(&F, 0, sizeof F);
   F.L = L;
   F.B = B;
-  auto bind_hc = [&](LongBufs &Bf, SfBand &F) -> int {
-    if (!cons) return SF_OK;
-    int rc;
-    void *dc, *part, *encl;
-    if ((rc = Bf.alloc(&dc, (size_t)L + 2, "constraint"))) return rc;
-    if ((rc = Bf.alloc(&part, ((size_t)L + 2) * sizeof(int32_t), "bracket partners"))) return rc;
-    if ((rc = Bf.alloc(&encl, ((size_t)L + 2) * sizeof(int32_t), "enclosing pairs"))) return rc;
-    HIPCHK(hipMemcpyAsync(dc, hc.data(), (size_t)L + 2, hipMemcpyHostToDevice, g.stream));
-    HIPCHK(hipMemcpyAsync(part, hpart.data(), ((size_t)L + 2) * sizeof(int32_t), hipMemcpyHostToDevice, g.stream));
-    HIPCHK(hipMemcpyAsync(encl, hencl.data(), ((size_t)L + 2) * sizeof(int32_t), hipMemcpyHostToDevice, g.stream));
-    F.hc.c = (const char *)dc;
-    F.hc.partner = (const int32_t *)part;
-    F.hc.encl = (const int32_t *)encl;
-    return SF_OK;
-  };
+  auto bind_hc = [&](LongBufs &Bf, SfBand &F) -> int { return cons ? H.bind(Bf, F.hc) : SF_OK; };
   auto fill = [&](const SfBand &F, const SfDevParams *D, int threads) {
     for (int d = 0; d < B; d++) {
       const size_t cells = (size_t)(L - d);
@@ -1921,6 +1932,185 @@ int sf_pf_long_times(double *inside_ms, double *outside_ms, int *attempts, doubl
   if (outside_ms) *outside_ms = g_pfl_ms[1];
   if (attempts) *attempts = g_pfl_attempts;
   if (lns) *lns = g_pfl_lns;
+  return SF_OK;
+}
+
+}  // extern "C"
+
+// ---------------- whole-record partition function under a span in banded tables (sf_pf_banded.hip.h) ----------------
+namespace {
+double g_pfb_ms[2] = {0, 0};  // inside (all attempts, with q5 / q3), outside (with the probabilities) of the last sf_pf_banded
+int g_pfb_attempts = 0, g_pfb_band = 0, g_pfb_launches = 0;
+double g_pfb_lns = 0.0;
+
+// |ln Z_s / L| B above which an inside pass is repeated with the scale it measured: a cell of B nucleotides is then within
+// e^+-300 of its neighbours' weights, which leaves the outside pass (products of two such cells) inside FP64
+const double kPfBandEpsB = 300.0;
+}  // namespace
+
+extern "C" {
+
+int sf_pf_banded_bytes(int L, int span, size_t *bytes) {
+  SF_ENTER();
+  if (L < 1 || L > SF_MAX_BANDED || span < 1 || !bytes) return SF_ERR_BAD_ARG;
+  *bytes = SF_PF_BANDED_BYTES(L, std::min(span, L));
+  return SF_OK;
+}
+
+int sf_pf_banded(const uint8_t *seq, int L, const char *cons, const int32_t *mfe_dcal_hint, double *ens_dG, double *mean_bp_dist,
+                 char *centroid_out, double *centroid_dist) {
+  int rc = check_ready();
+  if (rc) return rc;
+  if (!seq || L < 1 || L > SF_MAX_BANDED || g.max_bp_span < 1) return SF_ERR_BAD_ARG;
+  const int B = std::min(g.max_bp_span, L);
+  BandHc H;  // unbalanced brackets end the call before any launch
+  if (cons && (rc = H.parse(cons, L))) return rc;
+
+  const Ctx::ModelSlot &M = g.slot[g.cur];
+  const double kT = M.pf_kT, ln_mlbase = log(M.pf_MLbase);
+  const size_t nL = (size_t)L, nB = (size_t)B, lanes = pfl_lanes();
+  const int prob_waves = std::min(pfl_prob_waves(L, lanes), SF_PFBAND_MAX_WAVES);
+  std::vector<uint8_t> hS(nL + 2, 0);
+  for (int x = 0; x < L; x++) hS[x + 1] = sf_encode_nt(seq[x]);
+  const std::vector<double> hhp = pfl_hairpin_table(M, B);
+  // (these outlive Bf: the copies into them are drained by its destructor on an early return)
+  std::vector<double> hpow(2 * (nB + 2));
+  std::vector<char> hcen(nL + 1);
+  double hout[3] = {0, 0, 0};
+
+  // slices of the FP64 block, in elements: results, the powers of the scale, hairpin weights, the mantissas of q5 and q3,
+  // the partial sums of the probability pass.  SF_PF_BANDED_BYTES counts exactly these allocations.
+  const size_t o_out = 0, o_pow = o_out + 4, o_hp = o_pow + 2 * (nB + 2), o_m5 = o_hp + nB + 1, o_m3 = o_m5 + nL + 2;
+  const size_t o_part = o_m3 + nL + 2, n_f64 = o_part + 2 * (size_t)SF_PFBAND_MAX_WAVES;
+  SfPfBand F;
+  memset(&F, 0, sizeof F);
+  F.L = L;
+  F.B = B;
+  LongBufs Bf;
+  Bf.who = "sf_pf_banded";
+  void *p;
+  double *d_tab[SF_PFBAND_NTAB];
+  static const char *const tab_names[SF_PFBAND_NTAB] = {"qb", "qb by columns / A0", "qm", "qm by columns", "qm1 / w", "ob", "A1"};
+  for (int k = 0; k < SF_PFBAND_NTAB; k++) {
+    if ((rc = Bf.alloc(&p, nL * nB * sizeof(double), tab_names[k]))) return rc;
+    d_tab[k] = (double *)p;
+  }
+  if ((rc = Bf.alloc(&p, n_f64 * sizeof(double), "results, scale powers, hairpin weights, q5, q3, partial sums"))) return rc;
+  double *d_f64 = (double *)p;
+  if ((rc = Bf.alloc(&p, 2 * (nL + 2) * sizeof(int32_t), "exponents of q5 and q3"))) return rc;
+  F.e5 = (int32_t *)p;
+  F.e3 = F.e5 + nL + 2;
+  if ((rc = Bf.alloc(&p, 2 * nL + 3, "sequence, centroid"))) return rc;
+  uint8_t *d_u8 = (uint8_t *)p;
+  F.S = d_u8;
+  F.cen = (char *)d_u8 + nL + 2;
+  F.qb = d_tab[0]; F.qbt = d_tab[1]; F.qm = d_tab[2]; F.qmt = d_tab[3]; F.qm1t = d_tab[4]; F.ob = d_tab[5]; F.a1 = d_tab[6];
+  F.a0 = F.qbt;   // (dead after q5)
+  F.wt = F.qm1t;  // (dead after the inside pass)
+  F.out = d_f64 + o_out;
+  F.sc = d_f64 + o_pow;
+  F.mlbs = F.sc + nB + 2;
+  F.hpx = d_f64 + o_hp;
+  F.m5 = d_f64 + o_m5;
+  F.m3 = d_f64 + o_m3;
+  F.part = d_f64 + o_part;
+  HIPCHK(hipMemcpyAsync(d_u8, hS.data(), nL + 2, hipMemcpyHostToDevice, g.stream));
+  HIPCHK(hipMemcpyAsync(d_f64 + o_hp, hhp.data(), hhp.size() * sizeof(double), hipMemcpyHostToDevice, g.stream));
+  if (cons && (rc = H.bind(Bf, F.hc))) return rc;
+  for (auto &e : Bf.ev) HIPCHK(hipEventCreate(&e));
+
+  const SfDevParams *D = (const SfDevParams *)g.dP;
+  const SfDevParamsPF *X = (const SfDevParamsPF *)g.dX;
+  auto diagonal = [&](void (*kernel)(SfPfBand, int, int, const SfDevParams *, const SfDevParamsPF *), int d) {
+    const int threads = 256;
+    const size_t cells = (size_t)(L - d);
+    const int G = pfl_group(cells, d, lanes);
+    const size_t total = std::min(cells * (size_t)G, lanes);
+    SF_LAUNCH(kernel, (int)((total + threads - 1) / threads), threads, 0, g.stream, F, d, G, D, X);
+  };
+  // (a band of at most TURN + 1 diagonals holds no pair: Z = 1 whatever the scale, and scale 1 gives it exactly)
+  double lns = B <= SFD_TURN + 1 ? 0.0 : pfl_first_lns(mfe_dcal_hint, kT, L), ms_in = 0, ms_out = 0, dG = 0;
+  int attempts = 0, launches = 0;
+  // every way out once something was launched: the status word is read, and the times, scale and attempts are kept
+  auto leave = [&](int range_rc) {
+    const int status_rc = read_status(g.stream, false);
+    if (status_rc) return status_rc;
+    g_pfb_ms[0] = ms_in;
+    g_pfb_ms[1] = ms_out;
+    g_pfb_attempts = attempts;
+    g_pfb_lns = lns;
+    g_pfb_band = B;
+    g_pfb_launches = launches;
+    return range_rc;
+  };
+  float ms = 0;
+  for (;;) {
+    if (attempts >= SF_PFLONG_MAX_ATTEMPTS) return leave(SF_ERR_RANGE);
+    attempts++;
+    pfl_scale_powers(lns, ln_mlbase, B, hpow.data(), hpow.data() + nB + 2);
+    HIPCHK(hipMemcpyAsync(d_f64 + o_pow, hpow.data(), hpow.size() * sizeof(double), hipMemcpyHostToDevice, g.stream));
+    HIPCHK(hipEventRecord(Bf.ev[0], g.stream));
+    for (int d = 0; d < B; d++) diagonal(sf_pfband_inside_kernel, d);
+    HIPCHK(hipGetLastError());
+    SF_LAUNCH(sf_pfband_exterior_kernel, 2, 64, 0, g.stream, F, D, X);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(Bf.ev[1], g.stream));
+    HIPCHK(hipMemcpyAsync(hout, d_f64 + o_out, sizeof hout, hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipStreamSynchronize(g.stream));
+    HIPCHK(hipEventElapsedTime(&ms, Bf.ev[0], Bf.ev[1]));
+    ms_in += ms;
+    launches += B;
+    // The exterior loop carries its own exponents, so a finite ln Z_s gives the scale's error per nucleotide exactly
+    // whatever its size; where the band tables left the range, step by what a cell of B nucleotides can bear.
+    const double lz = hout[0], eps = lz / L;
+    if (!isfinite(lz)) {  // (an overflow gives +inf or NaN; NaN counts as an overflow)
+      lns += (lz < 0 ? -700.0 : 700.0) / B;
+      continue;
+    }
+    if (fabs(eps) * B > kPfBandEpsB) {
+      lns += eps;
+      continue;
+    }
+    HIPCHK(hipMemsetAsync(F.cen, '.', nL + 1, g.stream));
+    HIPCHK(hipEventRecord(Bf.ev[2], g.stream));
+    for (int d = B - 1; d >= SFD_TURN + 1; d--) diagonal(sf_pfband_outside_kernel, d);
+    HIPCHK(hipGetLastError());
+    SF_LAUNCH(sf_pfband_prob_kernel, prob_waves, 64, 0, g.stream, F);
+    SF_LAUNCH(sf_pfband_finish_kernel, 1, 64, 0, g.stream, F, prob_waves);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(Bf.ev[3], g.stream));
+    HIPCHK(hipMemcpyAsync(hout, d_f64 + o_out, sizeof hout, hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipMemcpyAsync(hcen.data(), F.cen, nL, hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipStreamSynchronize(g.stream));
+    HIPCHK(hipEventElapsedTime(&ms, Bf.ev[2], Bf.ev[3]));
+    ms_out += ms;
+    launches += std::max(0, B - 1 - SFD_TURN);
+    if (isfinite(hout[1]) && isfinite(hout[2])) {
+      dG = -(lz + (double)L * lns) * kT / 1000.0;
+      if (!isfinite(dG)) return leave(SF_ERR_RANGE);
+      break;
+    }
+    if (fabs(eps) * B < 1.0) return leave(SF_ERR_RANGE);  // Z_s is centred and the outside tables still leave the range
+    lns += eps;
+  }
+  if ((rc = leave(SF_OK))) return rc;
+  // staged until here: nothing reaches the caller unless the call succeeds
+  hcen[nL] = 0;
+  if (ens_dG) *ens_dG = dG;
+  if (mean_bp_dist) *mean_bp_dist = hout[1];
+  if (centroid_dist) *centroid_dist = hout[2];
+  if (centroid_out) memcpy(centroid_out, hcen.data(), nL + 1);
+  return SF_OK;
+}
+
+int sf_pf_banded_times(double *inside_ms, double *outside_ms, int *attempts, double *lns, int *band, int *launches) {
+  SF_ENTER();
+  if (inside_ms) *inside_ms = g_pfb_ms[0];
+  if (outside_ms) *outside_ms = g_pfb_ms[1];
+  if (attempts) *attempts = g_pfb_attempts;
+  if (lns) *lns = g_pfb_lns;
+  if (band) *band = g_pfb_band;
+  if (launches) *launches = g_pfb_launches;
   return SF_OK;
 }
 

@@ -14,6 +14,8 @@ refolds of ScanFold.py:1582-1776 (scanfold_amd.motifs: `<that>.ExtractedStructur
 then with the -1 and the -2 filter's dot-bracket lines as hard constraints, through the RNA facade (whole-record folds,
 sf_fold_long), into `<that>.<--dbn_file_path>` and `<that>.AllDBN.txt`.  ScanFold.py's per-record directories and IGV
 wig exports are not reproduced.
+--global_span N (not upstream) runs those three folds under max bp span N in banded tables (sf_fold_banded), and
+--global_ensemble_banded adds their ensembles from the banded partition function (sf_pf_banded), at any record length.
 --global_zscore (not upstream) z-scores the whole record against shuffles of itself (one batched whole-record fold,
 sf_fold_long_batch) into `<that>.global_zscore.txt`.
 --lri replaces the window scan by the k-mer duplex scan (ScanFold.py:391-393,421,769-1034; scanfold_amd.lri): it writes
@@ -152,7 +154,8 @@ def read_reactivities(path):
     return vec
 
 
-def global_refold(seq, name, outname, temperature, dbn_file_path="AllDBN-global_refold.txt", ensemble=False, span=0):
+def global_refold(seq, name, outname, temperature, dbn_file_path="AllDBN-global_refold.txt", ensemble=False, span=0,
+                  ensemble_banded=False):
     """ScanFold.py:1509-1547 (--global_refold): a fresh RNA.md() at md.temperature = int(-t) — no --span, exactly as
     upstream — folds the whole record unconstrained and with line 3 of `<outname>.ScanFold.-1.dbn` / `.-2.dbn` as
     hc_add_from_db constraint, and writes the three records to `<outname>.<dbn_file_path>`; `<outname>.AllDBN.txt` is the
@@ -168,7 +171,10 @@ def global_refold(seq, name, outname, temperature, dbn_file_path="AllDBN-global_
     MFE) into `<outname>.<dbn_file_path minus .txt>.ensemble.txt`, three records of a header line (ensemble free
     energy, ED = mean base-pair distance to 2 decimals, centroid distance), the sequence and the centroid.
     span (--global_span N, not upstream): the three folds run under max_bp_span = N in banded tables (Engine.fold_banded:
-    memory and work linear in the record's length, records past SF_MAX_LONG), and the header lines gain " span=N"."""
+    memory and work linear in the record's length, records past SF_MAX_LONG), and the header lines gain " span=N".
+    ensemble_banded (--global_ensemble_banded, not upstream; needs span): the same ensemble file from Engine.pf_banded, the
+    partition function under the span in banded tables, each fold's MFE as hint: any record fold_banded takes, where
+    --global_ensemble stops at SF_MAX_LONG.  Its header lines carry " span=N" too."""
     from . import RNA
     md = RNA.md()
     md.temperature = int(temperature)
@@ -198,7 +204,11 @@ def global_refold(seq, name, outname, temperature, dbn_file_path="AllDBN-global_
             s2, e2 = fc.mfe()
             s0, e0 = RNA.fold_compound(seq, md).mfe()
         ens = []
-        if ensemble and len(seq) > _lib.SF_MAX_W and eng.has_pf_long_batch():
+        if ensemble_banded:
+            if span < 1:
+                raise ValueError("the banded ensemble needs a base-pair span")
+            ens = [eng.pf_banded(seq, c, mfe_hint=int(round(e * 100))) for c, e in ((None, e0), (cons[0], e1), (cons[1], e2))]
+        elif ensemble and len(seq) > _lib.SF_MAX_W and eng.has_pf_long_batch():
             # the three ensembles in the same launches; each row is pf_long's bit for bit
             ens = eng.pf_long_batch([seq] * 3, [None, cons[0], cons[1]], [int(round(e * 100)) for e in (e0, e1, e2)])
         elif ensemble:
@@ -221,12 +231,13 @@ def global_refold(seq, name, outname, temperature, dbn_file_path="AllDBN-global_
         w.write(">" + str(name) + "\tGlobal Full MFE=" + str(e0) + tail + "\n" + seq + "\n" + s0 + "\n")
         w.write(">" + str(name) + "\tRefolded with -1 constraints MFE=" + str(e1) + tail + "\n" + seq + "\n" + s1 + "\n")
         w.write(">" + str(name) + "\tRefolded with -2 constraints MFE=" + str(e2) + tail + "\n" + seq + "\n" + s2 + "\n")
-    if ensemble:
+    if ensemble or ensemble_banded:
+        ens_tail = tail if ensemble_banded else ""
         stem = dbn_file_path[:-4] if dbn_file_path.endswith(".txt") else dbn_file_path
         with open(outname + "." + stem + ".ensemble.txt", "w") as w:
             for label, r in zip(("Global Full", "Refolded with -1 constraints", "Refolded with -2 constraints"), ens):
-                w.write(">%s\t%s ensemble dG=%.2f ED=%.2f centroid distance=%.2f\n%s\n%s\n"
-                        % (name, label, r["dG"], r["mean_bp_dist"], r["centroid_dist"], seq, r["centroid"]))
+                w.write(">%s\t%s ensemble dG=%.2f ED=%.2f centroid distance=%.2f%s\n%s\n%s\n"
+                        % (name, label, r["dG"], r["mean_bp_dist"], r["centroid_dist"], ens_tail, seq, r["centroid"]))
     with open(outname + ".AllDBN.txt", "w") as w:
         for tag in ("no_filter", "-1", "-2"):
             with open(outname + ".ScanFold." + tag + ".dbn") as f:
@@ -301,6 +312,9 @@ def build_parser():
     p.add_argument('--global_span', type=int, default=None,
                    help='not in upstream ScanFold: with --global_refold, fold the whole record under this max bp span in banded '
                         'tables (memory and time linear in its length; records past 32767 nt)')
+    p.add_argument('--global_ensemble_banded', action='store_true',
+                   help='not in upstream ScanFold: with --global_refold and --global_span N, write the ensemble file of '
+                        '--global_ensemble from the partition function under the span in banded tables (records past 32767 nt)')
     p.add_argument('--global_zscore', action='store_true',
                    help='not in upstream ScanFold: z-score of the whole record (its MFE at -t, no --span, against -r shuffles of '
                         '--type seeded with --seed) into <output prefix>.global_zscore.txt; costs r + 1 whole-record folds')
@@ -329,14 +343,26 @@ def main(argv=None):
         raise ValueError("--global_refold refolds with the -1 / -2 dbn files of the Fold stage: not with -c 0 or --dont_fold")
     if args.global_ensemble and not args.global_refold:
         raise ValueError("--global_ensemble adds the partition function to the folds of --global_refold: give both")
+    if args.global_ensemble_banded and (not args.global_refold or args.global_span is None):
+        raise ValueError("--global_ensemble_banded is the ensemble of the folds of --global_refold under --global_span N: "
+                         "give all three")
+    if args.global_ensemble_banded and args.global_ensemble:
+        raise ValueError("--global_ensemble and --global_ensemble_banded write the same file: give one of them")
     if args.global_span is not None and (not args.global_refold or args.global_span < 1):
         raise ValueError("--global_span N (N >= 1) sets the base-pair span of the folds of --global_refold: give both")
     if args.global_span is not None and (args.global_ensemble or args.global_zscore):  # refused before any record is scanned
         for read_name, seq in scanmod.read_fasta(args.filename):
             if len(seq) > _lib.SF_MAX_LONG:
-                raise ValueError("--global_span: record %s has %d nt; %s has no banded form yet and stops at %d nt"
-                                 % (read_name, len(seq), "--global_ensemble (the partition function)" if args.global_ensemble
-                                    else "--global_zscore (the batched fold of the shuffles)", _lib.SF_MAX_LONG))
+                raise ValueError("--global_span: record %s has %d nt; %s stops at %d nt"
+                                 % (read_name, len(seq), "--global_ensemble (the partition function in full tables; "
+                                    "--global_ensemble_banded has no such limit)" if args.global_ensemble
+                                    else "--global_zscore (the batched fold of the shuffles) has no banded form yet and",
+                                    _lib.SF_MAX_LONG))
+    if args.global_ensemble_banded:  # refused before any record is scanned
+        for read_name, seq in scanmod.read_fasta(args.filename):
+            if len(seq) > _lib.SF_MAX_BANDED:
+                raise ValueError("--global_ensemble_banded: record %s has %d nt, banded folds stop at %d"
+                                 % (read_name, len(seq), _lib.SF_MAX_BANDED))
     if args.global_zscore and args.lri:
         raise ValueError("--global_zscore z-scores the record of a window scan: not with --lri")
     if args.global_zscore:  # refused before any record is scanned
@@ -413,7 +439,7 @@ def main(argv=None):
             if args.global_refold:
                 print("Refolding full sequence using ScanFold results as constraints...")
                 global_refold(seq, args.name, outname, args.t, args.dbn_file_path, ensemble=args.global_ensemble,
-                              span=args.global_span or 0)
+                              span=args.global_span or 0, ensemble_banded=args.global_ensemble_banded)
             if args.c == 1 and not args.dont_extract:
                 with open(outname + ".ScanFold.-2.dbn") as f:
                     line = f.readlines()[2]
