@@ -1688,6 +1688,27 @@ std::vector<double> pfl_hairpin_table(const Ctx::ModelSlot &M, int n) {
 // the lane budget of ONE sf_pf_long call: it sizes every row's lane groups and probability waves, whatever a batch holds
 size_t pfl_lanes() { return (size_t)(g.n_cu > 0 ? g.n_cu : 1) * SF_PFLONG_LANES_PER_CU; }
 
+// the seven tables of a state (SfPfLong, SfPfBand) out of seven allocations, `off` elements into each; their names in the
+// text of a failed allocation
+const char *const kPfTableNames[7] = {"qb", "qb by columns / A0", "qm", "qm by columns", "qm1 / w", "ob", "A1"};
+template <class T>
+void pfl_bind_tables(T &F, double *const tab[7], size_t off) {
+  F.qb = tab[0] + off; F.qbt = tab[1] + off; F.qm = tab[2] + off; F.qmt = tab[3] + off;
+  F.qm1t = tab[4] + off; F.ob = tab[5] + off; F.a1 = tab[6] + off;
+  F.a0 = F.qbt;   // (dead after q5)
+  F.wt = F.qm1t;  // (dead after the inside pass)
+}
+// one diagonal of the inside or outside pass of a single sequence: its own lane groups and grid
+template <class T>
+void pfl_launch_diagonal(void (*kernel)(T, int, int, const SfDevParams *, const SfDevParamsPF *), const T &F, int d, size_t lanes) {
+  const int threads = 256;
+  const size_t cells = (size_t)(F.L - d);
+  const int G = pfl_group(cells, d, lanes);
+  const size_t total = std::min(cells * (size_t)G, lanes);
+  SF_LAUNCH(kernel, (int)((total + threads - 1) / threads), threads, 0, g.stream, F, d, G, (const SfDevParams *)g.dP,
+            (const SfDevParamsPF *)g.dX);
+}
+
 // The partition functions of rows s0 .. s0 + n - 1 of R: the host side of sf_pf_long (its one row) and of one chunk of
 // sf_pf_long_batch, after their argument checks.  hint: NULL, or one value per row of the call (SF_PF_LONG_NO_HINT: none).
 // rows_host / cen_host: the caller's staging buffers (the records at rows_host[s0 ..], the centroids back to back, L + 1
@@ -1729,9 +1750,8 @@ int pf_long_rows(const LongRows &R, const int32_t *hint, int s0, int n, Launch &
   void *p;
   double *d_tri[SF_PFLONG_NTRI], *d_f64;
   uint8_t *d_u8;
-  static const char *const tri_names[SF_PFLONG_NTRI] = {"qb", "qb transposed / A0", "qm", "qm transposed", "qm1 / w", "ob", "A1"};
   for (int k = 0; k < SF_PFLONG_NTRI; k++) {
-    if ((rc = B.alloc(&p, tri * sizeof(double), tri_names[k]))) return rc;
+    if ((rc = B.alloc(&p, tri * sizeof(double), kPfTableNames[k]))) return rc;
     d_tri[k] = (double *)p;
   }
   if ((rc = B.alloc(&p, n_f64 * sizeof(double), "results, scale powers, hairpin weights, q5, q3, partial sums"))) return rc;
@@ -1749,10 +1769,7 @@ int pf_long_rows(const LongRows &R, const int32_t *hint, int s0, int n, Launch &
     pow_off[k] = 2 * (a_L + 2 * (size_t)k);
     F.sc = d_f64 + o_pow + pow_off[k];
     F.mlbs = F.sc + (size_t)L + 2;
-    F.qb = d_tri[0] + a_tri; F.qbt = d_tri[1] + a_tri; F.qm = d_tri[2] + a_tri; F.qmt = d_tri[3] + a_tri;
-    F.qm1t = d_tri[4] + a_tri; F.ob = d_tri[5] + a_tri; F.a1 = d_tri[6] + a_tri;
-    F.a0 = F.qbt;   // (dead after q5)
-    F.wt = F.qm1t;  // (dead after the inside pass)
+    pfl_bind_tables(F, d_tri, a_tri);
     F.q5 = d_f64 + o_q5 + a_L + 2 * (size_t)k;
     F.q3 = d_f64 + o_q3 + a_L + 3 * (size_t)k;
     F.part = d_f64 + o_part + a_part;
@@ -1882,16 +1899,9 @@ struct PflSingleLaunch {
     return SF_OK;
   }
   int mark(const uint8_t *) { return SF_OK; }
-  void diagonal(void (*kernel)(SfPfLong, int, int, const SfDevParams *, const SfDevParamsPF *), int d) {
-    const int threads = 256;
-    const size_t cells = (size_t)(F.L - d);
-    const int G = pfl_group(cells, d, lanes);
-    const size_t total = std::min(cells * (size_t)G, lanes);
-    SF_LAUNCH(kernel, (int)((total + threads - 1) / threads), threads, 0, g.stream, F, d, G, D, X);
-  }
-  void inside(int, int d) { diagonal(sf_pflong_inside_kernel, d); }
+  void inside(int, int d) { pfl_launch_diagonal(sf_pflong_inside_kernel, F, d, lanes); }
   void exterior() { SF_LAUNCH(sf_pflong_exterior_kernel, 1, 64, 0, g.stream, F, D, X); }
-  void outside(int, int d) { diagonal(sf_pflong_outside_kernel, d); }
+  void outside(int, int d) { pfl_launch_diagonal(sf_pflong_outside_kernel, F, d, lanes); }
   void prob() { SF_LAUNCH(sf_pflong_prob_kernel, prob_waves, 64, 0, g.stream, F); }
   void finish() { SF_LAUNCH(sf_pflong_finish_kernel, 1, 64, 0, g.stream, F, prob_waves); }
 };
@@ -1990,9 +2000,8 @@ int sf_pf_banded(const uint8_t *seq, int L, const char *cons, const int32_t *mfe
   Bf.who = "sf_pf_banded";
   void *p;
   double *d_tab[SF_PFBAND_NTAB];
-  static const char *const tab_names[SF_PFBAND_NTAB] = {"qb", "qb by columns / A0", "qm", "qm by columns", "qm1 / w", "ob", "A1"};
   for (int k = 0; k < SF_PFBAND_NTAB; k++) {
-    if ((rc = Bf.alloc(&p, nL * nB * sizeof(double), tab_names[k]))) return rc;
+    if ((rc = Bf.alloc(&p, nL * nB * sizeof(double), kPfTableNames[k]))) return rc;
     d_tab[k] = (double *)p;
   }
   if ((rc = Bf.alloc(&p, n_f64 * sizeof(double), "results, scale powers, hairpin weights, q5, q3, partial sums"))) return rc;
@@ -2004,9 +2013,7 @@ int sf_pf_banded(const uint8_t *seq, int L, const char *cons, const int32_t *mfe
   uint8_t *d_u8 = (uint8_t *)p;
   F.S = d_u8;
   F.cen = (char *)d_u8 + nL + 2;
-  F.qb = d_tab[0]; F.qbt = d_tab[1]; F.qm = d_tab[2]; F.qmt = d_tab[3]; F.qm1t = d_tab[4]; F.ob = d_tab[5]; F.a1 = d_tab[6];
-  F.a0 = F.qbt;   // (dead after q5)
-  F.wt = F.qm1t;  // (dead after the inside pass)
+  pfl_bind_tables(F, d_tab, 0);
   F.out = d_f64 + o_out;
   F.sc = d_f64 + o_pow;
   F.mlbs = F.sc + nB + 2;
@@ -2021,13 +2028,6 @@ int sf_pf_banded(const uint8_t *seq, int L, const char *cons, const int32_t *mfe
 
   const SfDevParams *D = (const SfDevParams *)g.dP;
   const SfDevParamsPF *X = (const SfDevParamsPF *)g.dX;
-  auto diagonal = [&](void (*kernel)(SfPfBand, int, int, const SfDevParams *, const SfDevParamsPF *), int d) {
-    const int threads = 256;
-    const size_t cells = (size_t)(L - d);
-    const int G = pfl_group(cells, d, lanes);
-    const size_t total = std::min(cells * (size_t)G, lanes);
-    SF_LAUNCH(kernel, (int)((total + threads - 1) / threads), threads, 0, g.stream, F, d, G, D, X);
-  };
   // (a band of at most TURN + 1 diagonals holds no pair: Z = 1 whatever the scale, and scale 1 gives it exactly)
   double lns = B <= SFD_TURN + 1 ? 0.0 : pfl_first_lns(mfe_dcal_hint, kT, L), ms_in = 0, ms_out = 0, dG = 0;
   int attempts = 0, launches = 0;
@@ -2050,7 +2050,7 @@ int sf_pf_banded(const uint8_t *seq, int L, const char *cons, const int32_t *mfe
     pfl_scale_powers(lns, ln_mlbase, B, hpow.data(), hpow.data() + nB + 2);
     HIPCHK(hipMemcpyAsync(d_f64 + o_pow, hpow.data(), hpow.size() * sizeof(double), hipMemcpyHostToDevice, g.stream));
     HIPCHK(hipEventRecord(Bf.ev[0], g.stream));
-    for (int d = 0; d < B; d++) diagonal(sf_pfband_inside_kernel, d);
+    for (int d = 0; d < B; d++) pfl_launch_diagonal(sf_pfband_inside_kernel, F, d, lanes);
     HIPCHK(hipGetLastError());
     SF_LAUNCH(sf_pfband_exterior_kernel, 2, 64, 0, g.stream, F, D, X);
     HIPCHK(hipGetLastError());
@@ -2073,7 +2073,7 @@ int sf_pf_banded(const uint8_t *seq, int L, const char *cons, const int32_t *mfe
     }
     HIPCHK(hipMemsetAsync(F.cen, '.', nL + 1, g.stream));
     HIPCHK(hipEventRecord(Bf.ev[2], g.stream));
-    for (int d = B - 1; d >= SFD_TURN + 1; d--) diagonal(sf_pfband_outside_kernel, d);
+    for (int d = B - 1; d >= SFD_TURN + 1; d--) pfl_launch_diagonal(sf_pfband_outside_kernel, F, d, lanes);
     HIPCHK(hipGetLastError());
     SF_LAUNCH(sf_pfband_prob_kernel, prob_waves, 64, 0, g.stream, F);
     SF_LAUNCH(sf_pfband_finish_kernel, 1, 64, 0, g.stream, F, prob_waves);

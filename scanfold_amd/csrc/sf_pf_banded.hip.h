@@ -9,9 +9,12 @@
 // j - k <= S - 1 and qm[k+1][i-1]; A0[i][j] reads A0[i-1][j] (0 on diagonal B) and w(i-1, j); ob's sum over l ends at
 // l = i - 1 + max_pair_dist and reads A1[i][l], A0[i][l], qm[j+1][l-1]; interior loops read qb inside (i, j) and ob[k][l]
 // around it, which is 0 outside the band (the (u1, u2) loop is clipped to l - k < B); q5 / q3 read qb only.  So B diagonals
-// of each table give the sums of sf_pf_long.hip.h's triangles: the recurrences, the energy helpers and the lane-group scheme
-// (pfl_group, sfpl_group_sum) are the same, every loop clipped to the band.  Only sums are taken in another order, so the
-// two agree to rounding, not bit for bit.
+// of each table give the sums of sf_pf_long.hip.h's triangles.  The inside, probability and finishing passes are the
+// templates of sf_pf_cells.hip.h which sf_pf_long.hip.h instantiates too: one body, which sees the band through the
+// overloads below.  The outside pass is this file's own (sfpb_outside: sf_pf_long.hip.h's recurrences and lane-group scheme,
+// every loop clipped to the band; one body for both cost the triangle's kernel time, profiles/pf_cells_shared).  Every sum
+// has sf_pf_long.hip.h's order; the exterior loop and the place of Z_s differ (Two scales, below), so the two agree to
+// rounding, not bit for bit.
 //
 // Layout (FP64, 64-bit offsets; a band table holds L * B entries, the cells 0 <= j - i <= B - 1; R = row-banded, row i holds
 // j = i .. i+B-1 at (i-1) B + (j-i); C = column-banded, column j holds i = j-B+1 .. j at (j-1) B + (i-j+B-1): SfBand's).
@@ -49,7 +52,7 @@
 // Device memory of one call: SF_PF_BANDED_BYTES(L, B) = 56 L B + 35 L + 24 B + 65 677 bytes (include/scanfold_hip_long.h).
 #pragma once
 #include "sf_mfe_banded.hip.h"
-#include "sf_pf_long.hip.h"
+#include "sf_pf_cells.hip.h"
 
 #define SF_PFBAND_NTAB 7
 #define SF_PFBAND_MAX_WAVES 4096  // waves of the probability pass at most: the partial sums are a fixed 64 KiB
@@ -68,114 +71,23 @@ struct SfPfBand {
   char *cen;
 };
 
-// sfpl_type / sfpl_hairpin / sfpl_ext of sf_pf_long.hip.h over SfPfBand (int32 bracket partners)
-__device__ __forceinline__ int sfpb_type(const SfDevParams *D, const SfPfBand &F, int a, int b) {
+// the layout and the place of Z_s as sf_pf_cells.hip.h's templates see them
+__device__ __forceinline__ int sfp_type(const SfDevParams *D, const SfPfBand &F, int a, int b) {
   const bool ok = b - a <= D->max_pair_dist;
   return sf_hc_type_of(F.hc, ok ? D->pair[F.S[a]][F.S[b]] : 0, a, b, ok);
 }
-__device__ __forceinline__ double sfpb_hairpin(const SfDevParams *D, const SfDevParamsPF *X, const SfPfBand &F, int i, int j,
-                                               int type) {
-  const int size = j - i - 1;
-  if (size <= SF_MAX_W + 1) return sfx_hairpin(D, X, F.S, i, j, type);
-  return F.hpx[size] * X->mismatchH[type][F.S[i + 1]][F.S[j - 1]];  // (no special hairpin is that long)
+__device__ __forceinline__ size_t sfp_row(const SfPfBand &F, int i, int j) { return sfb_row(F.B, i, j); }
+__device__ __forceinline__ size_t sfp_col(const SfPfBand &F, int j, int i) { return sfb_col(F.B, j, i); }
+// (p[i - 1] is in the table for i = max(1, j-B+1) .. j)
+__device__ __forceinline__ const double *sfp_colp(const SfPfBand &F, const double *t, int j) {
+  return t + ((long long)(j - 1) * F.B + (F.B - j));
 }
-__device__ __forceinline__ double sfpb_ext(const SfDevParamsPF *X, const SfPfBand &F, int type, int i, int j) {
-  return sfx_extloop(X, type, i > 1 ? F.S[i - 1] : -1, j < F.L ? F.S[j + 1] : -1);
-}
-// p[i] = (column-banded table)[i][j] for i = max(1, j-B+1) .. j
-__device__ __forceinline__ const double *sfpb_colp(const double *t, int B, int j) {
-  return t + ((long long)(j - 1) * B + (B - 1 - j));
-}
+__device__ __forceinline__ int sfp_xhi(const SfPfBand &F, int i) { return sfd_min(F.L - i, F.B - 1); }
+__device__ __forceinline__ double sfp_z(const SfPfBand &) { return 1.0; }  // (ob is divided by Z_s already; x / 1.0 is x)
 
-// Diagonal d < B of the inside pass.  Lane r = gt % G of group gt / G; a group takes cells group, group + ngroups, ...
-__device__ __forceinline__ void sfpb_inside(const SfPfBand &F, int d, int G, size_t gt, size_t nl, const SfDevParams *__restrict__ D,
-                                            const SfDevParamsPF *__restrict__ X) {
-  const int L = F.L, B = F.B;
-  const int r = (int)(gt % (size_t)G);
-  const size_t group = gt / (size_t)G, ngroups = nl / (size_t)G;
-  const size_t ncell = (size_t)(L - d);
-  const size_t rounds = (ncell + ngroups - 1) / ngroups;  // the same for every lane: the butterflies stay convergent
-  for (size_t it = 0; it < rounds; it++) {
-    const size_t cell = group + it * ngroups;
-    const bool valid = cell < ncell;
-    const int i = (int)cell + 1, j = i + d;
-    if (d < SFD_TURN + 1) {  // no pair and no multiloop this short (the same for every thread of the launch)
-      if (valid && r == 0) {
-        const size_t ro = sfb_row(B, i, j), co = sfb_col(B, j, i);
-        F.qb[ro] = 0.0; F.qbt[co] = 0.0; F.qm[ro] = 0.0; F.qmt[co] = 0.0; F.qm1t[co] = 0.0;
-      }
-      continue;
-    }
-    double z = 0.0, ml = 0.0, m = 0.0;
-    int type = 0;
-    if (valid) {
-      type = sfpb_type(D, F, i, j);
-      if (type) {
-        if (r == 0) z = sfpb_hairpin(D, X, F, i, j, type) * F.sc[d + 1];
-        const int umax = sfd_min(SFD_MAXLOOP, d - 2 - (SFD_TURN + 1));
-        const int si1 = F.S[i + 1], sj1 = F.S[j - 1];
-        for (int u1 = 0; u1 <= umax; u1++) {
-          const int p = i + 1 + u1;
-          const double *row = F.qb + sfb_row(B, p, p);  // row[q - p] = qb[p][q]
-          for (int u2 = r; u2 <= umax - u1; u2 += G) {
-            const int q = j - 1 - u2;
-            const double v = row[q - p];
-            if (v == 0.0) continue;
-            const int t2 = sfpb_type(D, F, p, q);
-            if (!t2) continue;
-            z += sfx_intloop(X, u1, u2, type, sfd_rtype(t2), si1, sj1, F.S[p - 1], F.S[q + 1]) * v * F.sc[u1 + u2 + 2];
-          }
-        }
-        // multiloop closed by (i, j): sum_u qm[i+1][u-1] qm1[u][j-1], u = i+2+TURN .. j-TURN-2
-        const int n = j - SFD_TURN - 2 - (i + 2 + SFD_TURN) + 1;
-        if (n > 0) {
-          const double *aa = F.qm + sfb_row(B, i + 1, i + 1) + SFD_TURN;         // aa[x] = qm[i+1][u-1], u = i+2+TURN+x
-          const double *bb = sfpb_colp(F.qm1t, B, j - 1) + (i + 2 + SFD_TURN);  // bb[x] = qm1[u][j-1]
-          double s1 = 0.0;
-          int x = r;
-          for (; x + G < n; x += 2 * G) {
-            ml += aa[x] * bb[x];
-            s1 += aa[x + G] * bb[x + G];
-          }
-          if (x < n) ml += aa[x] * bb[x];
-          ml += s1;
-        }
-      }
-      {
-        // qm[i][j] = qm1[i][j] + sum_u (MLbase^(u-i) + qm[i][u-1]) qm1[u][j], u = i+1 .. j-TURN-1
-        const double *a = F.qm + sfb_row(B, i, i);               // a[x] = qm[i][i+x]; term x (u = i+1+x) reads a[x]
-        const double *b = sfpb_colp(F.qm1t, B, j) + (i + 1);     // b[x] = qm1[i+1+x][j]
-        const double *pw = F.mlbs + 1;                           // pw[x] = (MLbase/s)^(x+1)
-        const int n = j - SFD_TURN - 1 - (i + 1) + 1;
-        double s1 = 0.0;
-        int x = r;
-        for (; x + G < n; x += 2 * G) {
-          m += (pw[x] + a[x]) * b[x];
-          s1 += (pw[x + G] + a[x + G]) * b[x + G];
-        }
-        if (x < n) m += (pw[x] + a[x]) * b[x];
-        m += s1;
-      }
-    }
-    // (one butterfly for the pair's weight: the multiloop factor is the cell's, the same in every lane)
-    if (type) z += ml * (X->MLclosing * sfx_mlstem(X, sfd_rtype(type), F.S[j - 1], F.S[i + 1]) * F.sc[2]);
-    z = sfpl_group_sum(z, G);
-    m = sfpl_group_sum(m, G);
-    if (valid && r == 0) {
-      const size_t ro = sfb_row(B, i, j), co = sfb_col(B, j, i);
-      const double qbij = type ? z : 0.0;
-      double m1 = F.qm1t[sfb_col(B, j - 1, i)] * X->MLbase * F.sc[1];
-      if (type) m1 += qbij * sfx_mlstem(X, type, i > 1 ? F.S[i - 1] : -1, j < L ? F.S[j + 1] : -1);
-      const double qmij = m1 + m;
-      F.qb[ro] = qbij; F.qbt[co] = qbij;
-      F.qm1t[co] = m1;
-      F.qm[ro] = qmij; F.qmt[co] = qmij;
-    }
-  }
-}
 __global__ void sf_pfband_inside_kernel(SfPfBand F, int d, int G, const SfDevParams *__restrict__ D,
                                         const SfDevParamsPF *__restrict__ X) {
-  sfpb_inside(F, d, G, (size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x, D, X);
+  sfp_inside(F, d, G, (size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x, D, X);
 }
 
 // Workgroup 0: q5[j] = q5[j-1] / s + sum_i q5[i-1] qb[i][j] ext(i, j), i >= j-B+1, and out[0] = ln Z_s.  Workgroup 1: q3
@@ -188,13 +100,13 @@ __global__ void sf_pfband_exterior_kernel(SfPfBand F, const SfDevParams *__restr
     __syncthreads();
     for (int j = 1; j <= L; j++) {
       double v = 0.0;
-      const double *cj = sfpb_colp(F.qbt, B, j);  // cj[i] = qb[i][j]
+      const double *cj = sfp_colp(F, F.qbt, j);  // cj[i - 1] = qb[i][j]
       const int lo = j - B + 1 > 1 ? j - B + 1 : 1, eref = F.e5[j - 1];
       for (int i = lo + tid; i + SFD_TURN + 1 <= j; i += nt) {
-        const double q = cj[i];
+        const double q = cj[i - 1];
         if (q == 0.0) continue;
-        const int type = sfpb_type(D, F, i, j);
-        if (type) v += ldexp(F.m5[i - 1] * (q * sfpb_ext(X, F, type, i, j)), F.e5[i - 1] - eref);
+        const int type = sfp_type(D, F, i, j);
+        if (type) v += ldexp(F.m5[i - 1] * (q * sfp_ext(X, F, type, i, j)), F.e5[i - 1] - eref);
       }
       v = sfpl_group_sum(v, 64);
       if (tid == 0) {
@@ -215,8 +127,8 @@ __global__ void sf_pfband_exterior_kernel(SfPfBand F, const SfDevParams *__restr
       for (int j = i + SFD_TURN + 1 + tid; j <= hi; j += nt) {
         const double q = ri[j - i];
         if (q == 0.0) continue;
-        const int type = sfpb_type(D, F, i, j);
-        if (type) v += ldexp(F.m3[j + 1] * (q * sfpb_ext(X, F, type, i, j)), F.e3[j + 1] - eref);
+        const int type = sfp_type(D, F, i, j);
+        if (type) v += ldexp(F.m3[j + 1] * (q * sfp_ext(X, F, type, i, j)), F.e3[j + 1] - eref);
       }
       v = sfpl_group_sum(v, 64);
       if (tid == 0) {
@@ -227,6 +139,13 @@ __global__ void sf_pfband_exterior_kernel(SfPfBand F, const SfDevParams *__restr
       __syncthreads();
     }
   }
+}
+
+// p[i] = (column-banded table)[i][j] for i = max(1, j-B+1) .. j: sfp_colp(F, t, j) - 1.  Kept beside sfp_colp because the
+// outside kernel written with sfp_colp(...) + (klo - 1) compiled to other address arithmetic and took 2 % longer
+// (profiles/pf_cells_shared)
+__device__ __forceinline__ const double *sfpb_colp(const double *t, int B, int j) {
+  return t + ((long long)(j - 1) * B + (B - 1 - j));
 }
 
 // Diagonal d < B of the outside pass (d descending from B-1 to TURN+1); groups and rounds as in the inside pass.
@@ -261,12 +180,12 @@ __device__ __forceinline__ void sfpb_outside(const SfPfBand &F, int d, int G, si
           a1 += s1;
         }
       }
-      type = sfpb_type(D, F, i, j);
+      type = sfp_type(D, F, i, j);
       qbij = F.qb[sfb_row(B, i, j)];
       if (type && qbij != 0.0) {
         // the exterior seed q5[i-1] q3[j+1] / Z_s, from the three mantissas and exponents
         if (r == 0)
-          o = ldexp(F.m5[i - 1] * F.m3[j + 1] / F.m5[L] * sfpb_ext(X, F, type, i, j), F.e5[i - 1] + F.e3[j + 1] - F.e5[L]);
+          o = ldexp(F.m5[i - 1] * F.m3[j + 1] / F.m5[L] * sfp_ext(X, F, type, i, j), F.e5[i - 1] + F.e3[j + 1] - F.e5[L]);
         if (i > 1 && j < L) {
           const int rt = sfd_rtype(type);
           const int sp1 = F.S[i - 1], sq1 = F.S[j + 1];
@@ -280,7 +199,7 @@ __device__ __forceinline__ void sfpb_outside(const SfPfBand &F, int d, int G, si
               const int l = j + 1 + u2;
               const double v = row[l - kk];
               if (v == 0.0) continue;
-              const int tk = sfpb_type(D, F, kk, l);
+              const int tk = sfp_type(D, F, kk, l);
               if (!tk) continue;
               o += v * sfx_intloop(X, u1, u2, tk, rt, F.S[kk + 1], F.S[l - 1], sp1, sq1) * F.sc[u1 + u2 + 2];
             }
@@ -328,39 +247,7 @@ __global__ void sf_pfband_outside_kernel(SfPfBand F, int d, int G, const SfDevPa
                                          const SfDevParamsPF *__restrict__ X) {
   sfpb_outside(F, d, G, (size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x, D, X);
 }
-
-// p = ob qb over every cell of the band (ob is divided by Z_s already): the centroid's pairs (p > 0.5) and each wave's share
-// of sum p(1-p) and of the centroid distance, into part[2 * wave]; a wave takes rows wave, wave + nwaves, ...
 __global__ void sf_pfband_prob_kernel(SfPfBand F) {
-  const size_t wave = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = ((size_t)gridDim.x * blockDim.x) >> 6;
-  const int L = F.L, B = F.B, lane = threadIdx.x & 63;
-  double mbd = 0.0, cd = 0.0;
-  for (size_t i = wave + 1; i <= (size_t)L; i += nwaves) {
-    const double *po = F.ob + sfb_row(B, (int)i, (int)i), *pq = F.qb + sfb_row(B, (int)i, (int)i);
-    const int xhi = L - (int)i < B - 1 ? L - (int)i : B - 1;
-    for (int x = SFD_TURN + 1 + lane; x <= xhi; x += 64) {
-      const double q = pq[x];
-      if (q == 0.0) continue;
-      const double p = po[x] * q;
-      mbd += p * (1.0 - p);
-      if (p > 0.5) {
-        cd += 1.0 - p;
-        F.cen[i - 1] = '(';
-        F.cen[i - 1 + x] = ')';
-      } else cd += p;
-    }
-  }
-  mbd = sfpl_group_sum(mbd, 64);
-  cd = sfpl_group_sum(cd, 64);
-  if (lane == 0) { F.part[2 * wave] = mbd; F.part[2 * wave + 1] = cd; }
+  sfp_prob(F, ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, ((size_t)gridDim.x * blockDim.x) >> 6);
 }
-
-// The partial sums in wave order; one wave.
-__global__ void sf_pfband_finish_kernel(SfPfBand F, int nwaves) {
-  const int tid = threadIdx.x;
-  double mbd = 0.0, cd = 0.0;
-  for (int w = tid; w < nwaves; w += 64) { mbd += F.part[2 * w]; cd += F.part[2 * w + 1]; }
-  mbd = sfpl_group_sum(mbd, 64);
-  cd = sfpl_group_sum(cd, 64);
-  if (tid == 0) { F.out[1] = 2.0 * mbd; F.out[2] = cd; }
-}
+__global__ void sf_pfband_finish_kernel(SfPfBand F, int nwaves) { sfp_finish(F, nwaves); }

@@ -3,7 +3,9 @@
 // distance and mean base-pair distance (ensemble diversity).  sf_pf.hip.h stops at SF_MAX_W = 400 (one workgroup per fold).
 //
 // Recurrences: those in the header of sf_pf.hip.h (qb / qm1 / qm, q5 / q3, the outside pass through w, A0, A1 in O(L^3)),
-// FP64 throughout, pair admissibility from sf_hc_type with the resident max_bp_span.  Only sums are taken in another order
+// FP64 throughout, pair admissibility from sf_hc_type with the resident max_bp_span.  The inside, probability and finishing
+// passes are the templates of sf_pf_cells.hip.h, which the banded partition function instantiates too; this file has the
+// state, the layout as those templates see it, the exterior loop, the outside pass and the kernels.  Only sums are taken in another order
 // (a cell's terms are spread over a group of lanes), so results agree with the window kernels to rounding, not bit for bit.
 //
 // Scaling.  ln Z grows by ~0.5 per nucleotide (1.5 for G/C-only sequences), so a whole record never fits FP64 unscaled and
@@ -20,7 +22,7 @@
 // Launches.  One launch per anti-diagonal d = j - i, ascending for the inside pass and descending for the outside pass: all
 // ordering between workgroups comes from kernel boundaries (no grid barrier, no floating-point atomics).  A cell is handled
 // by a group of G lanes (a power of two <= 64) which take its terms round-robin and add their partial sums in a butterfly of
-// __shfl_xor.  pfl_group below (host and device: sf_pf_long_batch.hip.h calls it per row) sizes G so that cells * G fills the lane budget of the device (SF_PFLONG_LANES_PER_CU per compute unit: a
+// __shfl_xor.  pfl_group of sf_pf_cells.hip.h (host and device: sf_pf_long_batch.hip.h calls it per row) sizes G so that cells * G fills the lane budget of the device (SF_PFLONG_LANES_PER_CU per compute unit: a
 // compile-time figure, smaller in the CPU emulation build of the tests, which pays per lane) and lets a group walk several cells where the diagonal has more
 // cells than the budget has groups.  G is a function of L, d and the device's number of compute units only, so two calls on the same input on
 // the same device add in the same order and return bit-identical doubles.  q5 / q3 are sequential in j / i: one wave each, reducing over the other index.
@@ -42,7 +44,7 @@
 // An allocation that fails returns SF_ERR_HIP with the text in sf_last_hip_error().
 #pragma once
 #include "sf_mfe_long.hip.h"
-#include "sf_pf.hip.h"
+#include "sf_pf_cells.hip.h"
 
 #define SF_PFLONG_NTRI 7
 #ifdef SF_EMUL
@@ -68,129 +70,21 @@ struct SfPfLong {
   char *cen;
 };
 
-__device__ __forceinline__ int sfpl_type(const SfDevParams *D, const SfPfLong &F, int a, int b) {
+// the layout and the place of Z_s as sf_pf_cells.hip.h's templates see them
+__device__ __forceinline__ int sfp_type(const SfDevParams *D, const SfPfLong &F, int a, int b) {
   const bool ok = b - a <= D->max_pair_dist;
   return sf_hc_type(F.hc, ok ? D->pair[F.S[a]][F.S[b]] : 0, a, b, ok);
 }
-__device__ __forceinline__ double sfpl_hairpin(const SfDevParams *D, const SfDevParamsPF *X, const SfPfLong &F, int i, int j,
-                                               int type) {
-  const int size = j - i - 1;
-  if (size <= SF_MAX_W + 1) return sfx_hairpin(D, X, F.S, i, j, type);
-  return F.hpx[size] * X->mismatchH[type][F.S[i + 1]][F.S[j - 1]];  // (no special hairpin is that long)
-}
-__device__ __forceinline__ double sfpl_ext(const SfDevParamsPF *X, const SfPfLong &F, int type, int i, int j) {
-  return sfx_extloop(X, type, i > 1 ? F.S[i - 1] : -1, j < F.L ? F.S[j + 1] : -1);
-}
-// sum over the G lanes of a cell's group (every lane of the wave takes part)
-__device__ __forceinline__ double sfpl_group_sum(double v, int G) {
-  for (int m = G >> 1; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-  return v;
-}
+__device__ __forceinline__ size_t sfp_row(const SfPfLong &F, int i, int j) { return sfl_row(F.L, i, j); }
+__device__ __forceinline__ size_t sfp_col(const SfPfLong &, int j, int i) { return sfl_col(j, i); }
+__device__ __forceinline__ const double *sfp_colp(const SfPfLong &, const double *t, int j) { return t + sfl_col(j, 1); }
+__device__ __forceinline__ int sfp_xhi(const SfPfLong &F, int i) { return F.L - i; }
+__device__ __forceinline__ double sfp_z(const SfPfLong &F) { return F.q5[F.L]; }
 
-// lanes per cell of a diagonal with `cells` cells whose longest sum has `terms` terms: fill the lane budget, at most one wave,
-// and no more lanes than leave each some sixteen terms (four lanes for the interior loops of a short diagonal).  The host
-// (sf_pf_long) and the batched kernels (sf_pf_long_batch.hip.h) both size a group with this one function.
-__host__ __device__ inline int pfl_group(size_t cells, int terms, size_t lanes) {
-  int G = 1;
-  while (G < 64 && (size_t)(2 * G) * cells <= lanes && 32 * G <= (terms > 64 ? terms : 64)) G *= 2;
-  return G;
-}
-// waves of the probability pass of a sequence of L nt under a budget of `lanes` lanes: one per row of the triangle at most
-__host__ __device__ inline int pfl_prob_waves(int L, size_t lanes) {
-  return (size_t)L < lanes / 64 ? L : (int)(lanes / 64);
-}
-
-// The five passes below are functions of (F, the lane's position gt within its sequence's share of the launch, the share's
-// size nl): the kernels of this file give a sequence the whole launch, those of sf_pf_long_batch.hip.h a run of workgroups.
-
-// Diagonal d of the inside pass.  Lane r = gt % G of group gt / G; a group takes cells group, group + ngroups, ...
-__device__ __forceinline__ void sfpl_inside(const SfPfLong &F, int d, int G, size_t gt, size_t nl, const SfDevParams *__restrict__ D,
-                                            const SfDevParamsPF *__restrict__ X) {
-  const int L = F.L;
-  const int r = (int)(gt % (size_t)G);
-  const size_t group = gt / (size_t)G, ngroups = nl / (size_t)G;
-  const size_t ncell = (size_t)(L - d);
-  const size_t rounds = (ncell + ngroups - 1) / ngroups;  // the same for every lane: the butterflies stay convergent
-  for (size_t it = 0; it < rounds; it++) {
-    const size_t cell = group + it * ngroups;
-    const bool valid = cell < ncell;
-    const int i = (int)cell + 1, j = i + d;
-    if (d < SFD_TURN + 1) {  // no pair and no multiloop this short (the same for every thread of the launch)
-      if (valid && r == 0) {
-        const size_t ro = sfl_row(L, i, j), co = sfl_col(j, i);
-        F.qb[ro] = 0.0; F.qbt[co] = 0.0; F.qm[ro] = 0.0; F.qmt[co] = 0.0; F.qm1t[co] = 0.0;
-      }
-      continue;
-    }
-    double z = 0.0, ml = 0.0, m = 0.0;
-    int type = 0;
-    if (valid) {
-      type = sfpl_type(D, F, i, j);
-      if (type) {
-        if (r == 0) z = sfpl_hairpin(D, X, F, i, j, type) * F.sc[d + 1];
-        const int umax = sfd_min(SFD_MAXLOOP, d - 2 - (SFD_TURN + 1));
-        const int si1 = F.S[i + 1], sj1 = F.S[j - 1];
-        for (int u1 = 0; u1 <= umax; u1++) {
-          const int p = i + 1 + u1;
-          const double *row = F.qb + sfl_row(L, p, p);  // row[q - p] = qb[p][q]
-          for (int u2 = r; u2 <= umax - u1; u2 += G) {
-            const int q = j - 1 - u2;
-            const double v = row[q - p];
-            if (v == 0.0) continue;
-            const int t2 = sfpl_type(D, F, p, q);
-            if (!t2) continue;
-            z += sfx_intloop(X, u1, u2, type, sfd_rtype(t2), si1, sj1, F.S[p - 1], F.S[q + 1]) * v * F.sc[u1 + u2 + 2];
-          }
-        }
-        // multiloop closed by (i, j): sum_u qm[i+1][u-1] qm1[u][j-1], u = i+2+TURN .. j-TURN-2
-        const double *a = F.qm + sfl_row(L, i + 1, i + 1);  // a[x] = qm[i+1][i+1+x]
-        const double *b = F.qm1t + sfl_col(j - 1, 1);       // b[x] = qm1[x+1][j-1]
-        const int n = j - SFD_TURN - 2 - (i + 2 + SFD_TURN) + 1;
-        const double *aa = a + SFD_TURN, *bb = b + i + 1 + SFD_TURN;  // term x: u = i+2+TURN+x
-        double s1 = 0.0;
-        int x = r;
-        for (; x + G < n; x += 2 * G) {
-          ml += aa[x] * bb[x];
-          s1 += aa[x + G] * bb[x + G];
-        }
-        if (x < n) ml += aa[x] * bb[x];
-        ml += s1;
-      }
-      {
-        // qm[i][j] = qm1[i][j] + sum_u (MLbase^(u-i) + qm[i][u-1]) qm1[u][j], u = i+1 .. j-TURN-1
-        const double *a = F.qm + sfl_row(L, i, i);   // a[x] = qm[i][i+x]; term x (u = i+1+x) reads a[x]
-        const double *b = F.qm1t + sfl_col(j, 1) + i;  // b[x] = qm1[i+1+x][j]
-        const double *pw = F.mlbs + 1;                 // pw[x] = (MLbase/s)^(x+1)
-        const int n = j - SFD_TURN - 1 - (i + 1) + 1;
-        double s1 = 0.0;
-        int x = r;
-        for (; x + G < n; x += 2 * G) {
-          m += (pw[x] + a[x]) * b[x];
-          s1 += (pw[x + G] + a[x + G]) * b[x + G];
-        }
-        if (x < n) m += (pw[x] + a[x]) * b[x];
-        m += s1;
-      }
-    }
-    // (one butterfly for the pair's weight: the multiloop factor is the cell's, the same in every lane)
-    if (type) z += ml * (X->MLclosing * sfx_mlstem(X, sfd_rtype(type), F.S[j - 1], F.S[i + 1]) * F.sc[2]);
-    z = sfpl_group_sum(z, G);
-    m = sfpl_group_sum(m, G);
-    if (valid && r == 0) {
-      const size_t ro = sfl_row(L, i, j), co = sfl_col(j, i);
-      const double qbij = type ? z : 0.0;
-      double m1 = F.qm1t[sfl_col(j - 1, i)] * X->MLbase * F.sc[1];
-      if (type) m1 += qbij * sfx_mlstem(X, type, i > 1 ? F.S[i - 1] : -1, j < L ? F.S[j + 1] : -1);
-      const double qmij = m1 + m;
-      F.qb[ro] = qbij; F.qbt[co] = qbij;
-      F.qm1t[co] = m1;
-      F.qm[ro] = qmij; F.qmt[co] = qmij;
-    }
-  }
-}
+// The kernels of this file give the sequence the whole launch (those of sf_pf_long_batch.hip.h give a row a run of workgroups).
 __global__ void sf_pflong_inside_kernel(SfPfLong F, int d, int G, const SfDevParams *__restrict__ D,
                                      const SfDevParamsPF *__restrict__ X) {
-  sfpl_inside(F, d, G, (size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x, D, X);
+  sfp_inside(F, d, G, (size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x, D, X);
 }
 
 // q5[j] = q5[j-1] / s + sum_i q5[i-1] qb[i][j] ext(i, j), then q3 mirrored; one wave, which reads column j (row i) of qb
@@ -206,8 +100,8 @@ __device__ __forceinline__ void sfpl_exterior(const SfPfLong &F, const SfDevPara
     for (int i = tid + 1; i + SFD_TURN + 1 <= j; i += nt) {
       const double q = cj[i - 1];
       if (q == 0.0) continue;
-      const int type = sfpl_type(D, F, i, j);
-      if (type) v += F.q5[i - 1] * q * sfpl_ext(X, F, type, i, j);
+      const int type = sfp_type(D, F, i, j);
+      if (type) v += F.q5[i - 1] * q * sfp_ext(X, F, type, i, j);
     }
     v = sfpl_group_sum(v, 64);
     if (tid == 0) F.q5[j] = F.q5[j - 1] * F.sc[1] + v;
@@ -219,8 +113,8 @@ __device__ __forceinline__ void sfpl_exterior(const SfPfLong &F, const SfDevPara
     for (int j = i + SFD_TURN + 1 + tid; j <= L; j += nt) {
       const double q = ri[j - i];
       if (q == 0.0) continue;
-      const int type = sfpl_type(D, F, i, j);
-      if (type) v += q * sfpl_ext(X, F, type, i, j) * F.q3[j + 1];
+      const int type = sfp_type(D, F, i, j);
+      if (type) v += q * sfp_ext(X, F, type, i, j) * F.q3[j + 1];
     }
     v = sfpl_group_sum(v, 64);
     if (tid == 0) F.q3[i] = F.q3[i + 1] * F.sc[1] + v;
@@ -263,10 +157,10 @@ __device__ __forceinline__ void sfpl_outside(const SfPfLong &F, int d, int G, si
         if (x < n) a1 += a[x] * b[x];
         a1 += s1;
       }
-      type = sfpl_type(D, F, i, j);
+      type = sfp_type(D, F, i, j);
       qbij = F.qb[sfl_row(L, i, j)];
       if (type && qbij != 0.0) {
-        if (r == 0) o = F.q5[i - 1] * F.q3[j + 1] * sfpl_ext(X, F, type, i, j);
+        if (r == 0) o = F.q5[i - 1] * F.q3[j + 1] * sfp_ext(X, F, type, i, j);
         if (i > 1 && j < L) {
           const int rt = sfd_rtype(type);
           const int sp1 = F.S[i - 1], sq1 = F.S[j + 1];
@@ -279,7 +173,7 @@ __device__ __forceinline__ void sfpl_outside(const SfPfLong &F, int d, int G, si
               const int l = j + 1 + u2;
               const double v = row[l - kk];
               if (v == 0.0) continue;
-              const int tk = sfpl_type(D, F, kk, l);
+              const int tk = sfp_type(D, F, kk, l);
               if (!tk) continue;
               o += v * sfx_intloop(X, u1, u2, tk, rt, F.S[kk + 1], F.S[l - 1], sp1, sq1) * F.sc[u1 + u2 + 2];
             }
@@ -325,42 +219,7 @@ __global__ void sf_pflong_outside_kernel(SfPfLong F, int d, int G, const SfDevPa
                                       const SfDevParamsPF *__restrict__ X) {
   sfpl_outside(F, d, G, (size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x, D, X);
 }
-
-// p = ob qb / Z_s over every cell: the centroid's pairs (p > 0.5) and each wave's share of sum p(1-p) and of the centroid
-// distance, into part[2 * wave]; a wave takes rows wave, wave + nwaves, ... and reads them contiguously.
-__device__ __forceinline__ void sfpl_prob(const SfPfLong &F, size_t wave, size_t nwaves) {
-  const int L = F.L, lane = threadIdx.x & 63;
-  const double Z = F.q5[L];
-  double mbd = 0.0, cd = 0.0;
-  for (size_t i = wave + 1; i <= (size_t)L; i += nwaves) {
-    const double *po = F.ob + sfl_row(L, (int)i, (int)i), *pq = F.qb + sfl_row(L, (int)i, (int)i);
-    for (int x = SFD_TURN + 1 + lane; x <= L - (int)i; x += 64) {
-      const double q = pq[x];
-      if (q == 0.0) continue;
-      const double p = po[x] * q / Z;
-      mbd += p * (1.0 - p);
-      if (p > 0.5) {
-        cd += 1.0 - p;
-        F.cen[i - 1] = '(';
-        F.cen[i - 1 + x] = ')';
-      } else cd += p;
-    }
-  }
-  mbd = sfpl_group_sum(mbd, 64);
-  cd = sfpl_group_sum(cd, 64);
-  if (lane == 0) { F.part[2 * wave] = mbd; F.part[2 * wave + 1] = cd; }
-}
 __global__ void sf_pflong_prob_kernel(SfPfLong F) {
-  sfpl_prob(F, ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, ((size_t)gridDim.x * blockDim.x) >> 6);
+  sfp_prob(F, ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, ((size_t)gridDim.x * blockDim.x) >> 6);
 }
-
-// The partial sums in wave order; one wave.
-__device__ __forceinline__ void sfpl_finish(const SfPfLong &F, int nwaves) {
-  const int tid = threadIdx.x;
-  double mbd = 0.0, cd = 0.0;
-  for (int w = tid; w < nwaves; w += 64) { mbd += F.part[2 * w]; cd += F.part[2 * w + 1]; }
-  mbd = sfpl_group_sum(mbd, 64);
-  cd = sfpl_group_sum(cd, 64);
-  if (tid == 0) { F.out[1] = 2.0 * mbd; F.out[2] = cd; }
-}
-__global__ void sf_pflong_finish_kernel(SfPfLong F, int nwaves) { sfpl_finish(F, nwaves); }
+__global__ void sf_pflong_finish_kernel(SfPfLong F, int nwaves) { sfp_finish(F, nwaves); }

@@ -6,8 +6,9 @@
 // chunk.  act[s] != 0 marks the rows a launch works on: the rows still waiting for an inside pass in range, then the rows in
 // range for the outside pass.  A workgroup of any other row returns at once.
 //
-// Every pass is sf_pf_long.hip.h's own function (sfpl_inside, sfpl_exterior, sfpl_outside, sfpl_prob, sfpl_finish), and what
-// orders a row's sums is computed here from the row alone, exactly as sf_pf_long computes it:
+// Every pass is the function sf_pf_long.hip.h runs (sfp_inside, sfp_prob, sfp_finish of sf_pf_cells.hip.h over SfPfLong;
+// sfpl_exterior and sfpl_outside), and what orders a row's sums is computed here from the row alone, exactly as sf_pf_long
+// computes it:
 //   * the group size G of diagonal d = pfl_group(L_s - d, d, lanes), lanes = the SINGLE call's budget (n_cu *
 //     SF_PFLONG_LANES_PER_CU), never the batch's, never Lmax's;
 //   * the probability pass's wave count = pfl_prob_waves(L_s, lanes), a wave taking rows wave, wave + nwaves, ... of the
@@ -44,7 +45,7 @@ __global__ void sf_pflongb_inside_kernel(const SfPfLong *__restrict__ Fs, const 
   const int G = pfl_group((size_t)(F.L - d), d, (size_t)lanes);
   const size_t first = (size_t)((int)blockIdx.x - s * bps) * blockDim.x;  // this workgroup's first lane within the row's share
   if (first / (size_t)G >= (size_t)(F.L - d)) return;                     // no cell of this row here (the same for the workgroup)
-  sfpl_inside(F, d, G, first + threadIdx.x, (size_t)bps * blockDim.x, D, X);
+  sfp_inside(F, d, G, first + threadIdx.x, (size_t)bps * blockDim.x, D, X);
 }
 
 __global__ void sf_pflongb_exterior_kernel(const SfPfLong *__restrict__ Fs, const uint8_t *__restrict__ act,
@@ -73,12 +74,12 @@ __global__ void sf_pflongb_prob_kernel(const SfPfLong *__restrict__ Fs, const ui
   const SfPfLong F = Fs[s];
   const size_t nwaves = (size_t)pfl_prob_waves(F.L, (size_t)lanes);
   const size_t wave = (size_t)((int)blockIdx.x - s * bps) * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  if (wave >= nwaves) return;  // (the same for the wave; sfpl_prob has no workgroup barrier)
-  sfpl_prob(F, wave, nwaves);
+  if (wave >= nwaves) return;  // (the same for the wave; sfp_prob has no workgroup barrier)
+  sfp_prob(F, wave, nwaves);
 }
 
 __global__ void sf_pflongb_finish_kernel(const SfPfLong *__restrict__ Fs, const uint8_t *__restrict__ act, int lanes) {
   if (!act[blockIdx.x]) return;
   const SfPfLong F = Fs[blockIdx.x];
-  sfpl_finish(F, pfl_prob_waves(F.L, (size_t)lanes));
+  sfp_finish(F, pfl_prob_waves(F.L, (size_t)lanes));
 }

@@ -62,6 +62,10 @@ def test_span_not_below_the_length(gpu_engine):
     bp.check_span_not_below_length(gpu_engine)
 
 
+def test_span_not_below_the_length_65(gpu_engine):
+    bp.check_span_not_below_length(gpu_engine, 65)
+
+
 def test_hints(gpu_engine):
     bp.check_hints(gpu_engine, 3000, 401)
 

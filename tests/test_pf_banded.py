@@ -48,6 +48,11 @@ def test_span_not_below_the_length(emul):
     bp.check_span_not_below_length(emul)
 
 
+def test_span_not_below_the_length_65(emul):
+    """one nucleotide past a wave's 64: every row and column of the band table is a whole row or column of the triangle"""
+    bp.check_span_not_below_length(emul, 65)
+
+
 def test_hints(emul):
     bp.check_hints(emul, 433, 101)
 
