@@ -12,7 +12,8 @@
  * sequences, constraints and hints side by side (the three ensembles of --global_ensemble; fc.pf() over long fragments),
  * every row bit for bit what sf_pf_long returns for it.  sf_fold_banded is sf_fold_long under a base-pair span in banded
  * tables: memory and work linear in the record's length, records up to SF_MAX_BANDED nucleotides, the same bytes;
- * sf_pf_banded is sf_pf_long under a span in banded tables likewise, to rounding.
+ * sf_pf_banded is sf_pf_long under a span in banded tables likewise, to rounding.  sf_fold_banded_batch is sf_fold_banded
+ * for many sequences side by side (a genome and its shuffles under a span: the z-score of a record of any length).
  * Soft constraints (SHAPE) are not provided past SF_MAX_W.
  */
 #ifndef SCANFOLD_HIP_LONG_H
@@ -85,8 +86,32 @@ int sf_fold_long_batch(const uint8_t *seqs, int n, int ld, const int32_t *len, c
  * was not asked for), and the number of chunks it ran as.  Any pointer may be NULL. */
 int sf_fold_long_batch_times(double *fill_ms, double *f5_ms, double *trace_ms, int *chunks);
 
-/* The byte budget of one chunk of sf_fold_long_batch and of sf_pf_long_batch; 0 restores the default (8 GiB). */
+/* The byte budget of one chunk of sf_fold_long_batch, sf_fold_banded_batch and sf_pf_long_batch; 0 restores the default
+ * (8 GiB). */
 int sf_set_long_batch_bytes(size_t bytes);
+
+/* sf_fold_banded for n sequences at once, under the resident base-pair span S (sf_set_max_bp_span, S >= 1).  seqs, n, ld,
+ * len, cons, mfe_dcal_out, db_out exactly as for sf_fold_long_batch, with 1 <= len[s] <= SF_MAX_BANDED: ragged rows, a
+ * constraint row of '.' only is no constraint, db_out NULL means energies only, no traceback and no memory for it.  Row s
+ * lives in its own band of B_s = min(S, len[s]) diagonals.  Energies and structures are those of sf_fold_banded, byte for
+ * byte, whatever the order of the rows and however the call is chunked (every value is an integer minimum).
+ * One fill launch per diagonal d = 0 .. max B_s - 1 covers every row of a chunk (a row is absent from the launches
+ * d >= B_s); then the exterior loop f5 and the traceback run in one workgroup per row, the rows side by side, where
+ * sf_fold_banded has a single workgroup at work.  A chunk holds as many consecutive rows as fit the byte budget of
+ * sf_set_long_batch_bytes (8 GiB by default), each row counted as SF_BANDED_BYTES(L, B_s), always at least one row, and no
+ * more than keep rows * ceil(64 Lmax / 256) workgroups inside an int; its tables are a fixed number of device allocations
+ * made for the chunk and freed after it, with one hairpin table of max B_s + 1 entries.  The constraints are parsed on the
+ * host (int32 bracket partners).
+ * n == 0: SF_OK.  No span set, n < 0, a length < 1, > SF_MAX_BANDED or > ld, seqs / len / mfe_dcal_out NULL with n > 0:
+ * SF_ERR_BAD_ARG.  Unbalanced brackets in any row: SF_ERR_CONSTRAINT, before anything is launched.  Not enough device
+ * memory: SF_ERR_HIP with the text in sf_last_hip_error().  On any error no output is written. */
+int sf_fold_banded_batch(const uint8_t *seqs, int n, int ld, const int32_t *len, const char *cons, int32_t *mfe_dcal_out,
+                         char *db_out);
+
+/* Of the last successful sf_fold_banded_batch, summed over its chunks: device-event times (ms) of the fill, the exterior
+ * loop f5 and the traceback (0 when it was not asked for), the number of chunks, and the number of fill launches (a
+ * chunk's is its max B_s).  Any pointer may be NULL. */
+int sf_fold_banded_batch_times(double *fill_ms, double *f5_ms, double *trace_ms, int *chunks, int *fill_launches);
 
 /* fc.pf(); fc.centroid(); fc.mean_bp_distance() — RNAfold -p — for one sequence of any length 1..SF_MAX_LONG
  * (ScanFoldFunctions.py:758-772, rna_refold).  seq, cons as for sf_fold_long; the resident parameter set (rescaled

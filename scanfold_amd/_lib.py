@@ -85,6 +85,9 @@ _LONG_EXPORTS = {
                                           ctypes.c_void_p]),
     "sf_fold_long_batch_times": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double)] * 3 + [ctypes.POINTER(ctypes.c_int)]),
     "sf_set_long_batch_bytes": (ctypes.c_int, [ctypes.c_size_t]),
+    "sf_fold_banded_batch": (ctypes.c_int, [_c_u8p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_void_p]),
+    "sf_fold_banded_batch_times": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double)] * 3 + [ctypes.POINTER(ctypes.c_int)] * 2),
     "sf_pf_long": (ctypes.c_int, [_c_u8p, ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                   ctypes.c_void_p, ctypes.c_void_p]),
     "sf_pf_long_times": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
@@ -150,6 +153,7 @@ SF_ERR_DUPLEX_HITS = _header_value("scanfold_hip_duplex.h", "SF_ERR_DUPLEX_HITS"
 _FOLD_LONG = ("sf_fold_long", "whole-record folds")
 _FOLD_BANDED = ("sf_fold_banded", "whole-record folds under a base-pair span in banded tables")
 _FOLD_LONG_BATCH = ("sf_fold_long_batch", "folds of sequences past %d nt" % SF_MAX_W)
+_FOLD_BANDED_BATCH = ("sf_fold_banded_batch", "batched whole-record folds under a base-pair span in banded tables")
 _PF_LONG = ("sf_pf_long", "whole-record partition functions")
 _PF_BANDED = ("sf_pf_banded", "whole-record partition functions under a base-pair span in banded tables")
 _PF_LONG_BATCH = ("sf_pf_long_batch", "partition functions of many sequences past %d nt" % SF_MAX_W)
@@ -430,12 +434,16 @@ class Engine:
         cons: None, or one item per sequence, each a constraint string of the sequence's length or None.  Raises
         ScanFoldHipError on a library without the entry point (there is no fallback)."""
         self._need(*_FOLD_LONG_BATCH)
+        return self._fold_rows(self.lib.sf_fold_long_batch, seqs, cons, structure)
+
+    def _fold_rows(self, entry, seqs, cons, structure):
+        """entry = sf_fold_long_batch or sf_fold_banded_batch -> energies, or (energies, [dot-bracket])"""
         arr, lens, ld, c = _ragged_rows(seqs, cons)
         n = len(lens)
         e = np.zeros(n, dtype=np.int32)
         db = np.zeros((n, ld + 1), dtype=np.uint8) if structure else None
-        self._check(self.lib.sf_fold_long_batch(arr.ctypes.data, n, ld, lens.ctypes.data, None if c is None else c.ctypes.data,
-                                                e.ctypes.data, None if db is None else db.ctypes.data))
+        self._check(entry(arr.ctypes.data, n, ld, lens.ctypes.data, None if c is None else c.ctypes.data,
+                          e.ctypes.data, None if db is None else db.ctypes.data))
         if not structure:
             return e
         return e, [bytes(db[k, :lens[k]]).decode() for k in range(n)]
@@ -449,9 +457,31 @@ class Engine:
         return dict(fill_ms=t[0].value, f5_ms=t[1].value, trace_ms=t[2].value, chunks=ch.value)
 
     def set_long_batch_bytes(self, nbytes):
-        """the device memory one chunk of fold_long_batch may take for its tables; 0 restores the default (8 GiB)"""
+        """the device memory one chunk of fold_long_batch (and of fold_banded_batch and pf_long_batch) may take for its
+        tables; 0 restores the default (8 GiB)"""
         self._need(*_FOLD_LONG_BATCH)
         self._check(self.lib.sf_set_long_batch_bytes(int(nbytes)))
+
+    def has_fold_banded_batch(self):
+        return getattr(self.lib, "sf_fold_banded_batch", None) is not None
+
+    def fold_banded_batch(self, seqs, cons=None, structure=False):
+        """fold_banded for many sequences of 1..SF_MAX_BANDED nt, of any mix of lengths, side by side in the same launches
+        under the resident base-pair span (sf_fold_banded_batch) -> int32 array of energies (dcal/mol), or
+        (energies, [dot-bracket]) with structure=True: every row the bytes fold_banded returns for it.  cons as for
+        fold_long_batch.  Raises ScanFoldHipError where no span is set, and on a library without the entry point (there is no
+        fallback)."""
+        self._need(*_FOLD_BANDED_BATCH)
+        return self._fold_rows(self.lib.sf_fold_banded_batch, seqs, cons, structure)
+
+    def fold_banded_batch_times(self):
+        """-> dict(fill_ms, f5_ms, trace_ms, chunks, fill_launches) of the last fold_banded_batch (device events, summed over
+        its chunks; a chunk's fill launches are the widest band of its rows)."""
+        self._need(*_FOLD_BANDED_BATCH)
+        t = [ctypes.c_double() for _ in range(3)]
+        ch, n = ctypes.c_int(), ctypes.c_int()
+        self._check(self.lib.sf_fold_banded_batch_times(*(ctypes.byref(x) for x in t), ctypes.byref(ch), ctypes.byref(n)))
+        return dict(fill_ms=t[0].value, f5_ms=t[1].value, trace_ms=t[2].value, chunks=ch.value, fill_launches=n.value)
 
     def has_pf_long(self):
         return getattr(self.lib, "sf_pf_long", None) is not None

@@ -22,6 +22,7 @@
 #include "sf_mfe_long.hip.h"
 #include "sf_mfe_long_batch.hip.h"
 #include "sf_mfe_banded.hip.h"
+#include "sf_mfe_banded_batch.hip.h"
 #include "sf_pf.hip.h"
 #include "sf_pf_long.hip.h"
 #include "sf_pf_long_batch.hip.h"
@@ -1123,12 +1124,12 @@ struct LongRows {
   std::vector<char> constrained;  // per row: it has a constraint (made by long_rows_check)
 };
 
-// The argument checks both batch entry points make, and a look at every constraint row before anything is launched: a row of
-// dots is no constraint.
-int long_rows_check(LongRows &R) {
+// The argument checks the batch entry points make (max_len: the longest row the caller takes), and a look at every constraint
+// row before anything is launched: a row of dots is no constraint.
+int long_rows_check(LongRows &R, int max_len) {
   if (R.n < 0 || (R.n > 0 && (!R.seqs || !R.len))) return SF_ERR_BAD_ARG;
   for (int k = 0; k < R.n; k++)
-    if (R.len[k] < 1 || R.len[k] > SF_MAX_LONG || R.len[k] > R.ld) return SF_ERR_BAD_ARG;
+    if (R.len[k] < 1 || R.len[k] > max_len || R.len[k] > R.ld) return SF_ERR_BAD_ARG;
   R.constrained.assign((size_t)R.n, 0);
   if (R.cons)
     for (int k = 0; k < R.n; k++) {
@@ -1147,8 +1148,10 @@ int long_rows_check(LongRows &R) {
 // chunk(s0, m, str) works on rows s0 .. s0 + m - 1 and leaves their strings (structures, centroids) back to back at str,
 // L + 1 bytes each; str is NULL when str_out is.  The strings are staged here (they outlive the chunks' device buffers) and
 // reach str_out, n rows of ld + 1 bytes, only when every chunk has succeeded.
-template <class Chunk>
-int long_for_chunks(const LongRows &R, size_t (*row_bytes)(int), char *str_out, int *chunks, Chunk chunk) {
+// grid_lanes > 0 (rows past SF_MAX_LONG): a chunk's rows times the workgroups of grid_lanes lanes per nucleotide of its
+// longest row stay inside an int, the size of a one-dimensional grid that gives every row that many workgroups.
+template <class RowBytes, class Chunk>
+int long_for_chunks(const LongRows &R, RowBytes row_bytes, char *str_out, int *chunks, Chunk chunk, int grid_lanes = 0) {
   std::vector<char> str;
   if (str_out) {
     size_t total = 0;
@@ -1159,10 +1162,12 @@ int long_for_chunks(const LongRows &R, size_t (*row_bytes)(int), char *str_out, 
   *chunks = 0;
   for (int s0 = 0; s0 < R.n;) {
     size_t bytes = 0, str_bytes = 0;
-    int m = 0;
+    int m = 0, Lmax = 0;
     while (s0 + m < R.n && m < kLongBatchMaxSeqs) {
       const size_t b = row_bytes(R.len[s0 + m]);
       if (m > 0 && bytes + b > g_longb_bytes) break;
+      Lmax = std::max(Lmax, R.len[s0 + m]);
+      if (m > 0 && grid_lanes > 0 && (size_t)(m + 1) * (((size_t)Lmax * grid_lanes + 255) / 256) >= ((size_t)1 << 31)) break;
       bytes += b;
       str_bytes += (size_t)R.len[s0 + m] + 1;
       m++;
@@ -1623,7 +1628,7 @@ int sf_fold_long_batch(const uint8_t *seqs, int n, int ld, const int32_t *len, c
   if (rc) return rc;
   if (n > 0 && !mfe_out) return SF_ERR_BAD_ARG;
   LongRows R = {seqs, n, ld, len, cons, "sf_fold_long_batch"};
-  if ((rc = long_rows_check(R))) return rc;
+  if ((rc = long_rows_check(R, SF_MAX_LONG))) return rc;
   // the energies are staged and handed over, like the structures, only when every chunk has succeeded
   std::vector<int32_t> e_host((size_t)n);
   double ms[3] = {0, 0, 0};
@@ -1649,6 +1654,181 @@ int sf_fold_long_batch_times(double *fill_ms, double *f5_ms, double *trace_ms, i
 
 int sf_set_long_batch_bytes(size_t bytes) {
   g_longb_bytes = bytes ? bytes : kLongBatchBytesDefault;
+  return SF_OK;
+}
+
+}  // extern "C"
+
+// ---------------- many whole-record folds under a span at once (sf_mfe_banded_batch.hip.h) ----------------
+namespace {
+double g_bandb_ms[3] = {0, 0, 0};  // fill, f5, traceback of the last sf_fold_banded_batch, summed over its chunks
+int g_bandb_chunks = 0, g_bandb_launches = 0;
+
+// Sequences s0 .. s0 + n - 1 as one chunk under the span S, each in a band of B_s = min(S, L_s) diagonals.  e_host / db_host
+// as in long_batch_chunk.  The chunk's tables are slices of a fixed number of allocations: c, fML, fMLt (L_s B_s entries a
+// row), the DML rings, one int32 block (hairpin table of max B_s + 1 entries, the constrained rows' bracket partners and
+// enclosing pairs, energies, f5, traceback stacks), one byte block (sequences, the constrained rows' parsed characters,
+// structures) and the states.  *launches grows by the chunk's fill launches, max B_s.
+int band_batch_chunk(const LongRows &R, int S, int s0, int n, int32_t *e_host, char *db_host, double ms_out[3], int *launches) {
+  int rc;
+  const sf_params_blob *P = (const sf_params_blob *)g.slot[g.cur].src.data();  // the resident set as it was handed in
+  const LongPack K = long_pack(R, s0, n);
+  const int Lmax = K.Lmax, Bmax = std::min(S, Lmax);
+  const size_t n_L = K.n_L, n_hc = K.n_hcL + 2 * (size_t)K.n_hc;  // (a constrained row's arrays have L + 2 entries)
+  size_t cells = 0, n_stk = 0;
+  for (int k = 0; k < n; k++) {
+    const int L = R.len[s0 + k];
+    cells += (size_t)L * (size_t)std::min(S, L);
+    n_stk += SF_LONG_STACK_INTS(L);
+  }
+  const bool trace = db_host != nullptr;
+  // slices of the int32 allocation, in elements: what is copied up comes first
+  const size_t o_hp = 0, o_part = o_hp + (size_t)Bmax + 1, o_encl = o_part + n_hc, o_mfe = o_encl + n_hc;
+  const size_t o_f5 = o_mfe + (size_t)n, o_stk = o_f5 + n_L + (size_t)n, n_i32 = o_stk + (trace ? n_stk : 0);
+  // and of the byte block: the sequences (L + 2 each), the parsed constraint characters, the structures
+  const size_t o_c = K.o_src, o_db = o_c + n_hc, n_u8 = o_db + (trace ? n_L + (size_t)n : 0);
+
+  std::vector<int32_t> h32 = long_hairpin_table(P, Bmax);
+  h32.resize(o_mfe, 0);
+  std::vector<uint8_t> h8(K.h8.begin(), K.h8.begin() + (ptrdiff_t)K.o_src);
+  h8.resize(o_db, 0);
+  {  // the constraints, parsed here (int32 positions); long_rows_check has seen that every row balances
+    BandHc H;
+    size_t a = 0;
+    for (int k = 0; k < n; k++) {
+      if (!R.constrained[s0 + k]) continue;
+      const int L = R.len[s0 + k];
+      if ((rc = H.parse(R.cons + (size_t)(s0 + k) * R.ld, L))) return rc;
+      memcpy(h8.data() + o_c + a, H.c.data(), (size_t)L + 2);
+      memcpy(h32.data() + o_part + a, H.part.data(), ((size_t)L + 2) * sizeof(int32_t));
+      memcpy(h32.data() + o_encl + a, H.encl.data(), ((size_t)L + 2) * sizeof(int32_t));
+      a += (size_t)L + 2;
+    }
+  }
+  std::vector<SfBand> hF((size_t)n);
+
+  LongBufs B;
+  B.who = R.who;
+  void *p;
+  int32_t *d_c, *d_fML, *d_fMLt, *d_dml, *d_i32;
+  uint8_t *d_u8;
+  SfBand *d_F;
+  if ((rc = B.alloc(&p, cells * sizeof(int32_t), "c"))) return rc;
+  d_c = (int32_t *)p;
+  if ((rc = B.alloc(&p, cells * sizeof(int32_t), "fML"))) return rc;
+  d_fML = (int32_t *)p;
+  if ((rc = B.alloc(&p, cells * sizeof(int32_t), "fML transposed"))) return rc;
+  d_fMLt = (int32_t *)p;
+  if ((rc = B.alloc(&p, 3 * (n_L + 2 * (size_t)n) * sizeof(int32_t), "DML rings"))) return rc;
+  d_dml = (int32_t *)p;
+  if ((rc = B.alloc(&p, n_i32 * sizeof(int32_t), "hairpin table, bracket partners, energies, f5, traceback stacks"))) return rc;
+  d_i32 = (int32_t *)p;
+  if ((rc = B.alloc(&p, n_u8, "sequences, constraints, structures"))) return rc;
+  d_u8 = (uint8_t *)p;
+  if ((rc = B.alloc(&p, (size_t)n * sizeof(SfBand), "fold states"))) return rc;
+  d_F = (SfBand *)p;
+
+  size_t a_cells = 0, a_L = 0, a_stk = 0, a_hc = 0;
+  for (int k = 0; k < n; k++) {
+    const int L = R.len[s0 + k];
+    SfBand &F = hF[k];
+    memset(&F, 0, sizeof F);
+    F.L = L;
+    F.B = std::min(S, L);
+    F.S = d_u8 + a_L + 2 * (size_t)k;
+    F.hp = d_i32 + o_hp;
+    if (R.constrained[s0 + k]) {
+      F.hc.c = (const char *)d_u8 + o_c + a_hc;
+      F.hc.partner = d_i32 + o_part + a_hc;
+      F.hc.encl = d_i32 + o_encl + a_hc;
+      a_hc += (size_t)L + 2;
+    }
+    F.c = d_c + a_cells;
+    F.fML = d_fML + a_cells;
+    F.fMLt = d_fMLt + a_cells;
+    F.dml = d_dml + 3 * (a_L + 2 * (size_t)k);
+    F.f5 = d_i32 + o_f5 + a_L + (size_t)k;
+    F.status = (int *)g.status.p;
+    if (trace) {
+      F.stk = d_i32 + o_stk + a_stk;
+      F.db = (char *)d_u8 + o_db + a_L + (size_t)k;
+    }
+    a_cells += (size_t)L * (size_t)F.B;
+    a_L += (size_t)L;
+    a_stk += SF_LONG_STACK_INTS(L);
+  }
+  HIPCHK(hipMemcpyAsync(d_i32, h32.data(), h32.size() * sizeof(int32_t), hipMemcpyHostToDevice, g.stream));
+  HIPCHK(hipMemcpyAsync(d_u8, h8.data(), h8.size(), hipMemcpyHostToDevice, g.stream));
+  HIPCHK(hipMemcpyAsync(d_F, hF.data(), (size_t)n * sizeof(SfBand), hipMemcpyHostToDevice, g.stream));
+
+  for (auto &e : B.ev) HIPCHK(hipEventCreate(&e));
+  const SfDevParams *D = (const SfDevParams *)g.dP;
+  const int threads = SF_BANDB_THREADS;
+  std::vector<int> lens(R.len + s0, R.len + s0 + n);
+  std::sort(lens.begin(), lens.end());  // the rows live on diagonal d (d < B_s, that is d < L_s: d < S here) are a suffix
+  size_t live = 0, live_L = n_L;        // rows with L_s > d, and their nucleotides
+  HIPCHK(hipEventRecord(B.ev[0], g.stream));
+  for (int d = 0; d < Bmax; d++) {
+    while (live < (size_t)n && lens[live] <= d) live_L -= (size_t)lens[live++];
+    const int G = band_group(d, live_L - ((size_t)n - live) * (size_t)d);  // the cells of all rows on this diagonal
+    const int bps = (int)(((size_t)(Lmax - d) * (size_t)G + threads - 1) / threads);
+    SF_LAUNCH(sf_bandb_fill_kernel, n * bps, threads, 0, g.stream, (const SfBand *)d_F, d, G, bps, D);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(B.ev[1], g.stream));
+  SF_LAUNCH(sf_bandb_f5_kernel, n, Bmax <= 256 ? 64 : 256, 0, g.stream, (const SfBand *)d_F, D, d_i32 + o_mfe);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(B.ev[2], g.stream));
+  if (trace) {
+    SF_LAUNCH(sf_bandb_trace_kernel, n, threads, 0, g.stream, (const SfBand *)d_F, D);
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipEventRecord(B.ev[3], g.stream));
+  HIPCHK(hipMemcpyAsync(e_host + s0, d_i32 + o_mfe, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, g.stream));
+  if (trace) HIPCHK(hipMemcpyAsync(db_host, d_u8 + o_db, n_L + (size_t)n, hipMemcpyDeviceToHost, g.stream));
+  if ((rc = read_status(g.stream, false))) return rc;
+  for (int k = 0; k < 3; k++) {
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, B.ev[k], B.ev[k + 1]));
+    ms_out[k] += (k == 2 && !trace) ? 0.0 : ms;
+  }
+  *launches += Bmax;
+  return SF_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int sf_fold_banded_batch(const uint8_t *seqs, int n, int ld, const int32_t *len, const char *cons, int32_t *mfe_out, char *db_out) {
+  int rc = check_ready();
+  if (rc) return rc;
+  const int S = g.max_bp_span;
+  if (S < 1 || (n > 0 && !mfe_out)) return SF_ERR_BAD_ARG;
+  LongRows R = {seqs, n, ld, len, cons, "sf_fold_banded_batch"};
+  if ((rc = long_rows_check(R, SF_MAX_BANDED))) return rc;
+  // the energies are staged and handed over, like the structures, only when every chunk has succeeded
+  std::vector<int32_t> e_host((size_t)n);
+  double ms[3] = {0, 0, 0};
+  int chunks, launches = 0;
+  auto row_bytes = [S](int L) { return (size_t)SF_BANDED_BYTES(L, std::min(S, L)); };
+  rc = long_for_chunks(R, row_bytes, db_out, &chunks, [&](int s0, int m, char *db_host) {
+    return band_batch_chunk(R, S, s0, m, e_host.data(), db_host, ms, &launches);
+  }, 64);
+  if (rc) return rc;  // (n == 0: no chunk)
+  if (n) memcpy(mfe_out, e_host.data(), (size_t)n * sizeof(int32_t));
+  for (int k = 0; k < 3; k++) g_bandb_ms[k] = ms[k];
+  g_bandb_chunks = chunks;
+  g_bandb_launches = launches;
+  return SF_OK;
+}
+
+int sf_fold_banded_batch_times(double *fill_ms, double *f5_ms, double *trace_ms, int *chunks, int *fill_launches) {
+  SF_ENTER();
+  if (fill_ms) *fill_ms = g_bandb_ms[0];
+  if (f5_ms) *f5_ms = g_bandb_ms[1];
+  if (trace_ms) *trace_ms = g_bandb_ms[2];
+  if (chunks) *chunks = g_bandb_chunks;
+  if (fill_launches) *fill_launches = g_bandb_launches;
   return SF_OK;
 }
 
@@ -1915,7 +2095,7 @@ int sf_pf_long(const uint8_t *seq, int L, const char *cons, const int32_t *mfe_d
   if (rc) return rc;
   if (!seq || L < 1 || L > SF_MAX_LONG) return SF_ERR_BAD_ARG;
   LongRows R = {seq, 1, L, &L, cons, "sf_pf_long"};
-  if ((rc = long_rows_check(R))) return rc;
+  if ((rc = long_rows_check(R, SF_MAX_LONG))) return rc;
   // the record and the centroid are staged: nothing reaches the caller unless the call succeeds
   sf_pf_long_row row = {};
   std::vector<char> cen((size_t)L + 1);
@@ -2180,7 +2360,7 @@ int sf_pf_long_batch(const uint8_t *seqs, int n, int ld, const int32_t *len, con
   int rc = check_ready();
   if (rc) return rc;
   LongRows R = {seqs, n, ld, len, cons, "sf_pf_long_batch"};
-  if ((rc = long_rows_check(R))) return rc;
+  if ((rc = long_rows_check(R, SF_MAX_LONG))) return rc;
   // the records are staged and handed over, like the centroids, only when every chunk has succeeded
   std::vector<sf_pf_long_row> rows_host((size_t)n);
   double ms[2] = {0, 0};

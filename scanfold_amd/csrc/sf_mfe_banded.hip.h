@@ -61,12 +61,9 @@ __device__ __forceinline__ const int32_t *sft_colp(const SfBand &F, const int32_
 __device__ __forceinline__ int sft_lo(const SfBand &F, int j) { return j - F.B + 1 > 1 ? j - F.B + 1 : 1; }
 __device__ __forceinline__ bool sft_in(const SfBand &F, int i, int j) { return j - i < F.B; }
 
-// Diagonal d of the fill (d < B).  Thread t of the grid is lane t % G of the group of cell i = t / G + 1; every lane of a wave
-// takes part in the butterfly, with or without a cell.
-__global__ void sf_band_fill_kernel(SfBand F, int d, int G, const SfDevParams *__restrict__ D) {
-  const size_t gt = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int r = (int)(gt % (size_t)G);
-  const size_t cell = gt / (size_t)G;
+// Cell i = cell + 1 of diagonal d of the fill (d < B), as lane r of its group of G; every lane of a wave takes part in the
+// butterfly, with or without a cell.  The body of sf_band_fill_kernel and of sf_bandb_fill_kernel (sf_mfe_banded_batch.hip.h).
+__device__ __forceinline__ void sfb_fill_cell(const SfBand &F, int d, int G, int r, size_t cell, const SfDevParams *D) {
   const int L = F.L, B = F.B;
   const bool valid = cell < (size_t)(L - d);
   const int i = (int)cell + 1, j = i + d;
@@ -126,9 +123,15 @@ __global__ void sf_band_fill_kernel(SfBand F, int d, int G, const SfDevParams *_
   }
 }
 
+// Thread t of the grid is lane t % G of the group of cell i = t / G + 1.
+__global__ void sf_band_fill_kernel(SfBand F, int d, int G, const SfDevParams *__restrict__ D) {
+  const size_t gt = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  sfb_fill_cell(F, d, G, (int)(gt % (size_t)G), gt / (size_t)G, D);
+}
+
 // f5[j] = min(f5[j-1], min_i f5[i-1] + c[i][j] + ExtLoop(i, j)), i >= max(1, j-B+1); one workgroup (a single wave when the
 // band is narrow: its barriers cost nothing then), column j of c read contiguously.
-__global__ void sf_band_f5_kernel(SfBand F, const SfDevParams *__restrict__ D, int32_t *mfe_out) {
+__device__ __forceinline__ void sfb_f5(const SfBand &F, const SfDevParams *D, int32_t *mfe_out) {
   __shared__ int red[16];
   const int tid = threadIdx.x, nt = blockDim.x, L = F.L, B = F.B;
   if (tid == 0) F.f5[0] = 0;
@@ -150,4 +153,5 @@ __global__ void sf_band_f5_kernel(SfBand F, const SfDevParams *__restrict__ D, i
   }
   if (tid == 0 && mfe_out) *mfe_out = F.f5[L];
 }
+__global__ void sf_band_f5_kernel(SfBand F, const SfDevParams *__restrict__ D, int32_t *mfe_out) { sfb_f5(F, D, mfe_out); }
 __global__ void sf_band_trace_kernel(SfBand F, const SfDevParams *__restrict__ D) { sft_trace(F, D); }

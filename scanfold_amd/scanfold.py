@@ -17,7 +17,8 @@ wig exports are not reproduced.
 --global_span N (not upstream) runs those three folds under max bp span N in banded tables (sf_fold_banded), and
 --global_ensemble_banded adds their ensembles from the banded partition function (sf_pf_banded), at any record length.
 --global_zscore (not upstream) z-scores the whole record against shuffles of itself (one batched whole-record fold,
-sf_fold_long_batch) into `<that>.global_zscore.txt`.
+sf_fold_long_batch) into `<that>.global_zscore.txt`; --global_zscore_span N (not upstream) does so under max bp span N in
+banded tables (one sf_fold_banded_batch: linear in the record's length, records past 32767 nt).
 --lri replaces the window scan by the k-mer duplex scan (ScanFold.py:391-393,421,769-1034; scanfold_amd.lri): it writes
 `<that>.LRI.out`, reports the number of hits and stops — upstream's continuation into the Fold stage is not runnable in
 general (README.md) and is not reproduced.
@@ -248,7 +249,7 @@ GLOBAL_ZSCORE_HEADER = ("Name\tLength\tTemperature\tRandomizations\tShuffleType\
                         "Z-score\tP-value\n")
 
 
-def global_zscore(seq, name, outname, temperature, randomizations, shuffle_type, seed=0):
+def global_zscore(seq, name, outname, temperature, randomizations, shuffle_type, seed=0, span=0):
     """--global_zscore (not upstream): the z-score of the WHOLE record.  The unconstrained MFE of `seq` at int(-t) under the
     model of global_refold (no --span) against `randomizations` shuffles of it (`functions.scramble`, "di" or "mono"), folded
     in one `functions.energies` call — past 400 nt one batched whole-record fold (sf_fold_long_batch) — and turned into a
@@ -259,16 +260,25 @@ def global_zscore(seq, name, outname, temperature, randomizations, shuffle_type,
     r = 100 by the single-fold time of DESIGN 4.4 (the batch's tables for such a record are one chunk per sequence).
     The shuffles draw from Python's `random` seeded with `seed`; the generator's state, and the engine's span, parameter
     set and temperature, are put back as they were, also when a fold raises, so every other output of the run is the same
-    with and without the flag."""
+    with and without the flag.
+    span (--global_zscore_span N, not upstream): the record and the same shuffles are folded under max_bp_span = N in banded
+    tables, all r + 1 of them in one Engine.fold_banded_batch (sf_fold_banded_batch: B = min(N, L) fill launches for all of
+    them, their exterior loops side by side), at a cost linear in the record's length and at any length up to
+    SF_MAX_BANDED; the file gains a trailing column Span."""
     import random
+    span = int(span or 0)
     eng = _lib.get_engine()
     span0, params0 = eng.max_bp_span, eng.params
     state0 = random.getstate()
     try:
         random.seed(seed)
         shuffles = sff.scramble(seq, randomizations, shuffle_type)
-        eng.set_max_bp_span(0)  # (the scan's --span is engine state; the whole-record model has none)
-        E = sff.energies([seq] + shuffles, int(temperature))
+        eng.set_max_bp_span(span)  # (the scan's --span is engine state; the whole-record model has none, or this flag's)
+        if span > 0:
+            eng.set_temperature(int(temperature))
+            E = sff._dcal_to_float(eng.fold_banded_batch([seq] + shuffles))
+        else:
+            E = sff.energies([seq] + shuffles, int(temperature))
     finally:
         random.setstate(state0)
         if eng.params is not params0:
@@ -279,8 +289,12 @@ def global_zscore(seq, name, outname, temperature, randomizations, shuffle_type,
     p = sff.pvalue_function(E, randomizations)
     row = [str(name), str(len(seq)), str(int(temperature)), str(randomizations), str(shuffle_type)]
     row += [str(round(x, 2)) for x in (E[0], statistics.mean(E[1:]), statistics.stdev(E[1:]), z, p)]
+    header = GLOBAL_ZSCORE_HEADER
+    if span > 0:
+        header = header[:-1] + "\tSpan\n"
+        row.append(str(span))
     with open(outname + ".global_zscore.txt", "w") as w:
-        w.write(GLOBAL_ZSCORE_HEADER)
+        w.write(header)
         w.write("\t".join(row) + "\n")
 
 
@@ -318,6 +332,10 @@ def build_parser():
     p.add_argument('--global_zscore', action='store_true',
                    help='not in upstream ScanFold: z-score of the whole record (its MFE at -t, no --span, against -r shuffles of '
                         '--type seeded with --seed) into <output prefix>.global_zscore.txt; costs r + 1 whole-record folds')
+    p.add_argument('--global_zscore_span', type=int, default=None,
+                   help='not in upstream ScanFold: the z-score of --global_zscore under this max bp span, the record and its '
+                        'shuffles folded together in banded tables (time linear in its length; records past 32767 nt); '
+                        'the file gains a Span column')
     p.add_argument('--dbn_file_path', type=str, default="AllDBN-global_refold.txt",
                    help='file name (after the output prefix) of the global refold records')
     p.add_argument('--lri', action='store_true', help='scan for long range interactions (k-mer duplexes) instead of windows')
@@ -365,6 +383,19 @@ def main(argv=None):
                                  % (read_name, len(seq), _lib.SF_MAX_BANDED))
     if args.global_zscore and args.lri:
         raise ValueError("--global_zscore z-scores the record of a window scan: not with --lri")
+    if args.global_zscore_span is not None:  # refused before any record is scanned
+        if args.global_zscore:
+            raise ValueError("--global_zscore and --global_zscore_span write the same file: give one of them")
+        if args.lri:
+            raise ValueError("--global_zscore_span z-scores the record of a window scan: not with --lri")
+        if args.global_zscore_span < 1:
+            raise ValueError("--global_zscore_span N needs a base-pair span N >= 1")
+        if args.type not in ("di", "mono"):
+            raise ValueError('Shuffle type not properly designated; please input "di" or "mono"')
+        for read_name, seq in scanmod.read_fasta(args.filename):
+            if len(seq) > _lib.SF_MAX_BANDED:
+                raise ValueError("--global_zscore_span: record %s has %d nt, banded folds stop at %d"
+                                 % (read_name, len(seq), _lib.SF_MAX_BANDED))
     if args.global_zscore:  # refused before any record is scanned
         if args.type not in ("di", "mono"):
             raise ValueError('Shuffle type not properly designated; please input "di" or "mono"')
@@ -433,9 +464,9 @@ def main(argv=None):
             writers.write_wig(zlist, step, args.name, outname + ".scan-zscores.wig")
             writers.write_wig(table.pvalues, step, args.name, outname + ".scan-pvalue.wig")
             writers.write_wig(table.ed.tolist(), step, args.name, outname + ".scan-ED.wig")
-            if args.global_zscore:
+            if args.global_zscore or args.global_zscore_span:
                 print("Folding the full sequence and its shuffles for the global z-score...")
-                global_zscore(seq, args.name, outname, args.t, r, args.type, args.seed)
+                global_zscore(seq, args.name, outname, args.t, r, args.type, args.seed, span=args.global_zscore_span or 0)
             if args.global_refold:
                 print("Refolding full sequence using ScanFold results as constraints...")
                 global_refold(seq, args.name, outname, args.t, args.dbn_file_path, ensemble=args.global_ensemble,
@@ -446,8 +477,8 @@ def main(argv=None):
                 found = motifmod.extract_structures(line, seq)
                 motifmod.refold_motifs(read_name, found, args.type, outname + ".ExtractedStructures.gff3",
                                        folder=motifmod.EngineFolder(args.t, args.algo), file_prefix=outname)
-        elif args.global_zscore:
-            global_zscore(seq, args.name, outname, args.t, r, args.type, args.seed)
+        elif args.global_zscore or args.global_zscore_span:
+            global_zscore(seq, args.name, outname, args.t, r, args.type, args.seed, span=args.global_zscore_span or 0)
     return 0
 
 
