@@ -52,7 +52,8 @@ int sf_fold_long_times(double *fill_ms, double *f5_ms, double *trace_ms);
  * constraint are int32 here).  seq, cons, mfe_dcal_out, db_out as for sf_fold_long.  S >= L is legal (B = L: a full fold
  * in banded storage).  B fill launches, then f5 in O(L B) and the traceback, each in one workgroup.
  * The tables live in device memory, allocated for the call and freed before it returns: SF_BANDED_BYTES(L, B) bytes, of
- * which 9 (L + 2) (the constraint's arrays) only with a constraint: 12 L B + 75 L + 4 B + 153
+ * which 9 (L + 2) (the constraint's arrays) only with a constraint and 49 L + 97 (the traceback stack and the structure)
+ * only with db_out, in at most seven allocations: 12 L B + 75 L + 4 B + 153
  * (218 MB at L = 29 903, S = 600; 3.6 GB at L = 500 000, S = 600).
  * No span set, L < 1, L > SF_MAX_BANDED, seq NULL: SF_ERR_BAD_ARG (without a span, call sf_fold_long).  Unbalanced
  * brackets: SF_ERR_CONSTRAINT, before anything is launched.  Not enough device memory: SF_ERR_HIP with the text in

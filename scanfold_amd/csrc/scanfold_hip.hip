@@ -1196,13 +1196,14 @@ struct LongPack {
   std::vector<uint8_t> h8;    // sequences and constraint rows, copied up in one piece
 };
 
-LongPack long_pack(const LongRows &R, int s0, int n) {
+// with_cons false: the sequences alone (the banded folds parse their constraints on the host and keep them elsewhere)
+LongPack long_pack(const LongRows &R, int s0, int n, bool with_cons = true) {
   LongPack K;
   for (int k = 0; k < n; k++) {
     const int L = R.len[s0 + k];
     K.Lmax = std::max(K.Lmax, L);
     K.n_L += (size_t)L;
-    if (R.constrained[s0 + k]) { K.n_hc++; K.n_hcL += (size_t)L; }
+    if (with_cons && R.constrained[s0 + k]) { K.n_hc++; K.n_hcL += (size_t)L; }
   }
   K.o_src = K.n_L + 2 * (size_t)n;
   K.o_hc = K.o_src + K.n_hcL;
@@ -1214,7 +1215,7 @@ LongPack long_pack(const LongRows &R, int s0, int n) {
     const uint8_t *row = R.seqs + (size_t)(s0 + k) * R.ld;
     uint8_t *hS = K.h8.data() + a_L + 2 * (size_t)k;
     for (int x = 0; x < L; x++) hS[x + 1] = sf_encode_nt(row[x]);
-    if (R.constrained[s0 + k]) {
+    if (with_cons && R.constrained[s0 + k]) {
       memcpy(K.h8.data() + K.o_src + a_hcL, R.cons + (size_t)(s0 + k) * R.ld, (size_t)L);
       a_hcL += (size_t)L;
     }
@@ -1271,78 +1272,154 @@ std::vector<int32_t> long_hairpin_table(const sf_params_blob *P, int n) {
   return hp;
 }
 
-// One whole-record fold, the host side of sf_fold_long (State = SfLong) and sf_fold_banded (SfBand), after their argument
-// checks.  F comes in zeroed but for L (and B).  Allocates the three tables of `entries` cells and the linear arrays, uploads
-// the sequence and a hairpin table of n_hp + 1 entries, lets bind_hc(B, F) set F.hc, then runs fill(F, D, threads) (the
-// caller's loop over diagonals), f5_kernel in one workgroup of f5_threads and, with db_out, trace_kernel.  Energy and
-// structure reach the caller only when the status word is clean (the structure is staged in host memory until then); ms_out
-// takes the device-event times of the three phases.
-template <class State, class BindHc, class Fill>
-int whole_fold(const char *who, State &F, const uint8_t *seq, size_t entries, int n_hp, BindHc bind_hc, Fill fill,
-               void (*f5_kernel)(State, const SfDevParams *, int32_t *), int f5_threads,
-               void (*trace_kernel)(State, const SfDevParams *), int32_t *mfe_out, char *db_out, double ms_out[3]) {
+// The minimum free energy folds of rows s0 .. s0 + n - 1 of R: the host side of sf_fold_long and sf_fold_banded (their one
+// row) and of one chunk of sf_fold_long_batch and sf_fold_banded_batch, after their argument checks; the counterpart of
+// pf_long_rows below.  e_host / db_host: the caller's staging buffers (the energies at e_host[s0 ..], the structures back
+// to back, L + 1 bytes each, at db_host, or NULL: no traceback and no memory for it); they hold the results once the stream
+// has drained, which read_status waits for.  ms_out grows by the device-event times of fill, f5 and traceback.  A fixed
+// number of device allocations whatever n is, all freed on return: c, fML, fMLt (ops.entries(L) a row), the DML rings, one
+// int32 block (a hairpin table of ops.hairpin_entries(Lmax) + 1 entries, energies, f5, traceback stacks), one byte block
+// (the packed rows, structures), what ops.bind allocates for the constraints, and the row states unless the kernels take
+// the state by value (Ops::by_value).  The caller's ops supply what differs between the layouts (Ops::State, host_hc,
+// entries, hairpin_entries, bind: a row's L / B / S / hc) and the launches over the states at F, in host memory when they
+// go by value and on the device otherwise: fill (every diagonal), f5 (energies to d_mfe) and trace.
+template <class Ops>
+int fold_rows(const LongRows &R, int s0, int n, Ops &ops, int32_t *e_host, char *db_host, double ms_out[3]) {
+  typedef typename Ops::State State;
   int rc;
-  const int L = F.L;
-  const size_t nL = (size_t)L;
-  std::vector<uint8_t> hS(nL + 2, 0);
-  for (int x = 0; x < L; x++) hS[x + 1] = sf_encode_nt(seq[x]);
-  const std::vector<int32_t> hhp = long_hairpin_table((const sf_params_blob *)g.slot[g.cur].src.data(), n_hp);
+  const LongPack K = long_pack(R, s0, n, !Ops::host_hc);
+  const int Lmax = K.Lmax;
+  const size_t n_L = K.n_L;
+  size_t cells = 0, n_stk = 0;
+  for (int k = 0; k < n; k++) {
+    cells += ops.entries(R.len[s0 + k]);
+    n_stk += SF_LONG_STACK_INTS(R.len[s0 + k]);
+  }
+  const bool trace = db_host != nullptr;
+  // slices of the int32 allocation, in elements; the structures follow the packed rows in the byte block
+  const std::vector<int32_t> hhp = long_hairpin_table((const sf_params_blob *)g.slot[g.cur].src.data(), ops.hairpin_entries(Lmax));
+  const size_t o_hp = 0, o_mfe = o_hp + hhp.size(), o_f5 = o_mfe + (size_t)n, o_stk = o_f5 + n_L + (size_t)n;
+  const size_t n_i32 = o_stk + (trace ? n_stk : 0);
+  const size_t o_db = K.o_end, n_u8 = o_db + (trace ? n_L + (size_t)n : 0);
+  std::vector<State> hF((size_t)n);
 
-  int32_t e = 0;  // (these outlive B: the copies into them are drained by its destructor on an early return)
-  std::vector<char> hdb(db_out ? nL + 1 : 0);
   LongBufs B;
-  B.who = who;
+  B.who = R.who;
   void *p;
-  if ((rc = B.alloc(&p, entries * sizeof(int32_t), "c"))) return rc;
-  F.c = (int32_t *)p;
-  if ((rc = B.alloc(&p, entries * sizeof(int32_t), "fML"))) return rc;
-  F.fML = (int32_t *)p;
-  if ((rc = B.alloc(&p, entries * sizeof(int32_t), "fML transposed"))) return rc;
-  F.fMLt = (int32_t *)p;
-  if ((rc = B.alloc(&p, 3 * (nL + 2) * sizeof(int32_t), "DML ring"))) return rc;
-  F.dml = (int32_t *)p;
-  if ((rc = B.alloc(&p, (nL + 1) * sizeof(int32_t), "f5"))) return rc;
-  F.f5 = (int32_t *)p;
-  if ((rc = B.alloc(&p, SF_LONG_STACK_INTS(L) * sizeof(int32_t), "traceback stack"))) return rc;
-  F.stk = (int32_t *)p;
-  if ((rc = B.alloc(&p, nL + 1, "structure"))) return rc;
-  F.db = (char *)p;
-  if ((rc = B.alloc(&p, nL + 2, "sequence"))) return rc;
-  F.S = (const uint8_t *)p;
-  HIPCHK(hipMemcpyAsync(p, hS.data(), nL + 2, hipMemcpyHostToDevice, g.stream));
-  if ((rc = B.alloc(&p, hhp.size() * sizeof(int32_t), "hairpin table"))) return rc;
-  F.hp = (const int32_t *)p;
-  HIPCHK(hipMemcpyAsync(p, hhp.data(), hhp.size() * sizeof(int32_t), hipMemcpyHostToDevice, g.stream));
-  if ((rc = B.alloc(&p, sizeof(int32_t), "energy"))) return rc;
-  int32_t *d_mfe = (int32_t *)p;
-  F.status = (int *)g.status.p;
-  if ((rc = bind_hc(B, F))) return rc;
-  for (auto &ev : B.ev) HIPCHK(hipEventCreate(&ev));
+  int32_t *d_tab[3], *d_dml, *d_i32;
+  uint8_t *d_u8;
+  const State *F = hF.data();
+  static const char *const names[3] = {"c", "fML", "fML transposed"};
+  for (int k = 0; k < 3; k++) {
+    if ((rc = B.alloc(&p, cells * sizeof(int32_t), names[k]))) return rc;
+    d_tab[k] = (int32_t *)p;
+  }
+  if ((rc = B.alloc(&p, 3 * (n_L + 2 * (size_t)n) * sizeof(int32_t), "DML rings"))) return rc;
+  d_dml = (int32_t *)p;
+  if ((rc = B.alloc(&p, n_i32 * sizeof(int32_t), "hairpin table, energies, f5, traceback stacks"))) return rc;
+  d_i32 = (int32_t *)p;
+  if ((rc = B.alloc(&p, n_u8, "sequences, constraints, structures"))) return rc;
+  d_u8 = (uint8_t *)p;
+  if (!Ops::by_value) {
+    if ((rc = B.alloc(&p, (size_t)n * sizeof(State), "fold states"))) return rc;
+    F = (const State *)p;
+  }
+  if ((rc = ops.bind(B, K, R, s0, d_u8, hF))) return rc;
+
+  size_t a_cells = 0, a_L = 0, a_stk = 0;
+  for (int k = 0; k < n; k++) {
+    const int L = R.len[s0 + k];
+    State &Fk = hF[k];
+    Fk.hp = d_i32 + o_hp;
+    Fk.c = d_tab[0] + a_cells;
+    Fk.fML = d_tab[1] + a_cells;
+    Fk.fMLt = d_tab[2] + a_cells;
+    Fk.dml = d_dml + 3 * (a_L + 2 * (size_t)k);
+    Fk.f5 = d_i32 + o_f5 + a_L + (size_t)k;
+    Fk.status = (int *)g.status.p;
+    if (trace) {
+      Fk.stk = d_i32 + o_stk + a_stk;
+      Fk.db = (char *)d_u8 + o_db + a_L + (size_t)k;
+    }
+    a_cells += ops.entries(L);
+    a_L += (size_t)L;
+    a_stk += SF_LONG_STACK_INTS(L);
+  }
+  HIPCHK(hipMemcpyAsync(d_i32 + o_hp, hhp.data(), hhp.size() * sizeof(int32_t), hipMemcpyHostToDevice, g.stream));
+  if (!Ops::by_value) HIPCHK(hipMemcpyAsync((void *)F, hF.data(), (size_t)n * sizeof(State), hipMemcpyHostToDevice, g.stream));
+
+  for (auto &e : B.ev) HIPCHK(hipEventCreate(&e));
   const SfDevParams *D = (const SfDevParams *)g.dP;
-  const int threads = 256;
+  const int32_t *len = R.len + s0;
   HIPCHK(hipEventRecord(B.ev[0], g.stream));
-  fill(F, D, threads);
+  ops.fill(F, len, n, Lmax, D);
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(B.ev[1], g.stream));
-  SF_LAUNCH(f5_kernel, 1, f5_threads, 0, g.stream, F, D, d_mfe);
+  ops.f5(F, n, Lmax, D, d_i32 + o_mfe);
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(B.ev[2], g.stream));
-  if (db_out) {
-    SF_LAUNCH(trace_kernel, 1, threads, 0, g.stream, F, D);
+  if (trace) {
+    ops.trace(F, n, D);
     HIPCHK(hipGetLastError());
   }
   HIPCHK(hipEventRecord(B.ev[3], g.stream));
-  HIPCHK(hipMemcpyAsync(&e, d_mfe, sizeof e, hipMemcpyDeviceToHost, g.stream));
-  if (db_out) HIPCHK(hipMemcpyAsync(hdb.data(), F.db, nL + 1, hipMemcpyDeviceToHost, g.stream));
+  HIPCHK(hipMemcpyAsync(e_host + s0, d_i32 + o_mfe, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, g.stream));
+  if (trace) HIPCHK(hipMemcpyAsync(db_host, d_u8 + o_db, n_L + (size_t)n, hipMemcpyDeviceToHost, g.stream));
   if ((rc = read_status(g.stream, false))) return rc;
-  if (mfe_out) *mfe_out = e;
-  if (db_out) memcpy(db_out, hdb.data(), nL + 1);
-  float ms[3] = {0, 0, 0};
-  for (int k = 0; k < 3; k++) HIPCHK(hipEventElapsedTime(&ms[k], B.ev[k], B.ev[k + 1]));
-  for (int k = 0; k < 3; k++) ms_out[k] = ms[k];
-  if (!db_out) ms_out[2] = 0.0;
+  for (int k = 0; k < 3; k++) {
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, B.ev[k], B.ev[k + 1]));
+    ms_out[k] += (k == 2 && !trace) ? 0.0 : ms;
+  }
   return SF_OK;
 }
+
+// A single call as the driver's one row, one chunk under any byte budget: R holds the row (ld = L, len = &L).  Energy and
+// structure are staged and, like the time record rec, written only when the call has succeeded.
+template <class Ops>
+int fold_single(LongRows &R, int max_len, Ops &ops, int32_t *mfe_out, char *db_out, double rec[3]) {
+  int rc;
+  if ((rc = long_rows_check(R, max_len))) return rc;
+  const size_t nL = (size_t)R.len[0];
+  int32_t e = 0;  // (these outlive the driver's buffers, whose destructor drains the copies into them)
+  std::vector<char> hdb(db_out ? nL + 1 : 0);
+  double ms[3] = {0, 0, 0};
+  if ((rc = fold_rows(R, 0, 1, ops, &e, db_out ? hdb.data() : nullptr, ms))) return rc;
+  if (mfe_out) *mfe_out = e;
+  if (db_out) memcpy(db_out, hdb.data(), nL + 1);
+  for (int k = 0; k < 3; k++) rec[k] = ms[k];
+  return SF_OK;
+}
+
+// What the triangular folds hand the driver: a row's tables hold SF_LONG_TRI(L) entries, the hairpin table reaches the
+// longest row, and the constraints are parsed on the device (int16 positions) by long_bind_rows.
+struct TriRows {
+  typedef SfLong State;
+  static const bool host_hc = false;
+  size_t entries(int L) const { return SF_LONG_TRI(L); }
+  int hairpin_entries(int Lmax) const { return Lmax; }
+  int bind(LongBufs &B, const LongPack &K, const LongRows &R, int s0, uint8_t *d_u8, std::vector<SfLong> &hF) {
+    return long_bind_rows(B, K, R, s0, d_u8, hF);
+  }
+};
+
+// sf_fold_long's launches: the one row's state goes to its kernels by value, with the row's own lane groups and grids.
+struct LongSingle : TriRows {
+  static const bool by_value = true;
+  void fill(const SfLong *F, const int32_t *, int, int L, const SfDevParams *D) {
+    const int threads = 256;
+    for (int d = 0; d < L; d++) {
+      const int G = long_group(d);
+      const size_t total = (size_t)(L - d) * (size_t)G;
+      const int grid = (int)((total + threads - 1) / threads);
+      SF_LAUNCH(sf_long_fill_kernel, grid, threads, 0, g.stream, *F, d, G, D);
+    }
+  }
+  void f5(const SfLong *F, int, int, const SfDevParams *D, int32_t *d_mfe) {
+    SF_LAUNCH(sf_long_f5_kernel, 1, 256, 0, g.stream, *F, D, d_mfe);
+  }
+  void trace(const SfLong *F, int, const SfDevParams *D) { SF_LAUNCH(sf_long_trace_kernel, 1, 256, 0, g.stream, *F, D); }
+};
 }  // namespace
 
 extern "C" {
@@ -1351,33 +1428,9 @@ int sf_fold_long(const uint8_t *seq, int L, const char *cons, int32_t *mfe_out, 
   int rc = check_ready();
   if (rc) return rc;
   if (!seq || L < 1 || L > SF_MAX_LONG) return SF_ERR_BAD_ARG;
-  bool noncanonical = false;  // (a type-7 bracket pair needs nothing special here: the int32 tables carry it)
-  if (cons && (rc = scan_constraints(seq, cons, 1, L, &noncanonical))) return rc;
-  SfLong F;
-  memset(&F, 0, sizeof F);
-  F.L = L;
-  // the constraint is parsed on the device, into int16 bracket partners and enclosing pairs
-  auto bind_hc = [&](LongBufs &B, SfLong &F) -> int {
-    if (!cons) return SF_OK;
-    int rc;
-    void *u8, *i16;  // the characters as given and parsed (L, then L + 2); long_parse_hc's int16 block
-    if ((rc = B.alloc(&u8, 2 * (size_t)L + 2, "constraint"))) return rc;
-    if ((rc = B.alloc(&i16, 3 * ((size_t)L + 2) * sizeof(int16_t), "bracket partners"))) return rc;
-    HIPCHK(hipMemcpyAsync(u8, cons, (size_t)L, hipMemcpyHostToDevice, g.stream));
-    long_parse_hc(F.hc, (const char *)u8, L, (char *)u8 + L, (int16_t *)i16);
-    HIPCHK(hipGetLastError());
-    return SF_OK;
-  };
-  auto fill = [&](const SfLong &F, const SfDevParams *D, int threads) {
-    for (int d = 0; d < L; d++) {
-      const int G = long_group(d);
-      const size_t total = (size_t)(L - d) * (size_t)G;
-      const int grid = (int)((total + threads - 1) / threads);
-      SF_LAUNCH(sf_long_fill_kernel, grid, threads, 0, g.stream, F, d, G, D);
-    }
-  };
-  return whole_fold("sf_fold_long", F, seq, SF_LONG_TRI(L), L, bind_hc, fill, sf_long_f5_kernel, 256, sf_long_trace_kernel,
-                    mfe_out, db_out, g_long_ms);
+  LongRows R = {seq, 1, L, &L, cons, "sf_fold_long"};
+  LongSingle ops;
+  return fold_single(R, SF_MAX_LONG, ops, mfe_out, db_out, g_long_ms);
 }
 
 int sf_fold_long_times(double *fill_ms, double *f5_ms, double *trace_ms) {
@@ -1451,16 +1504,74 @@ struct BandHc {
   }
 };
 
-size_t band_linear_bytes(int L, int B) {
-  return 3 * ((size_t)L + 2) * 4        // DML ring
-         + ((size_t)L + 1) * 4          // f5
-         + SF_LONG_STACK_INTS(L) * 4    // traceback stack
-         + ((size_t)L + 1)              // structure
-         + ((size_t)L + 2)              // sequence
-         + ((size_t)B + 1) * 4          // hairpin initiation
-         + 4                            // energy
-         + 9 * ((size_t)L + 2);         // constraint: characters, int32 bracket partners and enclosing pairs
-}
+// What the banded folds hand fold_rows: a row's tables hold L B entries, B = min(S, L), the hairpin table reaches the widest
+// band, and the constraints are parsed here (BandHc), into one allocation of their own: the constrained rows' bracket
+// partners, enclosing pairs and characters, L + 2 of each a row.  long_rows_check has seen that every row balances.
+struct BandRows {
+  typedef SfBand State;
+  static const bool host_hc = true;
+  const int S = g.max_bp_span;
+  std::vector<int32_t> h32;  // the parsed constraints as they are copied up (they outlive the driver's buffers)
+  std::vector<char> h8;
+  size_t entries(int L) const { return (size_t)L * (size_t)std::min(S, L); }
+  int hairpin_entries(int Lmax) const { return std::min(S, Lmax); }
+  int bind(LongBufs &B, const LongPack &K, const LongRows &R, int s0, uint8_t *d_u8, std::vector<SfBand> &hF) {
+    int rc;
+    size_t n_hc = 0, a_L = 0, a = 0;
+    for (size_t k = 0; k < hF.size(); k++)
+      if (R.constrained[s0 + k]) n_hc += (size_t)R.len[s0 + k] + 2;
+    h32.assign(2 * n_hc, 0);
+    h8.assign(n_hc, 0);
+    void *p = nullptr;
+    if (n_hc && (rc = B.alloc(&p, 9 * n_hc, "bracket partners, enclosing pairs, constraints"))) return rc;
+    const int32_t *d_part = (const int32_t *)p, *d_encl = d_part + n_hc;
+    const char *d_c = (const char *)(d_encl + n_hc);
+    HIPCHK(hipMemcpyAsync(d_u8, K.h8.data(), K.h8.size(), hipMemcpyHostToDevice, g.stream));
+    BandHc H;
+    for (size_t k = 0; k < hF.size(); k++) {
+      const int L = R.len[s0 + k];
+      SfBand &F = hF[k];
+      memset(&F, 0, sizeof F);
+      F.L = L;
+      F.B = std::min(S, L);
+      F.S = d_u8 + a_L + 2 * k;
+      if (R.constrained[s0 + k]) {
+        if ((rc = H.parse(R.cons + (size_t)(s0 + k) * R.ld, L))) return rc;
+        memcpy(h32.data() + a, H.part.data(), ((size_t)L + 2) * sizeof(int32_t));
+        memcpy(h32.data() + n_hc + a, H.encl.data(), ((size_t)L + 2) * sizeof(int32_t));
+        memcpy(h8.data() + a, H.c.data(), (size_t)L + 2);
+        F.hc.partner = d_part + a;
+        F.hc.encl = d_encl + a;
+        F.hc.c = d_c + a;
+        a += (size_t)L + 2;
+      }
+      a_L += (size_t)L;
+    }
+    if (n_hc) {
+      HIPCHK(hipMemcpyAsync(p, h32.data(), 8 * n_hc, hipMemcpyHostToDevice, g.stream));
+      HIPCHK(hipMemcpyAsync((char *)p + 8 * n_hc, h8.data(), n_hc, hipMemcpyHostToDevice, g.stream));
+    }
+    return SF_OK;
+  }
+};
+
+// sf_fold_banded's launches: the one row's state by value, one fill launch per diagonal of its band.
+struct BandSingle : BandRows {
+  static const bool by_value = true;
+  void fill(const SfBand *F, const int32_t *, int, int L, const SfDevParams *D) {
+    const int threads = 256;
+    for (int d = 0; d < F->B; d++) {
+      const size_t cells = (size_t)(L - d);
+      const int G = band_group(d, cells);
+      const int grid = (int)((cells * (size_t)G + threads - 1) / threads);
+      SF_LAUNCH(sf_band_fill_kernel, grid, threads, 0, g.stream, *F, d, G, D);
+    }
+  }
+  void f5(const SfBand *F, int, int, const SfDevParams *D, int32_t *d_mfe) {
+    SF_LAUNCH(sf_band_f5_kernel, 1, F->B <= 256 ? 64 : 256, 0, g.stream, *F, D, d_mfe);
+  }
+  void trace(const SfBand *F, int, const SfDevParams *D) { SF_LAUNCH(sf_band_trace_kernel, 1, 256, 0, g.stream, *F, D); }
+};
 }  // namespace
 
 extern "C" {
@@ -1468,8 +1579,7 @@ extern "C" {
 int sf_fold_banded_bytes(int L, int span, size_t *bytes) {
   SF_ENTER();
   if (L < 1 || L > SF_MAX_BANDED || span < 1 || !bytes) return SF_ERR_BAD_ARG;
-  const int B = std::min(span, L);
-  *bytes = 12 * (size_t)L * (size_t)B + band_linear_bytes(L, B);
+  *bytes = SF_BANDED_BYTES(L, std::min(span, L));
   return SF_OK;
 }
 
@@ -1477,28 +1587,10 @@ int sf_fold_banded(const uint8_t *seq, int L, const char *cons, int32_t *mfe_out
   int rc = check_ready();
   if (rc) return rc;
   if (!seq || L < 1 || L > SF_MAX_BANDED || g.max_bp_span < 1) return SF_ERR_BAD_ARG;
-  const int B = std::min(g.max_bp_span, L);
-  // the constraint, parsed here (sf_hc_parse with int32 positions); unbalanced brackets end the call before any launch
-  BandHc H;
-  if (cons && (rc = H.parse(cons, L))) return rc;
-  SfBand F;
-  memset(&F, 0, sizeof F);
-  F.L = L;
-  F.B = B;
-  auto bind_hc = [&](LongBufs &Bf, SfBand &F) -> int { return cons ? H.bind(Bf, F.hc) : SF_OK; };
-  auto fill = [&](const SfBand &F, const SfDevParams *D, int threads) {
-    for (int d = 0; d < B; d++) {
-      const size_t cells = (size_t)(L - d);
-      const int G = band_group(d, cells);
-      const int grid = (int)((cells * (size_t)G + threads - 1) / threads);
-      SF_LAUNCH(sf_band_fill_kernel, grid, threads, 0, g.stream, F, d, G, D);
-    }
-  };
-  rc = whole_fold("sf_fold_banded", F, seq, (size_t)L * (size_t)B, B, bind_hc, fill, sf_band_f5_kernel, B <= 256 ? 64 : 256,
-                  sf_band_trace_kernel, mfe_out, db_out, g_band_ms);
-  if (rc) return rc;
-  g_band_B = B;
-  g_band_launches = B;  // one fill launch per diagonal
+  LongRows R = {seq, 1, L, &L, cons, "sf_fold_banded"};
+  BandSingle ops;
+  if ((rc = fold_single(R, SF_MAX_BANDED, ops, mfe_out, db_out, g_band_ms))) return rc;
+  g_band_B = g_band_launches = std::min(ops.S, L);  // one fill launch per diagonal
   return SF_OK;
 }
 
@@ -1521,104 +1613,25 @@ int g_longb_chunks = 0;
 
 size_t long_batch_seq_bytes(int L) { return 12 * SF_LONG_TRI(L) + 80 * (size_t)L; }
 
-// Sequences s0 .. s0 + n - 1 as one chunk.  e_host / db_host: the caller's staging buffers (the chunk's energies at
-// e_host[s0 ..], its structures back to back, L + 1 bytes each, at db_host, or NULL: no traceback); they hold the results
-// once the stream has drained, which read_status below waits for.
-int long_batch_chunk(const LongRows &R, int s0, int n, int32_t *e_host, char *db_host, double ms_out[3]) {
-  int rc;
-  const sf_params_blob *P = (const sf_params_blob *)g.slot[g.cur].src.data();  // the resident set as it was handed in
-  const LongPack K = long_pack(R, s0, n);
-  const int Lmax = K.Lmax;
-  const size_t n_L = K.n_L;
-  size_t tri = 0, n_stk = 0;
-  for (int k = 0; k < n; k++) {
-    tri += SF_LONG_TRI(R.len[s0 + k]);
-    n_stk += SF_LONG_STACK_INTS(R.len[s0 + k]);
-  }
-  const bool trace = db_host != nullptr;
-  // slices of the int32 allocation, in elements; the structures follow the packed rows in the byte block
-  const size_t o_hp = 0, o_mfe = o_hp + (size_t)Lmax + 1, o_f5 = o_mfe + (size_t)n, o_stk = o_f5 + n_L + (size_t)n;
-  const size_t n_i32 = o_stk + (trace ? n_stk : 0);
-  const size_t o_db = K.o_end, n_u8 = o_db + (trace ? n_L + (size_t)n : 0);
-
-  const std::vector<int32_t> hhp = long_hairpin_table(P, Lmax);
-  std::vector<SfLong> hF((size_t)n);
-
-  LongBufs B;
-  B.who = R.who;
-  void *p;
-  int32_t *d_c, *d_fML, *d_fMLt, *d_dml, *d_i32;
-  uint8_t *d_u8;
-  SfLong *d_F;
-  if ((rc = B.alloc(&p, tri * sizeof(int32_t), "c"))) return rc;
-  d_c = (int32_t *)p;
-  if ((rc = B.alloc(&p, tri * sizeof(int32_t), "fML"))) return rc;
-  d_fML = (int32_t *)p;
-  if ((rc = B.alloc(&p, tri * sizeof(int32_t), "fML transposed"))) return rc;
-  d_fMLt = (int32_t *)p;
-  if ((rc = B.alloc(&p, 3 * (n_L + 2 * (size_t)n) * sizeof(int32_t), "DML rings"))) return rc;
-  d_dml = (int32_t *)p;
-  if ((rc = B.alloc(&p, n_i32 * sizeof(int32_t), "hairpin table, energies, f5, traceback stacks"))) return rc;
-  d_i32 = (int32_t *)p;
-  if ((rc = B.alloc(&p, n_u8, "sequences, constraints, structures"))) return rc;
-  d_u8 = (uint8_t *)p;
-  if ((rc = B.alloc(&p, (size_t)n * sizeof(SfLong), "fold states"))) return rc;
-  d_F = (SfLong *)p;
-  if ((rc = long_bind_rows(B, K, R, s0, d_u8, hF))) return rc;
-
-  size_t a_tri = 0, a_L = 0, a_stk = 0;
-  for (int k = 0; k < n; k++) {
-    const int L = R.len[s0 + k];
-    SfLong &F = hF[k];
-    F.hp = d_i32 + o_hp;
-    F.c = d_c + a_tri;
-    F.fML = d_fML + a_tri;
-    F.fMLt = d_fMLt + a_tri;
-    F.dml = d_dml + 3 * (a_L + 2 * (size_t)k);
-    F.f5 = d_i32 + o_f5 + a_L + (size_t)k;
-    F.status = (int *)g.status.p;
-    if (trace) {
-      F.stk = d_i32 + o_stk + a_stk;
-      F.db = (char *)d_u8 + o_db + a_L + (size_t)k;
-    }
-    a_tri += SF_LONG_TRI(L);
-    a_L += (size_t)L;
-    a_stk += SF_LONG_STACK_INTS(L);
-  }
-  HIPCHK(hipMemcpyAsync(d_i32 + o_hp, hhp.data(), hhp.size() * sizeof(int32_t), hipMemcpyHostToDevice, g.stream));
-  HIPCHK(hipMemcpyAsync(d_F, hF.data(), (size_t)n * sizeof(SfLong), hipMemcpyHostToDevice, g.stream));
-
-  for (auto &e : B.ev) HIPCHK(hipEventCreate(&e));
-  const SfDevParams *D = (const SfDevParams *)g.dP;
+// A chunk's launches: the row states in a device array, every launch over all rows, the lanes per cell cut down until a
+// diagonal's launch fits the lane budget.
+struct LongBatch : TriRows {
+  static const bool by_value = false;
   const int threads = SF_LONGB_THREADS;
-  const size_t budget = (size_t)(g.n_cu > 0 ? g.n_cu : 1) * SF_LONGB_LANES_PER_CU;
-  HIPCHK(hipEventRecord(B.ev[0], g.stream));
-  for (int d = 0; d < Lmax; d++) {
-    int G = long_group(d);
-    while (G > 1 && (size_t)n * (size_t)(Lmax - d) * (size_t)G > budget) G >>= 1;
-    const int bps = (int)(((size_t)(Lmax - d) * (size_t)G + threads - 1) / threads);
-    SF_LAUNCH(sf_longb_fill_kernel, n * bps, threads, 0, g.stream, (const SfLong *)d_F, d, G, bps, D);
+  void fill(const SfLong *d_F, const int32_t *, int n, int Lmax, const SfDevParams *D) {
+    const size_t budget = (size_t)(g.n_cu > 0 ? g.n_cu : 1) * SF_LONGB_LANES_PER_CU;
+    for (int d = 0; d < Lmax; d++) {
+      int G = long_group(d);
+      while (G > 1 && (size_t)n * (size_t)(Lmax - d) * (size_t)G > budget) G >>= 1;
+      const int bps = (int)(((size_t)(Lmax - d) * (size_t)G + threads - 1) / threads);
+      SF_LAUNCH(sf_longb_fill_kernel, n * bps, threads, 0, g.stream, d_F, d, G, bps, D);
+    }
   }
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(B.ev[1], g.stream));
-  SF_LAUNCH(sf_longb_f5_kernel, n, threads, 0, g.stream, (const SfLong *)d_F, D, d_i32 + o_mfe);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(B.ev[2], g.stream));
-  if (trace) {
-    SF_LAUNCH(sf_longb_trace_kernel, n, threads, 0, g.stream, (const SfLong *)d_F, D);
-    HIPCHK(hipGetLastError());
+  void f5(const SfLong *d_F, int n, int, const SfDevParams *D, int32_t *d_mfe) {
+    SF_LAUNCH(sf_longb_f5_kernel, n, threads, 0, g.stream, d_F, D, d_mfe);
   }
-  HIPCHK(hipEventRecord(B.ev[3], g.stream));
-  HIPCHK(hipMemcpyAsync(e_host + s0, d_i32 + o_mfe, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, g.stream));
-  if (trace) HIPCHK(hipMemcpyAsync(db_host, d_u8 + o_db, n_L + (size_t)n, hipMemcpyDeviceToHost, g.stream));
-  if ((rc = read_status(g.stream, false))) return rc;
-  for (int k = 0; k < 3; k++) {
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, B.ev[k], B.ev[k + 1]));
-    ms_out[k] += (k == 2 && !trace) ? 0.0 : ms;
-  }
-  return SF_OK;
-}
+  void trace(const SfLong *d_F, int n, const SfDevParams *D) { SF_LAUNCH(sf_longb_trace_kernel, n, threads, 0, g.stream, d_F, D); }
+};
 }  // namespace
 
 extern "C" {
@@ -1633,8 +1646,9 @@ int sf_fold_long_batch(const uint8_t *seqs, int n, int ld, const int32_t *len, c
   std::vector<int32_t> e_host((size_t)n);
   double ms[3] = {0, 0, 0};
   int chunks;
+  LongBatch ops;
   rc = long_for_chunks(R, long_batch_seq_bytes, db_out, &chunks, [&](int s0, int m, char *db_host) {
-    return long_batch_chunk(R, s0, m, e_host.data(), db_host, ms);
+    return fold_rows(R, s0, m, ops, e_host.data(), db_host, ms);
   });
   if (rc) return rc;  // (n == 0: no chunk)
   if (n) memcpy(mfe_out, e_host.data(), (size_t)n * sizeof(int32_t));
@@ -1664,137 +1678,32 @@ namespace {
 double g_bandb_ms[3] = {0, 0, 0};  // fill, f5, traceback of the last sf_fold_banded_batch, summed over its chunks
 int g_bandb_chunks = 0, g_bandb_launches = 0;
 
-// Sequences s0 .. s0 + n - 1 as one chunk under the span S, each in a band of B_s = min(S, L_s) diagonals.  e_host / db_host
-// as in long_batch_chunk.  The chunk's tables are slices of a fixed number of allocations: c, fML, fMLt (L_s B_s entries a
-// row), the DML rings, one int32 block (hairpin table of max B_s + 1 entries, the constrained rows' bracket partners and
-// enclosing pairs, energies, f5, traceback stacks), one byte block (sequences, the constrained rows' parsed characters,
-// structures) and the states.  *launches grows by the chunk's fill launches, max B_s.
-int band_batch_chunk(const LongRows &R, int S, int s0, int n, int32_t *e_host, char *db_host, double ms_out[3], int *launches) {
-  int rc;
-  const sf_params_blob *P = (const sf_params_blob *)g.slot[g.cur].src.data();  // the resident set as it was handed in
-  const LongPack K = long_pack(R, s0, n);
-  const int Lmax = K.Lmax, Bmax = std::min(S, Lmax);
-  const size_t n_L = K.n_L, n_hc = K.n_hcL + 2 * (size_t)K.n_hc;  // (a constrained row's arrays have L + 2 entries)
-  size_t cells = 0, n_stk = 0;
-  for (int k = 0; k < n; k++) {
-    const int L = R.len[s0 + k];
-    cells += (size_t)L * (size_t)std::min(S, L);
-    n_stk += SF_LONG_STACK_INTS(L);
-  }
-  const bool trace = db_host != nullptr;
-  // slices of the int32 allocation, in elements: what is copied up comes first
-  const size_t o_hp = 0, o_part = o_hp + (size_t)Bmax + 1, o_encl = o_part + n_hc, o_mfe = o_encl + n_hc;
-  const size_t o_f5 = o_mfe + (size_t)n, o_stk = o_f5 + n_L + (size_t)n, n_i32 = o_stk + (trace ? n_stk : 0);
-  // and of the byte block: the sequences (L + 2 each), the parsed constraint characters, the structures
-  const size_t o_c = K.o_src, o_db = o_c + n_hc, n_u8 = o_db + (trace ? n_L + (size_t)n : 0);
-
-  std::vector<int32_t> h32 = long_hairpin_table(P, Bmax);
-  h32.resize(o_mfe, 0);
-  std::vector<uint8_t> h8(K.h8.begin(), K.h8.begin() + (ptrdiff_t)K.o_src);
-  h8.resize(o_db, 0);
-  {  // the constraints, parsed here (int32 positions); long_rows_check has seen that every row balances
-    BandHc H;
-    size_t a = 0;
-    for (int k = 0; k < n; k++) {
-      if (!R.constrained[s0 + k]) continue;
-      const int L = R.len[s0 + k];
-      if ((rc = H.parse(R.cons + (size_t)(s0 + k) * R.ld, L))) return rc;
-      memcpy(h8.data() + o_c + a, H.c.data(), (size_t)L + 2);
-      memcpy(h32.data() + o_part + a, H.part.data(), ((size_t)L + 2) * sizeof(int32_t));
-      memcpy(h32.data() + o_encl + a, H.encl.data(), ((size_t)L + 2) * sizeof(int32_t));
-      a += (size_t)L + 2;
-    }
-  }
-  std::vector<SfBand> hF((size_t)n);
-
-  LongBufs B;
-  B.who = R.who;
-  void *p;
-  int32_t *d_c, *d_fML, *d_fMLt, *d_dml, *d_i32;
-  uint8_t *d_u8;
-  SfBand *d_F;
-  if ((rc = B.alloc(&p, cells * sizeof(int32_t), "c"))) return rc;
-  d_c = (int32_t *)p;
-  if ((rc = B.alloc(&p, cells * sizeof(int32_t), "fML"))) return rc;
-  d_fML = (int32_t *)p;
-  if ((rc = B.alloc(&p, cells * sizeof(int32_t), "fML transposed"))) return rc;
-  d_fMLt = (int32_t *)p;
-  if ((rc = B.alloc(&p, 3 * (n_L + 2 * (size_t)n) * sizeof(int32_t), "DML rings"))) return rc;
-  d_dml = (int32_t *)p;
-  if ((rc = B.alloc(&p, n_i32 * sizeof(int32_t), "hairpin table, bracket partners, energies, f5, traceback stacks"))) return rc;
-  d_i32 = (int32_t *)p;
-  if ((rc = B.alloc(&p, n_u8, "sequences, constraints, structures"))) return rc;
-  d_u8 = (uint8_t *)p;
-  if ((rc = B.alloc(&p, (size_t)n * sizeof(SfBand), "fold states"))) return rc;
-  d_F = (SfBand *)p;
-
-  size_t a_cells = 0, a_L = 0, a_stk = 0, a_hc = 0;
-  for (int k = 0; k < n; k++) {
-    const int L = R.len[s0 + k];
-    SfBand &F = hF[k];
-    memset(&F, 0, sizeof F);
-    F.L = L;
-    F.B = std::min(S, L);
-    F.S = d_u8 + a_L + 2 * (size_t)k;
-    F.hp = d_i32 + o_hp;
-    if (R.constrained[s0 + k]) {
-      F.hc.c = (const char *)d_u8 + o_c + a_hc;
-      F.hc.partner = d_i32 + o_part + a_hc;
-      F.hc.encl = d_i32 + o_encl + a_hc;
-      a_hc += (size_t)L + 2;
-    }
-    F.c = d_c + a_cells;
-    F.fML = d_fML + a_cells;
-    F.fMLt = d_fMLt + a_cells;
-    F.dml = d_dml + 3 * (a_L + 2 * (size_t)k);
-    F.f5 = d_i32 + o_f5 + a_L + (size_t)k;
-    F.status = (int *)g.status.p;
-    if (trace) {
-      F.stk = d_i32 + o_stk + a_stk;
-      F.db = (char *)d_u8 + o_db + a_L + (size_t)k;
-    }
-    a_cells += (size_t)L * (size_t)F.B;
-    a_L += (size_t)L;
-    a_stk += SF_LONG_STACK_INTS(L);
-  }
-  HIPCHK(hipMemcpyAsync(d_i32, h32.data(), h32.size() * sizeof(int32_t), hipMemcpyHostToDevice, g.stream));
-  HIPCHK(hipMemcpyAsync(d_u8, h8.data(), h8.size(), hipMemcpyHostToDevice, g.stream));
-  HIPCHK(hipMemcpyAsync(d_F, hF.data(), (size_t)n * sizeof(SfBand), hipMemcpyHostToDevice, g.stream));
-
-  for (auto &e : B.ev) HIPCHK(hipEventCreate(&e));
-  const SfDevParams *D = (const SfDevParams *)g.dP;
+// A chunk's launches under the span S, each row in a band of B_s = min(S, L_s) diagonals: the row states in a device array,
+// one fill launch per diagonal d < max B_s over all rows, its lanes per cell sized by the cells of the rows still live on it.
+// `launches` grows by a chunk's fill launches.
+struct BandBatch : BandRows {
+  static const bool by_value = false;
   const int threads = SF_BANDB_THREADS;
-  std::vector<int> lens(R.len + s0, R.len + s0 + n);
-  std::sort(lens.begin(), lens.end());  // the rows live on diagonal d (d < B_s, that is d < L_s: d < S here) are a suffix
-  size_t live = 0, live_L = n_L;        // rows with L_s > d, and their nucleotides
-  HIPCHK(hipEventRecord(B.ev[0], g.stream));
-  for (int d = 0; d < Bmax; d++) {
-    while (live < (size_t)n && lens[live] <= d) live_L -= (size_t)lens[live++];
-    const int G = band_group(d, live_L - ((size_t)n - live) * (size_t)d);  // the cells of all rows on this diagonal
-    const int bps = (int)(((size_t)(Lmax - d) * (size_t)G + threads - 1) / threads);
-    SF_LAUNCH(sf_bandb_fill_kernel, n * bps, threads, 0, g.stream, (const SfBand *)d_F, d, G, bps, D);
+  int launches = 0;
+  void fill(const SfBand *d_F, const int32_t *len, int n, int Lmax, const SfDevParams *D) {
+    const int Bmax = std::min(S, Lmax);
+    std::vector<int> lens(len, len + n);
+    std::sort(lens.begin(), lens.end());  // the rows live on diagonal d (d < B_s, that is d < L_s: d < S here) are a suffix
+    size_t live = 0, live_L = 0;          // rows with L_s > d, and their nucleotides
+    for (int L : lens) live_L += (size_t)L;
+    for (int d = 0; d < Bmax; d++) {
+      while (live < (size_t)n && lens[live] <= d) live_L -= (size_t)lens[live++];
+      const int G = band_group(d, live_L - ((size_t)n - live) * (size_t)d);  // the cells of all rows on this diagonal
+      const int bps = (int)(((size_t)(Lmax - d) * (size_t)G + threads - 1) / threads);
+      SF_LAUNCH(sf_bandb_fill_kernel, n * bps, threads, 0, g.stream, d_F, d, G, bps, D);
+    }
+    launches += Bmax;
   }
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(B.ev[1], g.stream));
-  SF_LAUNCH(sf_bandb_f5_kernel, n, Bmax <= 256 ? 64 : 256, 0, g.stream, (const SfBand *)d_F, D, d_i32 + o_mfe);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(B.ev[2], g.stream));
-  if (trace) {
-    SF_LAUNCH(sf_bandb_trace_kernel, n, threads, 0, g.stream, (const SfBand *)d_F, D);
-    HIPCHK(hipGetLastError());
+  void f5(const SfBand *d_F, int n, int Lmax, const SfDevParams *D, int32_t *d_mfe) {
+    SF_LAUNCH(sf_bandb_f5_kernel, n, std::min(S, Lmax) <= 256 ? 64 : 256, 0, g.stream, d_F, D, d_mfe);
   }
-  HIPCHK(hipEventRecord(B.ev[3], g.stream));
-  HIPCHK(hipMemcpyAsync(e_host + s0, d_i32 + o_mfe, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, g.stream));
-  if (trace) HIPCHK(hipMemcpyAsync(db_host, d_u8 + o_db, n_L + (size_t)n, hipMemcpyDeviceToHost, g.stream));
-  if ((rc = read_status(g.stream, false))) return rc;
-  for (int k = 0; k < 3; k++) {
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, B.ev[k], B.ev[k + 1]));
-    ms_out[k] += (k == 2 && !trace) ? 0.0 : ms;
-  }
-  *launches += Bmax;
-  return SF_OK;
-}
+  void trace(const SfBand *d_F, int n, const SfDevParams *D) { SF_LAUNCH(sf_bandb_trace_kernel, n, threads, 0, g.stream, d_F, D); }
+};
 }  // namespace
 
 extern "C" {
@@ -1809,16 +1718,17 @@ int sf_fold_banded_batch(const uint8_t *seqs, int n, int ld, const int32_t *len,
   // the energies are staged and handed over, like the structures, only when every chunk has succeeded
   std::vector<int32_t> e_host((size_t)n);
   double ms[3] = {0, 0, 0};
-  int chunks, launches = 0;
+  int chunks;
+  BandBatch ops;
   auto row_bytes = [S](int L) { return (size_t)SF_BANDED_BYTES(L, std::min(S, L)); };
   rc = long_for_chunks(R, row_bytes, db_out, &chunks, [&](int s0, int m, char *db_host) {
-    return band_batch_chunk(R, S, s0, m, e_host.data(), db_host, ms, &launches);
+    return fold_rows(R, s0, m, ops, e_host.data(), db_host, ms);
   }, 64);
   if (rc) return rc;  // (n == 0: no chunk)
   if (n) memcpy(mfe_out, e_host.data(), (size_t)n * sizeof(int32_t));
   for (int k = 0; k < 3; k++) g_bandb_ms[k] = ms[k];
   g_bandb_chunks = chunks;
-  g_bandb_launches = launches;
+  g_bandb_launches = ops.launches;
   return SF_OK;
 }
 

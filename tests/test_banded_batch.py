@@ -1,8 +1,9 @@
 """Many whole-record folds under a base-pair span at once (sf_fold_banded_batch, include/scanfold_hip_long.h) on the CPU build of
 the kernel sources: against the oracle on records whose band is live up to its last diagonal, against sf_fold_banded row by
 row in a ragged call (rows shorter than the band, rows that drop out of early diagonals, constraints, a type-7 pair), in
-reversed order, chunked by the byte budget and energies only, always with == on energy and structure; bad arguments; and the
-combined driver's --global_zscore_span.
+reversed order, chunked by the byte budget and energies only, always with == on energy and structure; bad arguments; what the
+one host driver of the four MFE entry points promises (a single call is one chunk under any budget, the four time records stay
+apart, dots are no constraint and a one-row batch is the single call); and the combined driver's --global_zscore_span.
 
 The checks are shared with test_gpu_banded_batch.py, which runs them on the MI355X over more spans, longer rows, other
 parameter sets and records past 32 767 nt.  Record builders and the `model` context come from test_banded_fold.py."""
@@ -180,6 +181,71 @@ def check_errors(engine):
         engine.set_max_bp_span(0)
 
 
+DRIVER_SPAN = 40  # the span of the checks below, which hold the four MFE entry points to what their one host driver promises
+
+
+def driver_rows():
+    """seeded rows of 57, 120, 150 and 433 nt"""
+    return [rand_seq(np.random.default_rng(100 + L), L) for L in (57, 120, 150, 433)]
+
+
+def check_single_is_one_chunk(engine):
+    """fold_banded is one chunk under any byte budget: the 433-nt row folds to the same tuple under a budget of one byte,
+    under which a batch of five 57-nt rows runs as five chunks"""
+    s = driver_rows()[3]
+    engine.set_max_bp_span(DRIVER_SPAN)
+    try:
+        ref = engine.fold_banded(s)
+        try:
+            engine.set_long_batch_bytes(1)
+            assert engine.fold_banded(s) == ref
+            rows = [rand_seq(np.random.default_rng(k), 57) for k in range(5)]
+            engine.fold_banded_batch(rows)
+            assert engine.fold_banded_batch_times()["chunks"] == 5
+        finally:
+            engine.set_long_batch_bytes(0)
+    finally:
+        engine.set_max_bp_span(0)
+
+
+def check_time_records_stay_apart(engine):
+    """every entry point's time record is left alone by the other family's calls and by its own family's other call"""
+    rows = driver_rows()
+    engine.set_max_bp_span(DRIVER_SPAN)
+    try:
+        engine.fold_banded_batch(rows, structure=True)
+        t = engine.fold_banded_batch_times()
+        assert t["chunks"] == 1 and t["fill_launches"] == DRIVER_SPAN
+        engine.fold_banded(rows[3])
+        t_single = engine.fold_banded_times()
+        assert t_single["band"] == DRIVER_SPAN and t_single["fill_launches"] == DRIVER_SPAN
+        engine.fold_long(rows[2])
+        assert engine.fold_banded_batch_times() == t  # after a fold_banded and a fold_long
+        engine.fold_long_batch(rows, structure=True)
+        t_long, t_long_batch = engine.fold_long_times(), engine.fold_long_batch_times()
+        engine.fold_banded_batch(rows, structure=True)
+        assert engine.fold_banded_times() == t_single  # after a fold_long_batch and a fold_banded_batch
+        engine.fold_banded(rows[1])
+        assert engine.fold_long_times() == t_long  # after both banded calls
+        assert engine.fold_long_batch_times() == t_long_batch
+    finally:
+        engine.set_max_bp_span(0)
+
+
+def check_dots_and_one_row_batches(engine, oracle):
+    """a constraint of dots is no constraint for fold_banded, and a batch of that one row, with dots and with the structure,
+    gives the single call's energy and string; rows of 1 and 4 nt give the oracle's under the span"""
+    with tb.model(engine, oracle, None, DRIVER_SPAN):
+        for s in driver_rows() + [rand_seq(np.random.default_rng(100 + L), L) for L in (1, 4)]:
+            L = len(s)
+            ref = engine.fold_banded(s)
+            if L <= 4:
+                assert ref == oracle.mfe(s)[::-1]
+            assert engine.fold_banded(s, "." * L) == ref
+            e, db = engine.fold_banded_batch([s], ["." * L], structure=True)
+            assert e.shape == (1,) and (int(e[0]), db[0]) == ref
+
+
 def expected_zscore_span_file(energy_dcal, seq, name, r, kind, seed, span):
     """<outname>.global_zscore.txt of --global_zscore_span from the generator draws of --seed and energy_dcal(sequence), the
     fold under the span: GLOBAL_ZSCORE_HEADER's columns and a trailing Span"""
@@ -269,6 +335,18 @@ def test_ragged_call_equals_fold_banded(emul):
 
 def test_errors(emul):
     check_errors(emul)
+
+
+def test_single_call_is_one_chunk_under_any_budget(emul):
+    check_single_is_one_chunk(emul)
+
+
+def test_time_records_stay_apart(emul):
+    check_time_records_stay_apart(emul)
+
+
+def test_dots_and_one_row_batches(emul, oracle):
+    check_dots_and_one_row_batches(emul, oracle)
 
 
 def test_combined_driver_global_zscore_span(emul, oracle, tmp_path, monkeypatch):

@@ -1,8 +1,8 @@
 """Many whole-record folds under a base-pair span at once (sf_fold_banded_batch) on the MI355X: the checks of
 test_banded_batch.py over the full list of spans at 433 and 1 200 nt, the ragged call at spans 64 and 401 with a 3 000-nt row
 and under other parameter sets, a record and its shuffles against a loop of sf_fold_banded, rows of 40 000 nt (bracket
-partners past 32 767) against the oracle's block-wise answer, and the combined driver's --global_zscore_span at 450 and at
-40 000 nt.  Always == on energy and structure."""
+partners past 32 767) against the oracle's block-wise answer, the promises of the four MFE entry points' one host driver, and
+the combined driver's --global_zscore_span at 450 and at 40 000 nt.  Always == on energy and structure."""
 import os
 import random
 
@@ -108,6 +108,18 @@ def test_rows_past_the_old_limit(gpu_engine, oracle):
 
 def test_errors(gpu_engine):
     tbb.check_errors(gpu_engine)
+
+
+def test_single_call_is_one_chunk_under_any_budget(gpu_engine):
+    tbb.check_single_is_one_chunk(gpu_engine)
+
+
+def test_time_records_stay_apart(gpu_engine):
+    tbb.check_time_records_stay_apart(gpu_engine)
+
+
+def test_dots_and_one_row_batches(gpu_engine, oracle):
+    tbb.check_dots_and_one_row_batches(gpu_engine, oracle)
 
 
 def test_combined_driver_global_zscore_span(gpu_engine, oracle, tmp_path, monkeypatch):
