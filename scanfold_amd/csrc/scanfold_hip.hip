@@ -274,24 +274,48 @@ static int pf_redo_flagged(const uint8_t *d_seqs, int n, int row_stride, int W, 
   return SF_OK;
 }
 
+// Which kernel folds the ensembles of a batch of windows, and the shape of its launch: the one place that decides it (the
+// table of DESIGN.md §4).  No HIP call in here.
+enum PfKernel { PF_GENERAL, PF_LDS, PF_TABLES };  // sf_pf_kernel<false>, sf_pf_lds_kernel, sf_pf_fast_kernel
+struct PfRoute {
+  PfKernel kernel;
+  int grid_cap, block;
+  size_t scratch_doubles;  // of g.pf_scratch, per workgroup
+};
+static PfRoute pf_route(int W, bool constrained, bool type7, int force_full, int pf_kernel) {
+  if (!force_full && !type7) {
+    // every table of a fold in the LDS of one CU: one workgroup per CU
+    if (pf_kernel == 0 && sf_pfl_supported(W) && (!constrained || sf_pfl_lds_bytes(W, true) <= SF_PFL_LDS_LIMIT))
+      return {PF_LDS, g.n_cu, SF_PFL_NT, 0};
+    if (W >= 16 && W <= (constrained ? SF_PFF_HC_MAXW : SF_PFF_MAXW))
+      return {PF_TABLES, g.n_cu * pf_fast_blocks_per_cu(W), sf_pff_threads(W), SF_PFF_SCRATCH_DOUBLES(W)};
+  }
+  return {PF_GENERAL, max_resident_blocks(), block_threads(W), SF_PF_SCRATCH_DOUBLES(W)};
+}
+
+// The only caller of the windowed partition-function kernels.  d_cons: a constraint row per fold (sf_fold_constrained), type7:
+// some row has a bracket pair of non-complementary bases.
 // d_tr != null: the n rows are the native windows of transcript d_tr (length L) that start at win0, win0+1, ...
 // (sf_scan with step 1): consecutive windows share their inside tables (sf_pf_lds.hip.h).  A flagged window keeps its
 // place in the run: the tables it hands on hold the same (unscaled) values as its neighbours' own folds would, and only
 // its own outputs are redone.
 int launch_pf(const uint8_t *d_seqs, int n, int row_stride, int W, double *d_dG, double *d_mbd, char *d_cen,
-              double *d_cd, hipStream_t st, const uint8_t *d_tr = nullptr, int L = 0, int win0 = 0, int step = 1) {
+              double *d_cd, hipStream_t st, const char *d_cons = nullptr, bool type7 = false, const uint8_t *d_tr = nullptr,
+              int L = 0, int win0 = 0, int step = 1) {
   if (n <= 0) return SF_OK;
-  int grid = n < max_resident_blocks() ? n : max_resident_blocks();
-  int *d_flag = nullptr;
-  if (sf_pfl_supported(W) && !g.force_full && g.pf_kernel == 0) {
-    int rc = pf_begin(n, W, 0, st);
-    if (rc) return rc;
-    d_flag = (int *)g.pf_flag.p;
-    // every table of a fold in the LDS of one CU: one workgroup per CU
-    grid = n < g.n_cu ? n : g.n_cu;
+  const PfRoute r = pf_route(W, d_cons != nullptr, type7, g.force_full, g.pf_kernel);
+  int grid = n < r.grid_cap ? n : r.grid_cap;
+  int rc = pf_begin(n, W, (size_t)grid * r.scratch_doubles * sizeof(double), st);
+  if (rc) return rc;
+  const SfDevParams *dP = g.dP;
+  const SfDevParamsPF *dX = g.dX;
+  double *scratch = (double *)g.pf_scratch.p;
+  int *d_status = d_cons ? (int *)g.status.p : nullptr, *d_flag = (int *)g.pf_flag.p;
+  bool started = true;
+  if (r.kernel == PF_LDS) {
     int run_len = 1;
     double *share = nullptr;
-    if (d_tr && g.pf_share_inside && n >= 2 && step >= 1 && step <= W / 4) {
+    if (!d_cons && d_tr && g.pf_share_inside && n >= 2 && step >= 1 && step <= W / 4) {
       // run length: the makespan of ceil(runs / CUs) runs per workgroup; a resumed window costs the outside pass
       // (~0.6 of a full fold) plus its share of the inside pass
       const double resumed = 0.6 + 0.4 * step / (double)(W - 4);
@@ -303,30 +327,25 @@ int launch_pf(const uint8_t *d_seqs, int n, int row_stride, int W, double *d_dG,
       }
       if (run_len > 1) {
         grid = (n + run_len - 1) / run_len < g.n_cu ? (n + run_len - 1) / run_len : g.n_cu;
-        int rc = ensure(g.pf_share, (size_t)((grid + 7) & ~7) * SF_PFL_SHARE_DOUBLES(W) * sizeof(double));  // whole groups of eight slices: see sv in the kernel
+        rc = ensure(g.pf_share, (size_t)((grid + 7) & ~7) * SF_PFL_SHARE_DOUBLES(W) * sizeof(double));  // whole groups of eight slices: see sv in the kernel
         if (rc) return rc;
         share = (double *)g.pf_share.p;
       }
     }
-    sf_pf_lds_launch(grid, W, share != nullptr, st, d_seqs, n, row_stride, W, (const SfDevParams *)g.dP, (const SfDevParamsPF *)g.dX,
-                     d_dG, d_mbd, d_cen, d_cd, d_tr, L, win0, step, run_len, share, (const char *)nullptr, (int *)nullptr, d_flag);
-  } else if (W >= 16 && W <= SF_PFF_MAXW && !g.force_full) {
-    const int pf_blocks = g.n_cu * pf_fast_blocks_per_cu(W);
-    grid = n < pf_blocks ? n : pf_blocks;
-    int rc = pf_begin(n, W, (size_t)grid * SF_PFF_SCRATCH_DOUBLES(W) * sizeof(double), st);
-    if (rc) return rc;
-    d_flag = (int *)g.pf_flag.p;
-    sf_pf_fast_launch(grid, W, st, d_flag, d_seqs, n, row_stride, W, (const SfDevParams *)g.dP, (const SfDevParamsPF *)g.dX,
-                      (double *)g.pf_scratch.p, d_dG, d_mbd, d_cen, d_cd);
+    started = sf_pf_lds_launch(d_cons != nullptr, share != nullptr, grid, r.block, W, st, d_seqs, n, row_stride, W, dP, dX,
+                               d_dG, d_mbd, d_cen, d_cd, d_tr, L, win0, step, run_len, share, d_cons, d_status, d_flag);
+  } else if (r.kernel == PF_TABLES) {
+    started = sf_pf_fast_launch(d_cons != nullptr, grid, r.block, W, st, d_seqs, n, row_stride, W, dP, dX, scratch, d_dG,
+                                d_mbd, d_cen, d_cd, d_cons, d_status, d_flag);
   } else {
-    int rc = pf_begin(n, W, (size_t)grid * SF_PF_SCRATCH_DOUBLES(W) * sizeof(double), st);
-    if (rc) return rc;
-    d_flag = (int *)g.pf_flag.p;
-    SF_LAUNCH((sf_pf_kernel<false>), grid, block_threads(W), 0, st, d_seqs, n, row_stride, W, (const SfDevParams *)g.dP,
-              (const SfDevParamsPF *)g.dX, (double *)g.pf_scratch.p, d_dG, d_mbd, d_cen, d_cd, (const char *)nullptr,
-              (int *)nullptr, d_flag);
+    SF_LAUNCH((sf_pf_kernel<false>), grid, r.block, 0, st, d_seqs, n, row_stride, W, dP, dX, scratch, d_dG, d_mbd, d_cen,
+              d_cd, d_cons, d_status, d_flag);
   }
-  return pf_redo_flagged(d_seqs, n, row_stride, W, d_dG, d_mbd, d_cen, d_cd, (const char *)nullptr, st);
+  if (!started) {
+    g.last_hip_error = "launch_pf: no instantiation of the partition-function kernel for this batch";
+    return SF_ERR_HIP;
+  }
+  return pf_redo_flagged(d_seqs, n, row_stride, W, d_dG, d_mbd, d_cen, d_cd, d_cons, st);
 }
 
 // energies of n rows: LDS-resident int16 kernel, then the exact int32 kernel on the rows it flagged.
@@ -397,15 +416,24 @@ static int mfe_poison() {
   return v;
 }
 
+// Which kernel folds a batch of windows: the LDS-resident int16 kernel (with the exact int32 kernel behind it, on the folds it
+// flags) or the int32 kernel alone.  The one place that decides it; no HIP call in here.
+enum MfeKernel { MFE_GENERAL, MFE_LDS };  // sf_mfe_full_kernel, sf_mfe_fast_kernel
+static MfeKernel mfe_route(int W, bool constrained, bool type7, int trace_stride, int force_full, int fast_ok) {
+  if (force_full || !fast_ok || type7 || !sf_fast_w_supported(W)) return MFE_GENERAL;
+  if (constrained && (W > 250 || trace_stride != 1)) return MFE_GENERAL;  // (the HC instantiations: W <= 250, every fold traced)
+  return MFE_LDS;
+}
+
 // d_cons / d_sc: every fold has its own hard constraint / Deigan pseudo-energies (row k of each; trace_stride 1): the
-// constrained native windows of sf_fold_constrained, on the LDS kernel where it applies (W <= 250), else the general one
+// constrained native windows of sf_fold_constrained; type7: some row has a bracket pair of non-complementary bases
 int launch_mfe(const uint8_t *d_seqs, int n, int W, int32_t *d_out, hipStream_t st, int trace_stride = 1,
-               char *d_db = nullptr, const char *d_cons = nullptr, const int32_t *d_sc = nullptr) {
+               char *d_db = nullptr, const char *d_cons = nullptr, const int32_t *d_sc = nullptr, bool type7 = false) {
   if (n <= 0) return SF_OK;
   ProfPair prof;
   int rc = SF_OK;
   const bool hc = d_cons || d_sc;
-  if (g.force_full || !g.fast_ok || !sf_fast_w_supported(W) || (hc && (W > 250 || trace_stride != 1))) {
+  if (mfe_route(W, hc, type7, trace_stride, g.force_full, g.fast_ok) == MFE_GENERAL) {
     if ((rc = prof.begin(st))) return rc;
     rc = launch_full(d_seqs, nullptr, nullptr, n, 1, 1, W, d_out, d_db, d_db ? trace_stride : 0, st, d_cons, d_sc);
     if (rc) return rc;
@@ -457,6 +485,17 @@ int launch_mfe(const uint8_t *d_seqs, int n, int W, int32_t *d_out, hipStream_t 
     g.prof_folds += n;
   }
   return rc;
+}
+
+// The four partition-function results of n windows (d_dG, then mean bp distance and centroid distance behind it in g.dbl;
+// centroids in g.cen) to the caller's arrays, those it asked for.
+int pf_results_to_host(int n, int W, double *ens_dG, double *mbd, char *centroid, double *cdist) {
+  const double *d_dG = (const double *)g.dbl.p, *d_mbd = d_dG + n, *d_cd = d_mbd + n;
+  if (ens_dG) HIPCHK(hipMemcpyAsync(ens_dG, d_dG, n * sizeof(double), hipMemcpyDeviceToHost, g.stream));
+  if (mbd) HIPCHK(hipMemcpyAsync(mbd, d_mbd, n * sizeof(double), hipMemcpyDeviceToHost, g.stream));
+  if (cdist) HIPCHK(hipMemcpyAsync(cdist, d_cd, n * sizeof(double), hipMemcpyDeviceToHost, g.stream));
+  if (centroid) HIPCHK(hipMemcpyAsync(centroid, g.cen.p, (size_t)n * (W + 1), hipMemcpyDeviceToHost, g.stream));
+  return SF_OK;
 }
 
 // Read the sticky traceback status word after everything queued on `st` (nullptr: the whole device) has finished,
@@ -698,10 +737,7 @@ int sf_pf_batch(const uint8_t *seqs, int n, int W, double *ens_dG, double *mbd, 
   double *d_dG = (double *)g.dbl.p, *d_mbd = d_dG + n, *d_cd = d_mbd + n;
   HIPCHK(hipMemcpyAsync(g.seqs.p, seqs, (size_t)n * W, hipMemcpyHostToDevice, g.stream));
   if ((rc = launch_pf((const uint8_t *)g.seqs.p, n, 1, W, d_dG, d_mbd, (char *)g.cen.p, d_cd, g.stream))) return rc;
-  if (ens_dG) HIPCHK(hipMemcpyAsync(ens_dG, d_dG, n * sizeof(double), hipMemcpyDeviceToHost, g.stream));
-  if (mbd) HIPCHK(hipMemcpyAsync(mbd, d_mbd, n * sizeof(double), hipMemcpyDeviceToHost, g.stream));
-  if (cdist) HIPCHK(hipMemcpyAsync(cdist, d_cd, n * sizeof(double), hipMemcpyDeviceToHost, g.stream));
-  if (centroid) HIPCHK(hipMemcpyAsync(centroid, g.cen.p, (size_t)n * (W + 1), hipMemcpyDeviceToHost, g.stream));
+  if ((rc = pf_results_to_host(n, W, ens_dG, mbd, centroid, cdist))) return rc;
   HIPCHK(hipStreamSynchronize(g.stream));
   return SF_OK;
 }
@@ -762,54 +798,21 @@ int sf_fold_constrained(const uint8_t *seqs, int n, int W, const char *cons, con
   if (want_mfe) {
     if ((rc = ensure(g.energies, (size_t)n * sizeof(int32_t)))) return rc;
     if ((rc = ensure(g.db, (size_t)n * (W + 1)))) return rc;
-    // (the LDS kernel with the per-fold constraint where it applies; every fold traced: the structure is the point)
-    if (noncanonical || !(d_cons || d_sc))
-      rc = (d_cons || d_sc) ? launch_full((const uint8_t *)g.seqs.p, nullptr, nullptr, n, 1, 1, W, (int32_t *)g.energies.p,
-                                          (char *)g.db.p, 0, g.stream, d_cons, d_sc)
-                            : launch_mfe((const uint8_t *)g.seqs.p, n, W, (int32_t *)g.energies.p, g.stream, 1, (char *)g.db.p);
-    else
-      rc = launch_mfe((const uint8_t *)g.seqs.p, n, W, (int32_t *)g.energies.p, g.stream, 1, (char *)g.db.p, d_cons, d_sc);
+    // (every fold traced: the structure is the point)
+    rc = launch_mfe((const uint8_t *)g.seqs.p, n, W, (int32_t *)g.energies.p, g.stream, 1, (char *)g.db.p, d_cons, d_sc, noncanonical);
     if (rc) return rc;
     if (mfe_out)
       HIPCHK(hipMemcpyAsync(mfe_out, g.energies.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, g.stream));
     if (db_out) HIPCHK(hipMemcpyAsync(db_out, g.db.p, (size_t)n * (W + 1), hipMemcpyDeviceToHost, g.stream));
   }
   if (want_pf) {
-    int grid = n < max_resident_blocks() ? n : max_resident_blocks();
     if ((rc = ensure(g.dbl, (size_t)n * 3 * sizeof(double)))) return rc;
     if ((rc = ensure(g.cen, (size_t)n * (W + 1)))) return rc;
     double *d_dG = (double *)g.dbl.p, *d_mbd = d_dG + n, *d_cd = d_mbd + n;
-    if (!d_cons) {  // (SHAPE data alone do not touch the partition function: the plain kernels)
-      if ((rc = launch_pf((const uint8_t *)g.seqs.p, n, 1, W, d_dG, d_mbd, (char *)g.cen.p, d_cd, g.stream))) return rc;
-    } else if (!noncanonical && !g.force_full && g.pf_kernel == 0 && sf_pfl_supported(W) &&
-               sf_pfl_lds_bytes(W, true) <= SF_PFL_LDS_LIMIT) {
-      grid = n < g.n_cu ? n : g.n_cu;  // every table of a fold in the LDS of one CU
-      if ((rc = pf_begin(n, W, 0, g.stream))) return rc;
-      sf_pf_lds_launch_hc(grid, W, g.stream, (const uint8_t *)g.seqs.p, n, 1, W, (const SfDevParams *)g.dP,
-                          (const SfDevParamsPF *)g.dX, d_dG, d_mbd, (char *)g.cen.p, d_cd, (const uint8_t *)nullptr, 0, 0, 1, 1,
-                          (double *)nullptr, d_cons, (int *)g.status.p, (int *)g.pf_flag.p);
-      if ((rc = pf_redo_flagged((const uint8_t *)g.seqs.p, n, 1, W, d_dG, d_mbd, (char *)g.cen.p, d_cd, d_cons, g.stream))) return rc;
-    } else if (!noncanonical && !g.force_full && W >= 16 && W <= SF_PFF_HC_MAXW) {
-      // the constrained instantiation of the device-table kernel (120 < W <= 250, or SCANFOLD_PF_KERNEL=global)
-      const int pf_blocks = g.n_cu * pf_fast_blocks_per_cu(W);
-      grid = n < pf_blocks ? n : pf_blocks;
-      if ((rc = pf_begin(n, W, (size_t)grid * SF_PFF_SCRATCH_DOUBLES(W) * sizeof(double), g.stream))) return rc;
-      sf_pf_fast_launch_hc(grid, W, g.stream, (const uint8_t *)g.seqs.p, n, 1, W, (const SfDevParams *)g.dP,
-                           (const SfDevParamsPF *)g.dX, (double *)g.pf_scratch.p, d_dG, d_mbd, (char *)g.cen.p, d_cd, d_cons,
-                           (int *)g.status.p, (int *)g.pf_flag.p);
-      if ((rc = pf_redo_flagged((const uint8_t *)g.seqs.p, n, 1, W, d_dG, d_mbd, (char *)g.cen.p, d_cd, d_cons, g.stream))) return rc;
-    } else {
-      if ((rc = pf_begin(n, W, (size_t)grid * SF_PF_SCRATCH_DOUBLES(W) * sizeof(double), g.stream))) return rc;
-      SF_LAUNCH((sf_pf_kernel<false>), grid, block_threads(W), 0, g.stream, (const uint8_t *)g.seqs.p, n, 1, W,
-                (const SfDevParams *)g.dP, (const SfDevParamsPF *)g.dX, (double *)g.pf_scratch.p, d_dG, d_mbd,
-                (char *)g.cen.p, d_cd, d_cons, (int *)g.status.p, (int *)g.pf_flag.p);
-      if ((rc = pf_redo_flagged((const uint8_t *)g.seqs.p, n, 1, W, d_dG, d_mbd, (char *)g.cen.p, d_cd, d_cons, g.stream))) return rc;
-    }
-    HIPCHK(hipGetLastError());
-    if (ens_dG) HIPCHK(hipMemcpyAsync(ens_dG, d_dG, n * sizeof(double), hipMemcpyDeviceToHost, g.stream));
-    if (mbd) HIPCHK(hipMemcpyAsync(mbd, d_mbd, n * sizeof(double), hipMemcpyDeviceToHost, g.stream));
-    if (cdist) HIPCHK(hipMemcpyAsync(cdist, d_cd, n * sizeof(double), hipMemcpyDeviceToHost, g.stream));
-    if (centroid) HIPCHK(hipMemcpyAsync(centroid, g.cen.p, (size_t)n * (W + 1), hipMemcpyDeviceToHost, g.stream));
+    // (SHAPE data alone do not touch the partition function: without constraint rows these are plain folds)
+    if ((rc = launch_pf((const uint8_t *)g.seqs.p, n, 1, W, d_dG, d_mbd, (char *)g.cen.p, d_cd, g.stream, d_cons, noncanonical)))
+      return rc;
+    if ((rc = pf_results_to_host(n, W, ens_dG, mbd, centroid, cdist))) return rc;
   }
   return read_status(g.stream, false);
 }
@@ -826,8 +829,7 @@ static int launch_shuffle(const uint8_t *d_tr, int L, int W, int step, int win_b
   const long long total = (long long)n_win * (r + 1);
   if (total <= 0) return SF_OK;
   const int grid = (int)((total + SF_SHUF_BLOCK - 1) / SF_SHUF_BLOCK);
-  const size_t lds = (((size_t)SF_SHUF_BLOCK * W + 3) & ~(size_t)3) * 2 + SF_SHUF_BLOCK * 25 * sizeof(uint16_t);
-  SF_LAUNCH(sf_shuffle_kernel, grid, SF_SHUF_BLOCK, lds, st, d_tr, L, W, step, win_begin, n_win, r, kind, seed, d_seqs);
+  SF_LAUNCH(sf_shuffle_kernel, grid, SF_SHUF_BLOCK, sf_shuffle_lds_bytes(W), st, d_tr, L, W, step, win_begin, n_win, r, kind, seed, d_seqs);
   HIPCHK(hipGetLastError());
   return SF_OK;
 }
@@ -875,7 +877,7 @@ int sf_scan_dev(const uint8_t *d_tr, int L, int W, int step, int win_begin, int 
     if ((rc = launch_mfe(d_seqs, nw * (r + 1), W, d_energies + (size_t)w0 * (r + 1), st, r + 1, dbp))) return rc;
     if (!(flags & SF_SCAN_NO_PF)) {
       if ((rc = launch_pf(d_seqs, nw, r + 1, W, d_ens_dG ? d_ens_dG + w0 : nullptr, d_ens_div ? d_ens_div + w0 : nullptr,
-                          d_centroid ? d_centroid + (size_t)w0 * (W + 1) : nullptr, nullptr, st,
+                          d_centroid ? d_centroid + (size_t)w0 * (W + 1) : nullptr, nullptr, st, nullptr, false,
                           d_tr, L, win_begin + w0, step)))
         return rc;
     }
@@ -1073,21 +1075,26 @@ int sf_prof_stop(void) {
 namespace {
 double g_long_ms[3] = {0, 0, 0};  // fill, f5, traceback of the last sf_fold_long
 
-// Every device buffer of one long fold; all freed when it goes out of scope (after the stream has drained).
-struct LongBufs {
+// Every device buffer (and timing event) of one call of a whole-record fold, a duplex batch or the LRI scan; all freed when it
+// goes out of scope (after the stream has drained).
+struct CallBufs {
   std::vector<void *> ptrs;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  const char *who = "sf_fold_long";  // the entry point named in an out-of-memory text
-  ~LongBufs() {
+  const char *who;  // the entry point named in an out-of-memory text
+  explicit CallBufs(const char *who_) : who(who_) {}
+  ~CallBufs() {
     hipStreamSynchronize(g.stream);
     for (void *p : ptrs) hipFree(p);
     for (hipEvent_t e : ev)
       if (e) hipEventDestroy(e);
   }
-  // hipMalloc that reports (and clears) an out-of-memory instead of leaving it for the next call's hipGetLastError
-  int alloc(void **p, size_t bytes, const char *what) {
-    *p = nullptr;
-    const hipError_t e = hipMalloc(p, bytes ? bytes : 1);
+  // hipMalloc of `count` T that reports (and clears) an out-of-memory instead of leaving it for the next call's hipGetLastError
+  template <class T>
+  int alloc(T **p, size_t count, const char *what) {
+    const size_t bytes = count * sizeof(T);
+    void *v = nullptr;
+    const hipError_t e = hipMalloc(&v, bytes ? bytes : 1);
+    *p = (T *)v;
     if (e != hipSuccess) {
       hipGetLastError();
       char b[512];
@@ -1096,7 +1103,15 @@ struct LongBufs {
       *p = nullptr;
       return SF_ERR_HIP;
     }
-    ptrs.push_back(*p);
+    ptrs.push_back(v);
+    return SF_OK;
+  }
+  // alloc, and the copy of h[0 .. count) into it on g.stream
+  template <class T>
+  int upload(T **d, const T *h, size_t count, const char *what) {
+    const int rc = alloc(d, count, what);
+    if (rc) return rc;
+    if (count) HIPCHK(hipMemcpyAsync(*d, h, count * sizeof(T), hipMemcpyHostToDevice, g.stream));
     return SF_OK;
   }
 };
@@ -1237,13 +1252,11 @@ void long_parse_hc(SfHc &hc, const char *src, int L, char *c, int16_t *i16) {
 // Clears the chunk's row states (SfLong or SfPfLong) and sets what both have: L, S and hc.  Copies the packed bytes to
 // d_u8, allocates the int16 block of the constrained rows (3 (L + 2) each) and parses each of them on the device.
 template <class State>
-int long_bind_rows(LongBufs &B, const LongPack &K, const LongRows &R, int s0, uint8_t *d_u8, std::vector<State> &hF) {
+int long_bind_rows(CallBufs &B, const LongPack &K, const LongRows &R, int s0, uint8_t *d_u8, std::vector<State> &hF) {
   int16_t *d_i16 = nullptr;
   if (K.n_hc) {
-    void *p;
-    const int rc = B.alloc(&p, 3 * (K.n_hcL + 2 * (size_t)K.n_hc) * sizeof(int16_t), "bracket partners");
+    const int rc = B.alloc(&d_i16, 3 * (K.n_hcL + 2 * (size_t)K.n_hc), "bracket partners");
     if (rc) return rc;
-    d_i16 = (int16_t *)p;
   }
   HIPCHK(hipMemcpyAsync(d_u8, K.h8.data(), K.h8.size(), hipMemcpyHostToDevice, g.stream));
   size_t a_L = 0, a_hcL = 0;
@@ -1303,27 +1316,18 @@ int fold_rows(const LongRows &R, int s0, int n, Ops &ops, int32_t *e_host, char 
   const size_t o_db = K.o_end, n_u8 = o_db + (trace ? n_L + (size_t)n : 0);
   std::vector<State> hF((size_t)n);
 
-  LongBufs B;
-  B.who = R.who;
-  void *p;
+  CallBufs B(R.who);
   int32_t *d_tab[3], *d_dml, *d_i32;
   uint8_t *d_u8;
-  const State *F = hF.data();
+  State *d_F = nullptr;
   static const char *const names[3] = {"c", "fML", "fML transposed"};
-  for (int k = 0; k < 3; k++) {
-    if ((rc = B.alloc(&p, cells * sizeof(int32_t), names[k]))) return rc;
-    d_tab[k] = (int32_t *)p;
-  }
-  if ((rc = B.alloc(&p, 3 * (n_L + 2 * (size_t)n) * sizeof(int32_t), "DML rings"))) return rc;
-  d_dml = (int32_t *)p;
-  if ((rc = B.alloc(&p, n_i32 * sizeof(int32_t), "hairpin table, energies, f5, traceback stacks"))) return rc;
-  d_i32 = (int32_t *)p;
-  if ((rc = B.alloc(&p, n_u8, "sequences, constraints, structures"))) return rc;
-  d_u8 = (uint8_t *)p;
-  if (!Ops::by_value) {
-    if ((rc = B.alloc(&p, (size_t)n * sizeof(State), "fold states"))) return rc;
-    F = (const State *)p;
-  }
+  for (int k = 0; k < 3; k++)
+    if ((rc = B.alloc(&d_tab[k], cells, names[k]))) return rc;
+  if ((rc = B.alloc(&d_dml, 3 * (n_L + 2 * (size_t)n), "DML rings"))) return rc;
+  if ((rc = B.alloc(&d_i32, n_i32, "hairpin table, energies, f5, traceback stacks"))) return rc;
+  if ((rc = B.alloc(&d_u8, n_u8, "sequences, constraints, structures"))) return rc;
+  if (!Ops::by_value && (rc = B.alloc(&d_F, (size_t)n, "fold states"))) return rc;
+  const State *F = Ops::by_value ? hF.data() : d_F;
   if ((rc = ops.bind(B, K, R, s0, d_u8, hF))) return rc;
 
   size_t a_cells = 0, a_L = 0, a_stk = 0;
@@ -1398,7 +1402,7 @@ struct TriRows {
   static const bool host_hc = false;
   size_t entries(int L) const { return SF_LONG_TRI(L); }
   int hairpin_entries(int Lmax) const { return Lmax; }
-  int bind(LongBufs &B, const LongPack &K, const LongRows &R, int s0, uint8_t *d_u8, std::vector<SfLong> &hF) {
+  int bind(CallBufs &B, const LongPack &K, const LongRows &R, int s0, uint8_t *d_u8, std::vector<SfLong> &hF) {
     return long_bind_rows(B, K, R, s0, d_u8, hF);
   }
 };
@@ -1487,19 +1491,17 @@ struct BandHc {
     return stack.empty() ? SF_OK : SF_ERR_CONSTRAINT;
   }
   // uploads the three arrays (9 (L + 2) bytes) into allocations of Bf and binds them
-  int bind(LongBufs &Bf, SfHc32 &hc) const {
+  int bind(CallBufs &Bf, SfHc32 &hc) const {
     int rc;
-    void *dc, *dp, *de;
+    char *dc;
+    int32_t *dp, *de;
     const size_t n = c.size();
-    if ((rc = Bf.alloc(&dc, n, "constraint"))) return rc;
-    if ((rc = Bf.alloc(&dp, n * sizeof(int32_t), "bracket partners"))) return rc;
-    if ((rc = Bf.alloc(&de, n * sizeof(int32_t), "enclosing pairs"))) return rc;
-    HIPCHK(hipMemcpyAsync(dc, c.data(), n, hipMemcpyHostToDevice, g.stream));
-    HIPCHK(hipMemcpyAsync(dp, part.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, g.stream));
-    HIPCHK(hipMemcpyAsync(de, encl.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, g.stream));
-    hc.c = (const char *)dc;
-    hc.partner = (const int32_t *)dp;
-    hc.encl = (const int32_t *)de;
+    if ((rc = Bf.upload(&dc, c.data(), n, "constraint")) || (rc = Bf.upload(&dp, part.data(), n, "bracket partners")) ||
+        (rc = Bf.upload(&de, encl.data(), n, "enclosing pairs")))
+      return rc;
+    hc.c = dc;
+    hc.partner = dp;
+    hc.encl = de;
     return SF_OK;
   }
 };
@@ -1515,14 +1517,14 @@ struct BandRows {
   std::vector<char> h8;
   size_t entries(int L) const { return (size_t)L * (size_t)std::min(S, L); }
   int hairpin_entries(int Lmax) const { return std::min(S, Lmax); }
-  int bind(LongBufs &B, const LongPack &K, const LongRows &R, int s0, uint8_t *d_u8, std::vector<SfBand> &hF) {
+  int bind(CallBufs &B, const LongPack &K, const LongRows &R, int s0, uint8_t *d_u8, std::vector<SfBand> &hF) {
     int rc;
     size_t n_hc = 0, a_L = 0, a = 0;
     for (size_t k = 0; k < hF.size(); k++)
       if (R.constrained[s0 + k]) n_hc += (size_t)R.len[s0 + k] + 2;
     h32.assign(2 * n_hc, 0);
     h8.assign(n_hc, 0);
-    void *p = nullptr;
+    char *p = nullptr;
     if (n_hc && (rc = B.alloc(&p, 9 * n_hc, "bracket partners, enclosing pairs, constraints"))) return rc;
     const int32_t *d_part = (const int32_t *)p, *d_encl = d_part + n_hc;
     const char *d_c = (const char *)(d_encl + n_hc);
@@ -1835,19 +1837,13 @@ int pf_long_rows(const LongRows &R, const int32_t *hint, int s0, int n, Launch &
   std::vector<SfPfLong> hF((size_t)n);
   std::vector<char> hcen(n_L + (size_t)n);
 
-  LongBufs B;
-  B.who = R.who;
-  void *p;
+  CallBufs B(R.who);
   double *d_tri[SF_PFLONG_NTRI], *d_f64;
   uint8_t *d_u8;
-  for (int k = 0; k < SF_PFLONG_NTRI; k++) {
-    if ((rc = B.alloc(&p, tri * sizeof(double), kPfTableNames[k]))) return rc;
-    d_tri[k] = (double *)p;
-  }
-  if ((rc = B.alloc(&p, n_f64 * sizeof(double), "results, scale powers, hairpin weights, q5, q3, partial sums"))) return rc;
-  d_f64 = (double *)p;
-  if ((rc = B.alloc(&p, n_u8, "sequences, constraints, centroids"))) return rc;
-  d_u8 = (uint8_t *)p;
+  for (int k = 0; k < SF_PFLONG_NTRI; k++)
+    if ((rc = B.alloc(&d_tri[k], tri, kPfTableNames[k]))) return rc;
+  if ((rc = B.alloc(&d_f64, n_f64, "results, scale powers, hairpin weights, q5, q3, partial sums"))) return rc;
+  if ((rc = B.alloc(&d_u8, n_u8, "sequences, constraints, centroids"))) return rc;
   if ((rc = long_bind_rows(B, K, R, s0, d_u8, hF))) return rc;
 
   std::vector<size_t> pow_off((size_t)n), cen_off((size_t)n);
@@ -1983,7 +1979,7 @@ struct PflSingleLaunch {
   const SfDevParamsPF *X = (const SfDevParamsPF *)g.dX;
   SfPfLong F;
   int prob_waves = 0;
-  int bind(LongBufs &, const std::vector<SfPfLong> &hF) {
+  int bind(CallBufs &, const std::vector<SfPfLong> &hF) {
     F = hF[0];
     prob_waves = pfl_prob_waves(F.L, lanes);
     return SF_OK;
@@ -2086,21 +2082,15 @@ int sf_pf_banded(const uint8_t *seq, int L, const char *cons, const int32_t *mfe
   memset(&F, 0, sizeof F);
   F.L = L;
   F.B = B;
-  LongBufs Bf;
-  Bf.who = "sf_pf_banded";
-  void *p;
-  double *d_tab[SF_PFBAND_NTAB];
-  for (int k = 0; k < SF_PFBAND_NTAB; k++) {
-    if ((rc = Bf.alloc(&p, nL * nB * sizeof(double), kPfTableNames[k]))) return rc;
-    d_tab[k] = (double *)p;
-  }
-  if ((rc = Bf.alloc(&p, n_f64 * sizeof(double), "results, scale powers, hairpin weights, q5, q3, partial sums"))) return rc;
-  double *d_f64 = (double *)p;
-  if ((rc = Bf.alloc(&p, 2 * (nL + 2) * sizeof(int32_t), "exponents of q5 and q3"))) return rc;
-  F.e5 = (int32_t *)p;
+  CallBufs Bf("sf_pf_banded");
+  double *d_tab[SF_PFBAND_NTAB], *d_f64;
+  uint8_t *d_u8;
+  for (int k = 0; k < SF_PFBAND_NTAB; k++)
+    if ((rc = Bf.alloc(&d_tab[k], nL * nB, kPfTableNames[k]))) return rc;
+  if ((rc = Bf.alloc(&d_f64, n_f64, "results, scale powers, hairpin weights, q5, q3, partial sums"))) return rc;
+  if ((rc = Bf.alloc(&F.e5, 2 * (nL + 2), "exponents of q5 and q3"))) return rc;
   F.e3 = F.e5 + nL + 2;
-  if ((rc = Bf.alloc(&p, 2 * nL + 3, "sequence, centroid"))) return rc;
-  uint8_t *d_u8 = (uint8_t *)p;
+  if ((rc = Bf.alloc(&d_u8, 2 * nL + 3, "sequence, centroid"))) return rc;
   F.S = d_u8;
   F.cen = (char *)d_u8 + nL + 2;
   pfl_bind_tables(F, d_tab, 0);
@@ -2223,14 +2213,14 @@ struct PflBatchLaunch {
   int n = 0, wmax = 0;
   const SfPfLong *d_F = nullptr;
   uint8_t *d_act = nullptr;
-  int bind(LongBufs &B, const std::vector<SfPfLong> &hF) {
+  int bind(CallBufs &B, const std::vector<SfPfLong> &hF) {
     n = (int)hF.size();
     for (const SfPfLong &F : hF) wmax = std::max(wmax, pfl_prob_waves(F.L, lanes));
-    void *p;
+    uint8_t *p;  // the states, then a mark a row
     const int rc = B.alloc(&p, (size_t)n * (sizeof(SfPfLong) + 1), "partition function states, row marks");
     if (rc) return rc;
     d_F = (const SfPfLong *)p;
-    d_act = (uint8_t *)p + (size_t)n * sizeof(SfPfLong);
+    d_act = p + (size_t)n * sizeof(SfPfLong);
     HIPCHK(hipMemcpyAsync(p, hF.data(), (size_t)n * sizeof(SfPfLong), hipMemcpyHostToDevice, g.stream));
     return SF_OK;
   }
@@ -2304,54 +2294,17 @@ namespace {
 double g_lri_ms = 0.0;
 int64_t g_lri_duplexes = 0;
 
-// device buffers of one duplex call; freed when it goes out of scope (after the stream has drained)
-struct DupBufs {
-  std::vector<void *> ptrs;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  ~DupBufs() {
-    hipStreamSynchronize(g.stream);
-    for (void *p : ptrs) hipFree(p);
-    for (hipEvent_t e : ev)
-      if (e) hipEventDestroy(e);
-  }
-  int alloc(void **p, size_t bytes) {
-    *p = nullptr;
-    const hipError_t e = hipMalloc(p, bytes ? bytes : 1);
-    if (e != hipSuccess) {
-      hipGetLastError();
-      char b[256];
-      snprintf(b, sizeof b, "duplex: hipMalloc of %zu bytes failed: %s", bytes, hipGetErrorString(e));
-      g.last_hip_error = b;
-      *p = nullptr;
-      return SF_ERR_HIP;
-    }
-    ptrs.push_back(*p);
-    return SF_OK;
-  }
-  template <class T>
-  int upload(T **d, const T *h, size_t count) {
-    void *p;
-    int rc = alloc(&p, count * sizeof(T));
-    if (rc) return rc;
-    *d = (T *)p;
-    if (count) HIPCHK(hipMemcpyAsync(p, h, count * sizeof(T), hipMemcpyHostToDevice, g.stream));
-    return SF_OK;
-  }
-};
-
 int dup_grid(long long tasks) {  // workgroups of a grid-stride launch: enough for every CU's LDS, bounded scratch
   const long long cap = (long long)(g.n_cu > 0 ? g.n_cu : 1) * 8;
   return (int)(tasks < cap ? (tasks < 1 ? 1 : tasks) : cap);
 }
 
 // n pairs that are already on the device as codes -> energies (and records) on the device
-int launch_duplex_batch(DupBufs &B, SfDupBatch A, int max1, int max2) {
+int launch_duplex_batch(CallBufs &B, SfDupBatch A, int max1, int max2) {
   if (A.n <= 0) return SF_OK;
   const int grid = dup_grid(((long long)A.n + SF_DUP_BLOCK - 1) / SF_DUP_BLOCK);
-  void *scr;
-  int rc = B.alloc(&scr, (size_t)(max1 > 0 ? max1 : 1) * (max2 > 0 ? max2 : 1) * grid * SF_DUP_BLOCK * sizeof(int16_t));
+  int rc = B.alloc(&A.scratch, (size_t)(max1 > 0 ? max1 : 1) * (max2 > 0 ? max2 : 1) * grid * SF_DUP_BLOCK, "duplex tables");
   if (rc) return rc;
-  A.scratch = (int16_t *)scr;
   A.max2 = max2 > 0 ? max2 : 1;
   A.status = (int *)g.status.p;
   SF_LAUNCH(sf_duplex_batch_kernel, grid, SF_DUP_BLOCK, 0, g.stream, A, (const SfDevParams *)g.dP);
@@ -2385,25 +2338,24 @@ int sf_duplex_batch(const uint8_t *s1, const uint8_t *s2, int n, int ld, const i
   }
   std::vector<uint8_t> c1((size_t)n * ld), c2((size_t)n * ld);
   for (size_t x = 0; x < c1.size(); x++) { c1[x] = sf_encode_nt(s1[x]); c2[x] = sf_encode_nt(s2[x]); }
-  DupBufs B;
+  CallBufs B("sf_duplex_batch");
   SfDupBatch A;
   memset(&A, 0, sizeof A);
   uint8_t *d1, *d2;
   int32_t *dl1, *dl2;
-  if ((rc = B.upload(&d1, c1.data(), c1.size())) || (rc = B.upload(&d2, c2.data(), c2.size())) ||
-      (rc = B.upload(&dl1, len1, (size_t)n)) || (rc = B.upload(&dl2, len2, (size_t)n)))
+  if ((rc = B.upload(&d1, c1.data(), c1.size(), "first strands")) || (rc = B.upload(&d2, c2.data(), c2.size(), "second strands")) ||
+      (rc = B.upload(&dl1, len1, (size_t)n, "first lengths")) || (rc = B.upload(&dl2, len2, (size_t)n, "second lengths")))
     return rc;
-  void *de, *di, *dj, *ds = nullptr;
-  if ((rc = B.alloc(&de, n * sizeof(int32_t))) || (rc = B.alloc(&di, n * sizeof(int32_t))) || (rc = B.alloc(&dj, n * sizeof(int32_t))))
+  if ((rc = B.alloc(&A.e, (size_t)n, "energies")) || (rc = B.alloc(&A.i, (size_t)n, "i")) || (rc = B.alloc(&A.j, (size_t)n, "j")))
     return rc;
-  if (structure_out && (rc = B.alloc(&ds, (size_t)n * SF_DUPLEX_STRUCT_LEN))) return rc;
+  if (structure_out && (rc = B.alloc(&A.structure, (size_t)n * SF_DUPLEX_STRUCT_LEN, "structures"))) return rc;
   A.s1 = d1; A.s2 = d2; A.len1 = dl1; A.len2 = dl2; A.n = n; A.ld = ld;
-  A.e = (int32_t *)de; A.i = (int32_t *)di; A.j = (int32_t *)dj; A.structure = (char *)ds;
   if ((rc = launch_duplex_batch(B, A, max1, max2))) return rc;
-  HIPCHK(hipMemcpyAsync(energy_out, de, n * sizeof(int32_t), hipMemcpyDeviceToHost, g.stream));
-  if (i_out) HIPCHK(hipMemcpyAsync(i_out, di, n * sizeof(int32_t), hipMemcpyDeviceToHost, g.stream));
-  if (j_out) HIPCHK(hipMemcpyAsync(j_out, dj, n * sizeof(int32_t), hipMemcpyDeviceToHost, g.stream));
-  if (structure_out) HIPCHK(hipMemcpyAsync(structure_out, ds, (size_t)n * SF_DUPLEX_STRUCT_LEN, hipMemcpyDeviceToHost, g.stream));
+  HIPCHK(hipMemcpyAsync(energy_out, A.e, n * sizeof(int32_t), hipMemcpyDeviceToHost, g.stream));
+  if (i_out) HIPCHK(hipMemcpyAsync(i_out, A.i, n * sizeof(int32_t), hipMemcpyDeviceToHost, g.stream));
+  if (j_out) HIPCHK(hipMemcpyAsync(j_out, A.j, n * sizeof(int32_t), hipMemcpyDeviceToHost, g.stream));
+  if (structure_out)
+    HIPCHK(hipMemcpyAsync(structure_out, A.structure, (size_t)n * SF_DUPLEX_STRUCT_LEN, hipMemcpyDeviceToHost, g.stream));
   return read_status(g.stream, false);
 }
 
@@ -2433,31 +2385,25 @@ int sf_lri_scan(const uint8_t *seq, int L, int kmer, int step, int32_t cutoff_dc
 
   std::vector<uint8_t> codes((size_t)L);
   for (int x = 0; x < L; x++) codes[x] = sf_encode_nt(seq[x]);
-  DupBufs B;
+  CallBufs B("sf_lri_scan");
   SfLriScan A;
   memset(&A, 0, sizeof A);
   uint8_t *dcodes;
-  if ((rc = B.upload(&dcodes, codes.data(), codes.size()))) return rc;
+  if ((rc = B.upload(&dcodes, codes.data(), codes.size(), "sequence"))) return rc;
   A.codes = dcodes; A.L = L; A.kmer = kmer; A.step = step; A.n_j = n_j; A.n_k = n_k;
   A.n_chunk = (n_k + SF_DUP_BLOCK - 1) / SF_DUP_BLOCK;
   A.cutoff = cutoff_dcal;
   A.max_hits = (unsigned)max_hits;
-  void *p;
   const size_t nd = (size_t)n_j * n_k;
   if (dense) {
-    if ((rc = B.alloc(&p, nd * sizeof(int32_t)))) return rc;
-    A.dense_e = (int32_t *)p;
-    if ((rc = B.alloc(&p, nd * sizeof(int32_t)))) return rc;
-    A.dense_i = (int32_t *)p;
-    if ((rc = B.alloc(&p, nd * sizeof(int32_t)))) return rc;
-    A.dense_j = (int32_t *)p;
+    if ((rc = B.alloc(&A.dense_e, nd, "dense energies")) || (rc = B.alloc(&A.dense_i, nd, "dense i")) ||
+        (rc = B.alloc(&A.dense_j, nd, "dense j")))
+      return rc;
   } else {
-    if ((rc = B.alloc(&p, (size_t)max_hits * sizeof(sf_lri_hit)))) return rc;
-    A.hits = (sf_lri_hit *)p;
+    if ((rc = B.alloc(&A.hits, (size_t)max_hits, "hits"))) return rc;
   }
-  if ((rc = B.alloc(&p, sizeof(unsigned)))) return rc;
-  A.n_hits = (unsigned *)p;
-  HIPCHK(hipMemsetAsync(p, 0, sizeof(unsigned), g.stream));
+  if ((rc = B.alloc(&A.n_hits, 1, "hit count"))) return rc;
+  HIPCHK(hipMemsetAsync(A.n_hits, 0, sizeof(unsigned), g.stream));
 
   const long long tasks = (long long)n_j * A.n_chunk;
   const int grid = dup_grid(tasks);
@@ -2469,15 +2415,14 @@ int sf_lri_scan(const uint8_t *seq, int L, int kmer, int step, int32_t cutoff_dc
   if (ldsc) {
     HIPCHK(hipFuncSetAttribute((const void *)sf_lri_scan_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   } else {
-    if ((rc = B.alloc(&p, ctab * grid))) return rc;
-    A.scratch = (int16_t *)p;
+    if ((rc = B.alloc(&A.scratch, ctab / sizeof(int16_t) * grid, "duplex tables"))) return rc;
   }
   // Bound the TIME of one launch, not its task count: the work of a duplex grows with kmer^4 (measured: 3.7e6 duplexes/s at
   // k = 20, 4.6e5 at k = 40), so a launch takes 8e6 * (20 / kmer)^4 duplexes — one to two seconds — and never fewer tasks
   // than the grid has workgroups.
   long long per_launch = (long long)(8.0e6 * (20.0 / kmer) * (20.0 / kmer) * (20.0 / kmer) * (20.0 / kmer)) / SF_DUP_BLOCK;
   if (per_launch < grid) per_launch = grid;
-  for (auto &e : B.ev) HIPCHK(hipEventCreate(&e));
+  for (int k = 0; k < 2; k++) HIPCHK(hipEventCreate(&B.ev[k]));
   HIPCHK(hipEventRecord(B.ev[0], g.stream));
   for (long long t0 = 0; t0 < tasks; t0 += per_launch) {
     const long long t1 = t0 + per_launch < tasks ? t0 + per_launch : tasks;
@@ -2548,28 +2493,26 @@ int sf_lri_background(const uint8_t *seq, int L, int kmer, const int32_t *j_win,
     if (j_win[h] < 0 || j_win[h] > L - kmer + 1 || k_win[h] < 0 || k_win[h] > L - kmer) return SF_ERR_BAD_ARG;
   std::vector<uint8_t> codes((size_t)L);
   for (int x = 0; x < L; x++) codes[x] = sf_encode_nt(seq[x]);
-  DupBufs B;
-  uint8_t *dcodes;
-  int32_t *djw, *dkw;
-  if ((rc = B.upload(&dcodes, codes.data(), codes.size())) || (rc = B.upload(&djw, j_win, (size_t)n_hits)) ||
-      (rc = B.upload(&dkw, k_win, (size_t)n_hits)))
+  CallBufs B("sf_lri_background");
+  uint8_t *dcodes, *r1, *r2;
+  int32_t *djw, *dkw, *l1;
+  if ((rc = B.upload(&dcodes, codes.data(), codes.size(), "sequence")) || (rc = B.upload(&djw, j_win, (size_t)n_hits, "j_win")) ||
+      (rc = B.upload(&dkw, k_win, (size_t)n_hits, "k_win")))
     return rc;
-  void *r1, *r2, *l1, *de;
-  const size_t nb = (size_t)rows * kmer;
-  if ((rc = B.alloc(&r1, nb)) || (rc = B.alloc(&r2, nb)) || (rc = B.alloc(&l1, rows * sizeof(int32_t))) ||
-      (rc = B.alloc(&de, rows * sizeof(int32_t))))
-    return rc;
-  const int sgrid = (int)((rows + SF_SHUF_BLOCK - 1) / SF_SHUF_BLOCK);
-  const size_t lds = (((size_t)SF_SHUF_BLOCK * kmer + 3) & ~(size_t)3) * 2 + SF_SHUF_BLOCK * 25 * sizeof(uint16_t);
-  SF_LAUNCH(sf_lri_shuffle_kernel, sgrid, SF_SHUF_BLOCK, lds, g.stream, (const uint8_t *)dcodes, L, kmer, (const int32_t *)djw,
-            (const int32_t *)dkw, n_hits, r, kind, seed, (uint8_t *)r1, (uint8_t *)r2, (int32_t *)l1);
-  HIPCHK(hipGetLastError());
   SfDupBatch A;
   memset(&A, 0, sizeof A);
-  A.s1 = (const uint8_t *)r1; A.s2 = (const uint8_t *)r2; A.len1 = (const int32_t *)l1; A.len2 = nullptr;
-  A.n = (int)rows; A.ld = kmer; A.n2 = kmer; A.e = (int32_t *)de;
+  const size_t nb = (size_t)rows * kmer;
+  if ((rc = B.alloc(&r1, nb, "first strands")) || (rc = B.alloc(&r2, nb, "second strands")) ||
+      (rc = B.alloc(&l1, (size_t)rows, "lengths")) || (rc = B.alloc(&A.e, (size_t)rows, "energies")))
+    return rc;
+  const int sgrid = (int)((rows + SF_SHUF_BLOCK - 1) / SF_SHUF_BLOCK);
+  SF_LAUNCH(sf_lri_shuffle_kernel, sgrid, SF_SHUF_BLOCK, sf_shuffle_lds_bytes(kmer), g.stream, (const uint8_t *)dcodes, L, kmer,
+            (const int32_t *)djw, (const int32_t *)dkw, n_hits, r, kind, seed, r1, r2, l1);
+  HIPCHK(hipGetLastError());
+  A.s1 = r1; A.s2 = r2; A.len1 = l1; A.len2 = nullptr;
+  A.n = (int)rows; A.ld = kmer; A.n2 = kmer;
   if ((rc = launch_duplex_batch(B, A, kmer, kmer))) return rc;
-  HIPCHK(hipMemcpyAsync(energies_out, de, rows * sizeof(int32_t), hipMemcpyDeviceToHost, g.stream));
+  HIPCHK(hipMemcpyAsync(energies_out, A.e, rows * sizeof(int32_t), hipMemcpyDeviceToHost, g.stream));
   if (rows1_out) HIPCHK(hipMemcpyAsync(rows1_out, r1, nb, hipMemcpyDeviceToHost, g.stream));
   if (rows2_out) HIPCHK(hipMemcpyAsync(rows2_out, r2, nb, hipMemcpyDeviceToHost, g.stream));
   return read_status(g.stream, false);

@@ -471,17 +471,23 @@ __global__ __launch_bounds__(NT, 2) void sf_pf_fast_kernel(const uint8_t *__rest
 #undef OWNT
 }
 
-template <typename... A>
-static inline void sf_pf_fast_launch(int grid, int W, hipStream_t st, int *pf_flag, A... args) {
-  if (W == 120) SF_LAUNCH((sf_pf_fast_kernel<128, 120>), grid, 128, 0, st, args..., (const char *)nullptr, (int *)nullptr, pf_flag);
-  else if (W <= 128) SF_LAUNCH((sf_pf_fast_kernel<128, 0>), grid, 128, 0, st, args..., (const char *)nullptr, (int *)nullptr, pf_flag);
-  else if (W == 200) SF_LAUNCH((sf_pf_fast_kernel<256, 200>), grid, 256, 0, st, args..., (const char *)nullptr, (int *)nullptr, pf_flag);
-  else SF_LAUNCH((sf_pf_fast_kernel<256, 0>), grid, 256, 0, st, args..., (const char *)nullptr, (int *)nullptr, pf_flag);
-}
-// constrained folds (a constraint row per fold); W <= 250
+// Every instantiation of the kernel, X(NT, WT, HC): 128 threads up to W = 128, else 256; W = 120 and W = 200 (BASELINE config 5)
+// have the width folded in; HC: a constraint row per fold, W <= SF_PFF_HC_MAXW, generic widths only.
+#define SF_PFF_INSTANCES(X) \
+  X(128, 120, false) X(128, 0, false) X(256, 200, false) X(256, 0, false) X(128, 0, true) X(256, 0, true)
 #define SF_PFF_HC_MAXW 250
+static inline int sf_pff_threads(int W) { return W <= 128 ? 128 : 256; }
+// Starts the instantiation for folds of W nt, constrained (hc) or not; `args` is the kernel's whole argument list.
+// false if SF_PFF_INSTANCES does not hold it (nothing is started then).
 template <typename... A>
-static inline void sf_pf_fast_launch_hc(int grid, int W, hipStream_t st, A... args) {
-  if (W <= 128) SF_LAUNCH((sf_pf_fast_kernel<128, 0, true>), grid, 128, 0, st, args...);
-  else SF_LAUNCH((sf_pf_fast_kernel<256, 0, true>), grid, 256, 0, st, args...);
+static inline bool sf_pf_fast_launch(bool hc, int grid, int threads, int W, hipStream_t st, A... args) {
+  const int wt = (!hc && (W == 120 || W == 200)) ? W : 0;
+#define SF_X(NT, WT, HC)                                                                   \
+  if (threads == NT && wt == WT && hc == HC) {                                             \
+    SF_LAUNCH((sf_pf_fast_kernel<NT, WT, HC>), grid, NT, 0, st, args...);                  \
+    return true;                                                                           \
+  }
+  SF_PFF_INSTANCES(SF_X)
+#undef SF_X
+  return false;
 }

@@ -1072,29 +1072,32 @@ __global__ __launch_bounds__(SF_PFL_NT) void sf_pf_lds_kernel(const uint8_t *__r
 #undef OWN
 }
 
+// Every instantiation of the kernel, X(WT, SH, HC): what sf_pfl_configure prepares and sf_pf_lds_launch can start.  W = 120
+// (ScanFold's default window) has the width folded in; SH: the windows of a run share their inside tables; HC: a constraint row
+// per fold — stand-alone folds only (a window's constraint slice changes which cells exist, so consecutive windows do not share
+// their inside tables), and no instantiation with the width folded in.
+#define SF_PFL_INSTANCES(X) X(120, false, false) X(120, true, false) X(0, false, false) X(0, true, false) X(0, false, true)
 static inline hipError_t sf_pfl_configure() {
-  hipError_t e = hipFuncSetAttribute((const void *)sf_pf_lds_kernel<120, false>, hipFuncAttributeMaxDynamicSharedMemorySize, SF_PFL_LDS_LIMIT);
+  hipError_t e;
+#define SF_X(WT, SH, HC)                                                                                                          \
+  e = hipFuncSetAttribute((const void *)sf_pf_lds_kernel<WT, SH, HC>, hipFuncAttributeMaxDynamicSharedMemorySize, SF_PFL_LDS_LIMIT); \
   if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute((const void *)sf_pf_lds_kernel<120, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SF_PFL_LDS_LIMIT);
-  if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute((const void *)sf_pf_lds_kernel<0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, SF_PFL_LDS_LIMIT);
-  if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute((const void *)sf_pf_lds_kernel<0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SF_PFL_LDS_LIMIT);
-  if (e != hipSuccess) return e;
-  return hipFuncSetAttribute((const void *)sf_pf_lds_kernel<0, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SF_PFL_LDS_LIMIT);
+  SF_PFL_INSTANCES(SF_X)
+#undef SF_X
+  return hipSuccess;
 }
 
-// constrained folds: stand-alone folds only (a window's constraint slice changes which cells exist, so consecutive windows
-// do not share their inside tables)
+// Starts the instantiation for folds of W nt, constrained (hc) or in shared runs; `args` is the kernel's whole argument list.
+// false if SF_PFL_INSTANCES does not hold it (nothing is started then).
 template <typename... A>
-static inline void sf_pf_lds_launch_hc(int grid, int W, hipStream_t st, A... args) {
-  SF_LAUNCH((sf_pf_lds_kernel<0, false, true>), grid, SF_PFL_NT, sf_pfl_lds_bytes(W, true), st, args...);
-}
-template <typename... A>
-static inline void sf_pf_lds_launch(int grid, int W, bool shared, hipStream_t st, A... args) {
-  const size_t lds = sf_pfl_lds_bytes(W);
-  if (W == 120 && shared) SF_LAUNCH((sf_pf_lds_kernel<120, true>), grid, SF_PFL_NT, lds, st, args...);
-  else if (W == 120) SF_LAUNCH((sf_pf_lds_kernel<120, false>), grid, SF_PFL_NT, lds, st, args...);
-  else if (shared) SF_LAUNCH((sf_pf_lds_kernel<0, true>), grid, SF_PFL_NT, lds, st, args...);
-  else SF_LAUNCH((sf_pf_lds_kernel<0, false>), grid, SF_PFL_NT, lds, st, args...);
+static inline bool sf_pf_lds_launch(bool hc, bool shared, int grid, int threads, int W, hipStream_t st, A... args) {
+  const int wt = (!hc && W == 120) ? 120 : 0;
+#define SF_X(WT, SH, HC)                                                                                  \
+  if (wt == WT && shared == SH && hc == HC && threads == SF_PFL_NT) {                                     \
+    SF_LAUNCH((sf_pf_lds_kernel<WT, SH, HC>), grid, SF_PFL_NT, sf_pfl_lds_bytes(W, hc), st, args...);     \
+    return true;                                                                                          \
+  }
+  SF_PFL_INSTANCES(SF_X)
+#undef SF_X
+  return false;
 }

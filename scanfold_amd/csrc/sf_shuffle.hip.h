@@ -148,6 +148,9 @@ __device__ __forceinline__ void sf_shuffle_row(const uint8_t *src, int W, int ki
 #define SF_SHUF_BLOCK 64
 
 // LDS per block: rows[64][W] output rows + lst[64][W] successor lists + cnt[64][25] uint16
+static inline size_t sf_shuffle_lds_bytes(int W) {  // the dynamic LDS of a launch of a shuffle kernel at width W
+  return (((size_t)SF_SHUF_BLOCK * W + 3) & ~(size_t)3) * 2 + SF_SHUF_BLOCK * 25 * sizeof(uint16_t);
+}
 __global__ void sf_shuffle_kernel(const uint8_t *__restrict__ transcript, int L, int W, int step, int win_begin,
                                   int n_win, int r, int kind, uint64_t seed, uint8_t *__restrict__ seqs_out) {
   SF_DYN_SMEM(smem);

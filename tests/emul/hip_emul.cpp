@@ -1,6 +1,8 @@
 /* TEST-ONLY: fiber scheduler behind hip_emul.h (see that header). */
 #include "hip_emul.h"
 
+#include <string>
+
 namespace sfemul {
 Block *g_blk = nullptr;
 dim3 g_blockIdx, g_gridDim, g_blockDim;
@@ -52,3 +54,16 @@ void run_block(unsigned nthreads, size_t shmem, const std::function<void()> &bod
   b->cur = -1;
 }
 }  // namespace sfemul
+
+/* the launch log: one line per SF_LAUNCH, the kernel as spelled at the call site; the first 64 KiB since it was last cleared
+ * (the whole-record tests launch a kernel per diagonal and never read it) */
+namespace sfemul {
+static std::string g_launch_log;
+void log_launch(const char *kern) {
+  if (g_launch_log.size() < 65536) g_launch_log.append(kern).push_back('\n');
+}
+}  // namespace sfemul
+extern "C" {
+const char *sfemul_launch_log() { return sfemul::g_launch_log.c_str(); }
+void sfemul_launch_log_clear() { sfemul::g_launch_log.clear(); }
+}

@@ -231,7 +231,9 @@ inline void sfemul_launch(K kern, dim3 grid, dim3 block, size_t shmem, A... args
     sfemul::run_block(block.x, shmem, [&]() { kern(args...); });
   }
 }
+/* every launch also appends the kernel as the call site spells it to a log (tests/test_window_routes.py) */
+namespace sfemul { void log_launch(const char *kern); }
 #define SF_LAUNCH(kern, grid, block, shmem, stream, ...) \
-  do { (void)(stream); sfemul_launch(kern, dim3(grid), dim3(block), shmem, __VA_ARGS__); } while (0)
+  do { (void)(stream); sfemul::log_launch(#kern); sfemul_launch(kern, dim3(grid), dim3(block), shmem, __VA_ARGS__); } while (0)
 
 #endif

@@ -109,8 +109,8 @@ PFSTAMP_PATCHES = [
      "      if (pf_flag) pf_flag[fold] = sf_pf_out_of_range(Z);  // redone scaled by sf_pf_kernel<true>\n    }\n    SF_PH(44)\n    if (SFL0) atomicAdd(SFP + 45, 1ull);\n"),
     (HOST, "    int rc = ensure(g.status, sizeof(int));\n    if (rc) return rc;\n    HIPCHK(hipMemset(g.status.p, 0, sizeof(int)));",
      "    int rc = ensure(g.status, 65536);\n    if (rc) return rc;\n    HIPCHK(hipMemset(g.status.p, 0, 65536));"),
-    (HOST, "                     d_dG, d_mbd, d_cen, d_cd, d_tr, L, win0, step, run_len, share, (const char *)nullptr, (int *)nullptr, d_flag);\n",
-     "                     d_dG, d_mbd, d_cen, d_cd, d_tr, L, win0, step, run_len, share, (const char *)nullptr, (int *)g.status.p, d_flag);\n"
+    (HOST, "                               d_dG, d_mbd, d_cen, d_cd, d_tr, L, win0, step, run_len, share, d_cons, d_status, d_flag);\n",
+     "                               d_dG, d_mbd, d_cen, d_cd, d_tr, L, win0, step, run_len, share, d_cons, (int *)g.status.p, d_flag);\n"
      "    if (const char *so = getenv(\"SF_STAMP_OUT\")) {\n      static unsigned long long hb[8 * 64];\n      HIPCHK(hipStreamSynchronize(st));\n"
      "      HIPCHK(hipMemcpy(hb, (char *)g.status.p + 32768, sizeof hb, hipMemcpyDeviceToHost));\n"
      "      HIPCHK(hipMemset((char *)g.status.p + 32768, 0, sizeof hb));\n      if (FILE *f = fopen(so, \"a\")) {\n"
