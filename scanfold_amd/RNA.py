@@ -8,17 +8,19 @@ md.temperature other than 37 needs a parameter set with enthalpy tables (params.
 fc.hc_add_from_db and fc.sc_add_SHAPE_deigan (ScanFold-Scan.py:410; ScanFold.py:512,534) are provided through
 sf_fold_constrained.  RNA.duplexfold(s1, s2) (ScanFold.py:785; ScanFoldFunctions.py:824) folds through sf_duplex_batch.
 Not provided: plotting, Zarringhalam soft constraints (upstream's call fails too).
-Sequences longer than SF_MAX_W (400 nt, the window kernels' limit) fold with fc.mfe() / RNA.fold through sf_fold_long
-(whole records up to 32 767 nt: ScanFold.py --global_refold, :1509-1547), hc_add_from_db included; with md.max_bp_span
-set they fold through sf_fold_banded (banded tables, the same bytes) when the record is longer than 32 767 nt (up to
-SF_MAX_BANDED) or at least four spans long.  Their partition
-function, centroid and mean base-pair distance exist in the engine (Engine.pf_long; functions.rna_refold) but this facade
-does not route to them yet: fc.pf() / fc.centroid() / fc.mean_bp_distance() raise NotImplementedError, as does the SHAPE
-term, which does not exist past 400 nt.
+Sequences longer than SF_MAX_W (400 nt, the window kernels' limit) fold with fc.mfe() / RNA.fold as whole records,
+hc_add_from_db included (ScanFold.py --global_refold, :1509-1547).  Which entry point they reach is scanfold_amd.whole's
+decision, under its AUTO policy ("Routes of the whole-record folds"): full tables up to 32 767 nt, banded
+tables under md.max_bp_span (the same bytes) for a longer record or one at least four spans long.  Their partition
+function, centroid and mean base-pair distance exist in the engine (functions.rna_refold) but this facade does not route
+to them yet: fc.pf() / fc.centroid() / fc.mean_bp_distance() raise NotImplementedError, as does the SHAPE term, which
+does not exist past 400 nt.
+The model is global state of the engine, like RNA's md defaults: Engine.md_span is the span this facade last made resident,
+and a fold_compound changes the engine's span only when its model's differs from that record.
 """
 import numpy as np
 
-from . import _lib
+from . import _lib, whole
 
 
 class md:
@@ -33,9 +35,9 @@ def _check_md(model):
     eng.set_temperature(float(model.temperature) if model is not None else 37.0)
     span = getattr(model, "max_bp_span", -1) if model is not None else -1
     span = int(span) if span not in (None, -1) and int(span) > 0 else 0
-    if span != getattr(eng, "_span", 0):  # the model is global state of the engine, like RNA's md defaults
+    if span != eng.md_span:  # the model is global state of the engine, like RNA's md defaults
         eng.set_max_bp_span(span)
-        eng._span = span
+        eng.md_span = span
     return eng
 
 
@@ -92,40 +94,16 @@ class fold_compound:
             raise TypeError("sc_add_SHAPE_zarringhalam() missing required arguments: b, default_value, shape_conversion")
         raise NotImplementedError("Zarringhalam soft constraints are not implemented by the HIP engine")
 
-    def _long(self):
-        return len(self.sequence) > _lib.SF_MAX_W
-
     def mfe(self):
         self._eng = _check_md(self._model)
-        if self._long():
-            if self._sc is not None:
-                raise NotImplementedError("SHAPE soft constraints on a sequence longer than %d nt: the whole-record fold "
-                                          "(sf_fold_long) has no pseudo-energy term" % _lib.SF_MAX_W)
-            L, span = len(self.sequence), self._eng.max_bp_span
-            if L > _lib.SF_MAX_LONG and span < 1:
-                raise ValueError("a sequence of %d nt folds only under md.max_bp_span (sf_fold_banded): without a span "
-                                 "whole-record folds stop at %d nt" % (L, _lib.SF_MAX_LONG))
-            # under a span the band holds the whole fold: the same bytes from 12 L span bytes of tables (sf_fold_banded)
-            if L > _lib.SF_MAX_LONG or (span > 0 and 4 * span <= L and self._eng.has_fold_banded()):
-                e, db = self._eng.fold_banded(self.sequence, self._hc)
-            else:
-                e, db = self._eng.fold_long(self.sequence, self._hc)
-            return db, _f32(e)
-        if self._hc is not None or self._sc is not None:
-            r = self._eng.fold_constrained([self.sequence], None if self._hc is None else [self._hc],
-                                           None if self._sc is None else self._sc[None, :], pf=False)
-            return r["structure"][0], _f32(r["mfe"][0])
-        e, db = self._eng.mfe_trace_batch([self.sequence])
-        return db[0], _f32(e[0])
+        e, db = whole.fold(self._eng, self.sequence, self._hc, whole.AUTO, self._sc)
+        return db, _f32(e)
 
     def pf(self):
         """-> (structure string, ensemble free energy).  The string is the centroid structure, not
         ViennaRNA's pair-propensity string (ScanFold discards it, ScanFold-Scan.py:383)."""
         self._eng = _check_md(self._model)
-        if self._long():
-            raise NotImplementedError("no partition function (and so no centroid / mean base-pair distance) through this "
-                                      "facade for a sequence longer than %d nt: only the MFE of a whole record is routed "
-                                      "(sf_fold_long); call Engine.pf_long or functions.rna_refold" % _lib.SF_MAX_W)
+        whole.pf_route(len(self.sequence), self._eng.max_bp_span, banded=whole.AUTO)  # refuses a whole record
         if self._sc is not None:
             raise NotImplementedError("partition function with SHAPE soft constraints (the reference calls fc.pf() "
                                       "before sc_add_SHAPE_*, ScanFold.py:525-539)")

@@ -4,6 +4,7 @@ There is no CPU fallback: if the shared library is missing or no GPU is usable, 
 (The reference's compute path is ViennaRNA on the CPU through a 12-process pool,
 ScanFold-Scan.py:73-77,244-262; nothing of it is kept.)
 """
+import contextlib
 import ctypes
 import os
 
@@ -159,6 +160,7 @@ _PF_BANDED = ("sf_pf_banded", "whole-record partition functions under a base-pai
 _PF_LONG_BATCH = ("sf_pf_long_batch", "partition functions of many sequences past %d nt" % SF_MAX_W)
 _DUPLEX = ("duplex entry points (sf_duplex_batch, sf_lri_scan, sf_lri_background)", "duplex folds and --lri",
            tuple(_DUPLEX_EXPORTS))
+_D, _I = ctypes.c_double, ctypes.c_int  # Engine._times' field types
 
 
 def _share_hip_runtime_with_torch():
@@ -268,6 +270,7 @@ class Engine:
         self.device = int(device)
         self.params = None
         self.max_bp_span = 0  # what the last set_max_bp_span made resident (sf_init: no limit)
+        self.md_span = 0  # the span the RNA facade last made resident (RNA._check_md sets it only when a model's differs)
         self.load_params(paramset if paramset is not None else _params.default_params())
 
     # -- plumbing --
@@ -317,6 +320,28 @@ class Engine:
         p = cache[t]
         self._load(p)
         self.params = p
+
+    @contextlib.contextmanager
+    def saved_model(self):
+        """A scope around folds under another model: on exit, also on an exception, the parameter set (and so the temperature),
+        the base-pair span and the facade's record of it are as they were on entry.  The set is uploaded again only where
+        the scope left another one resident."""
+        params0, span0, md_span0 = self.params, self.max_bp_span, self.md_span
+        try:
+            yield self
+        finally:
+            if self.params is not params0:
+                self._load(params0)
+                self.params = params0
+            self.set_max_bp_span(span0)
+            self.md_span = md_span0
+
+    def _times(self, need, **fields):
+        """the out-parameters of <entry point>_times, `fields` naming them in the C order with their types -> dict"""
+        self._need(*need)
+        vals = [t() for t in fields.values()]
+        self._check(getattr(self.lib, need[0] + "_times")(*(ctypes.byref(v) for v in vals)))
+        return {k: v.value for k, v in zip(fields, vals)}
 
     def shutdown(self):
         self._check(self.lib.sf_shutdown())
@@ -394,10 +419,7 @@ class Engine:
 
     def fold_long_times(self):
         """-> (fill_ms, f5_ms, traceback_ms) of the last fold_long (device events)."""
-        self._need(*_FOLD_LONG)
-        t = [ctypes.c_double() for _ in range(3)]
-        self._check(self.lib.sf_fold_long_times(*(ctypes.byref(x) for x in t)))
-        return tuple(x.value for x in t)
+        return tuple(self._times(_FOLD_LONG, fill_ms=_D, f5_ms=_D, trace_ms=_D).values())
 
     def has_fold_banded(self):
         return getattr(self.lib, "sf_fold_banded", None) is not None
@@ -412,11 +434,7 @@ class Engine:
 
     def fold_banded_times(self):
         """-> dict(fill_ms, f5_ms, trace_ms, band, fill_launches) of the last fold_banded (device events; band = min(span, L))."""
-        self._need(*_FOLD_BANDED)
-        t = [ctypes.c_double() for _ in range(3)]
-        b, n = ctypes.c_int(), ctypes.c_int()
-        self._check(self.lib.sf_fold_banded_times(*(ctypes.byref(x) for x in t), ctypes.byref(b), ctypes.byref(n)))
-        return dict(fill_ms=t[0].value, f5_ms=t[1].value, trace_ms=t[2].value, band=b.value, fill_launches=n.value)
+        return self._times(_FOLD_BANDED, fill_ms=_D, f5_ms=_D, trace_ms=_D, band=_I, fill_launches=_I)
 
     def fold_banded_bytes(self, L, span):
         """the device memory fold_banded would allocate for L nucleotides under `span` (sf_fold_banded_bytes)"""
@@ -450,11 +468,7 @@ class Engine:
 
     def fold_long_batch_times(self):
         """-> dict(fill_ms, f5_ms, trace_ms, chunks) of the last fold_long_batch (device events, summed over its chunks)."""
-        self._need(*_FOLD_LONG_BATCH)
-        t = [ctypes.c_double() for _ in range(3)]
-        ch = ctypes.c_int()
-        self._check(self.lib.sf_fold_long_batch_times(*(ctypes.byref(x) for x in t), ctypes.byref(ch)))
-        return dict(fill_ms=t[0].value, f5_ms=t[1].value, trace_ms=t[2].value, chunks=ch.value)
+        return self._times(_FOLD_LONG_BATCH, fill_ms=_D, f5_ms=_D, trace_ms=_D, chunks=_I)
 
     def set_long_batch_bytes(self, nbytes):
         """the device memory one chunk of fold_long_batch (and of fold_banded_batch and pf_long_batch) may take for its
@@ -477,11 +491,7 @@ class Engine:
     def fold_banded_batch_times(self):
         """-> dict(fill_ms, f5_ms, trace_ms, chunks, fill_launches) of the last fold_banded_batch (device events, summed over
         its chunks; a chunk's fill launches are the widest band of its rows)."""
-        self._need(*_FOLD_BANDED_BATCH)
-        t = [ctypes.c_double() for _ in range(3)]
-        ch, n = ctypes.c_int(), ctypes.c_int()
-        self._check(self.lib.sf_fold_banded_batch_times(*(ctypes.byref(x) for x in t), ctypes.byref(ch), ctypes.byref(n)))
-        return dict(fill_ms=t[0].value, f5_ms=t[1].value, trace_ms=t[2].value, chunks=ch.value, fill_launches=n.value)
+        return self._times(_FOLD_BANDED_BATCH, fill_ms=_D, f5_ms=_D, trace_ms=_D, chunks=_I, fill_launches=_I)
 
     def has_pf_long(self):
         return getattr(self.lib, "sf_pf_long", None) is not None
@@ -492,21 +502,22 @@ class Engine:
         item.  mfe_hint: the sequence's MFE in dcal/mol (fold_long's), which sets the scale of the first attempt.  Raises
         ScanFoldHipError on a library without the entry point (there is no fallback)."""
         self._need(*_PF_LONG)
+        return self._pf_record(self.lib.sf_pf_long, seq, cons, mfe_hint)
+
+    def _pf_record(self, entry, seq, cons, mfe_hint):
+        """entry = sf_pf_long or sf_pf_banded -> dict(dG, mean_bp_dist, centroid, centroid_dist)"""
         arr, L, c = _record(seq, cons)
         hint = None if mfe_hint is None else np.array([int(mfe_hint)], dtype=np.int32)
         out = np.zeros(3)
         cen = np.zeros(L + 1, dtype=np.uint8)
-        self._check(self.lib.sf_pf_long(arr.ctypes.data, L, c, None if hint is None else hint.ctypes.data,
-                                        out[0:].ctypes.data, out[1:].ctypes.data, cen.ctypes.data, out[2:].ctypes.data))
+        self._check(entry(arr.ctypes.data, L, c, None if hint is None else hint.ctypes.data,
+                          out[0:].ctypes.data, out[1:].ctypes.data, cen.ctypes.data, out[2:].ctypes.data))
         return dict(dG=float(out[0]), mean_bp_dist=float(out[1]), centroid=bytes(cen[:L]).decode(),
                     centroid_dist=float(out[2]))
 
     def pf_long_times(self):
         """-> dict(inside_ms, outside_ms, attempts, lns) of the last pf_long (device events; lns = the per-nucleotide scale)."""
-        self._need(*_PF_LONG)
-        a, b, n, l = ctypes.c_double(), ctypes.c_double(), ctypes.c_int(), ctypes.c_double()
-        self._check(self.lib.sf_pf_long_times(ctypes.byref(a), ctypes.byref(b), ctypes.byref(n), ctypes.byref(l)))
-        return dict(inside_ms=a.value, outside_ms=b.value, attempts=n.value, lns=l.value)
+        return self._times(_PF_LONG, inside_ms=_D, outside_ms=_D, attempts=_I, lns=_D)
 
     def has_pf_banded(self):
         return getattr(self.lib, "sf_pf_banded", None) is not None
@@ -518,23 +529,12 @@ class Engine:
         records whose composition changes along their length work.  Raises ScanFoldHipError where no span is set, and on a
         library without the entry point (there is no fallback)."""
         self._need(*_PF_BANDED)
-        arr, L, c = _record(seq, cons)
-        hint = None if mfe_hint is None else np.array([int(mfe_hint)], dtype=np.int32)
-        out = np.zeros(3)
-        cen = np.zeros(L + 1, dtype=np.uint8)
-        self._check(self.lib.sf_pf_banded(arr.ctypes.data, L, c, None if hint is None else hint.ctypes.data,
-                                          out[0:].ctypes.data, out[1:].ctypes.data, cen.ctypes.data, out[2:].ctypes.data))
-        return dict(dG=float(out[0]), mean_bp_dist=float(out[1]), centroid=bytes(cen[:L]).decode(),
-                    centroid_dist=float(out[2]))
+        return self._pf_record(self.lib.sf_pf_banded, seq, cons, mfe_hint)
 
     def pf_banded_times(self):
         """-> dict(inside_ms, outside_ms, attempts, lns, band, launches) of the last pf_banded (device events; lns = the band
         tables' per-nucleotide scale, band = min(span, L), launches = diagonal launches over all attempts)."""
-        self._need(*_PF_BANDED)
-        a, b, n, l, bd, ln = (ctypes.c_double(), ctypes.c_double(), ctypes.c_int(), ctypes.c_double(), ctypes.c_int(),
-                              ctypes.c_int())
-        self._check(self.lib.sf_pf_banded_times(*(ctypes.byref(x) for x in (a, b, n, l, bd, ln))))
-        return dict(inside_ms=a.value, outside_ms=b.value, attempts=n.value, lns=l.value, band=bd.value, launches=ln.value)
+        return self._times(_PF_BANDED, inside_ms=_D, outside_ms=_D, attempts=_I, lns=_D, band=_I, launches=_I)
 
     def pf_banded_bytes(self, L, span):
         """the device memory pf_banded would allocate for L nucleotides under `span` (sf_pf_banded_bytes)"""
@@ -573,10 +573,7 @@ class Engine:
     def pf_long_batch_times(self):
         """-> dict(inside_ms, outside_ms, chunks, inside_passes) of the last pf_long_batch (device events, summed over its
         chunks; inside_passes = chunks when no row needed another scale)."""
-        self._need(*_PF_LONG_BATCH)
-        a, b, ch, ps = ctypes.c_double(), ctypes.c_double(), ctypes.c_int(), ctypes.c_int()
-        self._check(self.lib.sf_pf_long_batch_times(ctypes.byref(a), ctypes.byref(b), ctypes.byref(ch), ctypes.byref(ps)))
-        return dict(inside_ms=a.value, outside_ms=b.value, chunks=ch.value, inside_passes=ps.value)
+        return self._times(_PF_LONG_BATCH, inside_ms=_D, outside_ms=_D, chunks=_I, inside_passes=_I)
 
     # -- duplex folds and the LRI scan (include/scanfold_hip_duplex.h) --
     def has_duplex(self):

@@ -12,7 +12,7 @@ dinuclShuffle(s)                       SFF:255-277   identical strings under the
 simple_transcribe(seq)                 SFF:580-584
 pvalue_function(energy_list, r)        SFF:727-738
 zscore_function(energy_list, r)        SFF:741-751   statistics.stdev variant, 0.0 when sd == 0
-rna_refold(frag, T, constraint_file)   SFF:758-772   RNAfold -p -T -C: whole records through fold_long / pf_long
+rna_refold(frag, T, constraint_file)   SFF:758-772   RNAfold -p -T -C: whole records in full tables (scanfold_amd.whole)
 rna_folder((frag, T, algo))            SFF:774-789   one batched device launch of size 1
 randomizer(frag)                       SFF:800-802
 energies(seq_list, T, algo)            SFF:805-814   ONE batched launch for the whole list (past 400 nt: fold_long_batch)
@@ -147,36 +147,15 @@ def energies(seq_list, temperature=37, algo="rnafold"):
     """MFE (kcal/mol) of every sequence, order preserved.  Lengths up to SF_MAX_W: one device launch (mfe_batch) per distinct
     length.  Every longer sequence of the call, up to SF_MAX_LONG and of any mix of lengths, goes to ONE fold_long_batch
     (whole-record folds side by side; chunked by device memory inside the library), so a record past the window limit and its
-    shuffles cost little more than one fold.  A library without sf_fold_long_batch raises ScanFoldHipError."""
-    from . import _lib
+    shuffles cost little more than one fold, in full tables whatever span is resident (whole.fold_rows under whole.NEVER).
+    A library without sf_fold_long_batch raises ScanFoldHipError."""
+    from . import _lib, whole
     if algo != "rnafold":
         # the reference leaves MFE unbound for any other algo (ScanFoldFunctions.py:785-789)
         raise UnboundLocalError("local variable 'MFE' referenced before assignment")
     eng = _lib.get_engine()
     eng.set_temperature(int(temperature))  # md.temperature = int(temperature), ScanFoldFunctions.py:776-777
-    seqs = [str(s) for s in seq_list]
-    out = [None] * len(seqs)
-    by_len = {}
-    for k, s in enumerate(seqs):
-        by_len.setdefault(len(s), []).append(k)
-    long_ks = [k for k, s in enumerate(seqs) if len(s) > _lib.SF_MAX_W]
-    if long_ks:
-        if not eng.has_fold_long_batch():
-            raise _lib.ScanFoldHipError("energies: a sequence of more than %d nt needs sf_fold_long_batch, which this library "
-                                        "(%s) does not export" % (_lib.SF_MAX_W, getattr(eng.lib, "_name", "?")))
-        for k, v in zip(long_ks, _dcal_to_float(eng.fold_long_batch([seqs[k] for k in long_ks]))):
-            out[k] = v
-    for n, ks in by_len.items():
-        if n > _lib.SF_MAX_W:
-            continue
-        if n == 0:
-            for k in ks:
-                out[k] = 0.0
-            continue
-        vals = _dcal_to_float(eng.mfe_batch([seqs[k] for k in ks]))
-        for k, v in zip(ks, vals):
-            out[k] = v
-    return out
+    return _dcal_to_float(whole.fold_rows(eng, [str(s) for s in seq_list], whole.NEVER))
 
 
 def rna_folder(arg):
@@ -192,10 +171,10 @@ def rna_refold(frag, temperature, constraint_file):
     with '>' before them is skipped); `frag` is the sequence that is folded, as upstream hands it to RNAfold's input.
     MFE in kcal/mol as ViennaRNA returns it; ED is the ensemble diversity (mean base-pair distance) rounded to 2 decimals,
     as RNAfold prints it.  Up to SF_MAX_W nt the window entry points fold (fold_constrained); longer sequences, up to
-    SF_MAX_LONG, go through fold_long and pf_long, the latter scaled from the former's energy.
+    SF_MAX_LONG, fold in full tables (whole.fold, whole.pf under whole.NEVER), the ensemble scaled from the fold's energy.
     Unlike upstream's subprocess the call is not stateless: like rna_folder it leaves the shared engine's resident model at
     `temperature` (Engine.set_temperature), which is what the next fold of this module sets anyway."""
-    from . import _lib
+    from . import _lib, whole
     eng = _lib.get_engine()
     eng.set_temperature(float(temperature))
     seq = str(frag).strip().upper().replace("T", "U")
@@ -207,8 +186,8 @@ def rna_refold(frag, temperature, constraint_file):
     if len(cons) != len(seq):
         raise ValueError("constraint string and sequence differ in length")
     if len(seq) > _lib.SF_MAX_W:
-        e, structure = eng.fold_long(seq, cons)
-        r = eng.pf_long(seq, cons, mfe_hint=e)
+        e, structure = whole.fold(eng, seq, cons, whole.NEVER)
+        r = whole.pf(eng, seq, cons, e, whole.NEVER)
         centroid, ed = r["centroid"], r["mean_bp_dist"]
     else:
         r = eng.fold_constrained([seq], [cons])

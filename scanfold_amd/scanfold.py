@@ -11,9 +11,9 @@ TSV round trip; the pair tabulation of that stage runs on the GPU (sf_tabulate_p
 stage's files with the prefix `<that>.ScanFold.`, then the dot-bracket files (makedbn) and the motif extraction /
 refolds of ScanFold.py:1582-1776 (scanfold_amd.motifs: `<that>.ExtractedStructures.gff3`, `<that>_motif_<n>.dbn/.ct`).
 --global_refold folds the whole record three times after the dbn files are written (ScanFold.py:1509-1547): unconstrained,
-then with the -1 and the -2 filter's dot-bracket lines as hard constraints, through the RNA facade (whole-record folds,
-sf_fold_long), into `<that>.<--dbn_file_path>` and `<that>.AllDBN.txt`.  ScanFold.py's per-record directories and IGV
-wig exports are not reproduced.
+then with the -1 and the -2 filter's dot-bracket lines as hard constraints (whole-record folds, routed by scanfold_amd.whole
+as the RNA facade routes them), into `<that>.<--dbn_file_path>` and `<that>.AllDBN.txt`.  ScanFold.py's per-record
+directories and IGV wig exports are not reproduced.
 --global_span N (not upstream) runs those three folds under max bp span N in banded tables (sf_fold_banded), and
 --global_ensemble_banded adds their ensembles from the banded partition function (sf_pf_banded), at any record length.
 --global_zscore (not upstream) z-scores the whole record against shuffles of itself (one batched whole-record fold,
@@ -34,7 +34,7 @@ from . import _lib, fold as foldmod
 from . import functions as sff
 from . import scan as scanmod
 from . import motifs as motifmod
-from . import writers
+from . import whole, writers
 
 
 def header_line(read_name):
@@ -166,19 +166,18 @@ def global_refold(seq, name, outname, temperature, dbn_file_path="AllDBN-global_
     last window's end; when the windows stop short of the record's end the line is padded with '.' (no ScanFold pair
     there, so no constraint) to the record's length.
     The engine's model (base-pair span, temperature, and the RNA facade's record of the span) is put back exactly as it
-    was, also when a fold raises: the stages after this one, and the next records, fold as they would without the flag.
-    ensemble (--global_ensemble, not upstream): the partition function of the same three folds (one Engine.pf_long_batch
-    call past SF_MAX_W where the library has it, else Engine.pf_long three times: the same numbers; scaled from each fold's
-    MFE) into `<outname>.<dbn_file_path minus .txt>.ensemble.txt`, three records of a header line (ensemble free
-    energy, ED = mean base-pair distance to 2 decimals, centroid distance), the sequence and the centroid.
+    was, also when a fold raises (Engine.saved_model): the stages after this one, and the next records, fold as they would
+    without the flag.  Which entry point each fold reaches is scanfold_amd.whole's decision; the flags only set the policy.
+    ensemble (--global_ensemble, not upstream): the partition function of the same three folds in full tables (one
+    Engine.pf_long_batch call past SF_MAX_W where the library has it, else Engine.pf_long three times: the same numbers;
+    scaled from each fold's MFE) into `<outname>.<dbn_file_path minus .txt>.ensemble.txt`, three records of a header line
+    (ensemble free energy, ED = mean base-pair distance to 2 decimals, centroid distance), the sequence and the centroid.
     span (--global_span N, not upstream): the three folds run under max_bp_span = N in banded tables (Engine.fold_banded:
     memory and work linear in the record's length, records past SF_MAX_LONG), and the header lines gain " span=N".
     ensemble_banded (--global_ensemble_banded, not upstream; needs span): the same ensemble file from Engine.pf_banded, the
     partition function under the span in banded tables, each fold's MFE as hint: any record fold_banded takes, where
     --global_ensemble stops at SF_MAX_LONG.  Its header lines carry " span=N" too."""
     from . import RNA
-    md = RNA.md()
-    md.temperature = int(temperature)
     span = int(span or 0)
     tail = " span=%d" % span if span > 0 else ""
     cons = []
@@ -187,47 +186,16 @@ def global_refold(seq, name, outname, temperature, dbn_file_path="AllDBN-global_
             line = f.readlines()[2].rstrip("\r\n")
         cons.append(line + "." * max(0, len(seq) - len(line)))
     eng = _lib.get_engine()
-    span0, params0 = eng.max_bp_span, eng.params
-    had_facade_span, facade_span0 = hasattr(eng, "_span"), getattr(eng, "_span", 0)
-    try:
+    with eng.saved_model():
         eng.set_max_bp_span(span)  # (the scan's --span is engine state; the fresh md has none, or --global_span's)
-        eng._span = span
-        if span > 0:
-            eng.set_temperature(float(md.temperature))
-            (e1, s1), (e2, s2), (e0, s0) = (eng.fold_banded(seq, c) for c in (cons[0], cons[1], None))
-            e1, e2, e0 = RNA._f32(e1), RNA._f32(e2), RNA._f32(e0)
-        else:
-            fc = RNA.fold_compound(seq, md)
-            fc.hc_add_from_db(cons[0])
-            s1, e1 = fc.mfe()
-            fc = RNA.fold_compound(seq, md)
-            fc.hc_add_from_db(cons[1])
-            s2, e2 = fc.mfe()
-            s0, e0 = RNA.fold_compound(seq, md).mfe()
+        eng.md_span = span
+        eng.set_temperature(float(int(temperature)))
+        (e1, s1), (e2, s2), (e0, s0) = ((RNA._f32(e), db) for e, db in (
+            whole.fold(eng, seq, c, whole.ALWAYS if span > 0 else whole.AUTO) for c in (cons[0], cons[1], None)))
         ens = []
-        if ensemble_banded:
-            if span < 1:
-                raise ValueError("the banded ensemble needs a base-pair span")
-            ens = [eng.pf_banded(seq, c, mfe_hint=int(round(e * 100))) for c, e in ((None, e0), (cons[0], e1), (cons[1], e2))]
-        elif ensemble and len(seq) > _lib.SF_MAX_W and eng.has_pf_long_batch():
-            # the three ensembles in the same launches; each row is pf_long's bit for bit
-            ens = eng.pf_long_batch([seq] * 3, [None, cons[0], cons[1]], [int(round(e * 100)) for e in (e0, e1, e2)])
-        elif ensemble:
-            for c, e in ((None, e0), (cons[0], e1), (cons[1], e2)):
-                if len(seq) > _lib.SF_MAX_W:
-                    ens.append(eng.pf_long(seq, c, mfe_hint=int(round(e * 100))))
-                else:
-                    r = eng.fold_constrained([seq], ["." * len(seq) if c is None else c], mfe=False)
-                    ens.append({k: (r[k][0] if k == "centroid" else float(r[k][0])) for k in r})
-    finally:
-        if eng.params is not params0:
-            eng._load(params0)
-            eng.params = params0
-        eng.set_max_bp_span(span0)
-        if had_facade_span:
-            eng._span = facade_span0
-        else:
-            del eng._span
+        if ensemble or ensemble_banded:
+            ens = whole.pf_rows(eng, seq, [None, cons[0], cons[1]], [int(round(e * 100)) for e in (e0, e1, e2)],
+                                whole.ALWAYS if ensemble_banded else whole.NEVER)
     with open(outname + "." + dbn_file_path, "w") as w:
         w.write(">" + str(name) + "\tGlobal Full MFE=" + str(e0) + tail + "\n" + seq + "\n" + s0 + "\n")
         w.write(">" + str(name) + "\tRefolded with -1 constraints MFE=" + str(e1) + tail + "\n" + seq + "\n" + s1 + "\n")
@@ -252,15 +220,15 @@ GLOBAL_ZSCORE_HEADER = ("Name\tLength\tTemperature\tRandomizations\tShuffleType\
 def global_zscore(seq, name, outname, temperature, randomizations, shuffle_type, seed=0, span=0):
     """--global_zscore (not upstream): the z-score of the WHOLE record.  The unconstrained MFE of `seq` at int(-t) under the
     model of global_refold (no --span) against `randomizations` shuffles of it (`functions.scramble`, "di" or "mono"), folded
-    in one `functions.energies` call — past 400 nt one batched whole-record fold (sf_fold_long_batch) — and turned into a
-    z-score and p-value by `zscore_function` / `pvalue_function`, quirks included.  Writes `<outname>.global_zscore.txt`: a
+    together as `functions.energies` folds them — past 400 nt one batched whole-record fold (sf_fold_long_batch) — and turned
+    into a z-score and p-value by `zscore_function` / `pvalue_function`, quirks included.  Writes `<outname>.global_zscore.txt`: a
     header line and one tab-separated row of name, length, temperature, randomizations, shuffle type, MFE, mean and sample
     standard deviation of the shuffles' MFEs, z-score, p-value, the numbers through str(round(x, 2)) as in the scan table.
     Cost: r + 1 folds of the whole record, O(L^3) each: tenths of a second at 1 kb, about twenty minutes at 30 kb with
     r = 100 by the single-fold time of DESIGN 4.4 (the batch's tables for such a record are one chunk per sequence).
     The shuffles draw from Python's `random` seeded with `seed`; the generator's state, and the engine's span, parameter
-    set and temperature, are put back as they were, also when a fold raises, so every other output of the run is the same
-    with and without the flag.
+    set and temperature (Engine.saved_model), are put back as they were, also when a fold raises, so every other output of the
+    run is the same with and without the flag.
     span (--global_zscore_span N, not upstream): the record and the same shuffles are folded under max_bp_span = N in banded
     tables, all r + 1 of them in one Engine.fold_banded_batch (sf_fold_banded_batch: B = min(N, L) fill launches for all of
     them, their exterior loops side by side), at a cost linear in the record's length and at any length up to
@@ -268,23 +236,16 @@ def global_zscore(seq, name, outname, temperature, randomizations, shuffle_type,
     import random
     span = int(span or 0)
     eng = _lib.get_engine()
-    span0, params0 = eng.max_bp_span, eng.params
     state0 = random.getstate()
     try:
         random.seed(seed)
         shuffles = sff.scramble(seq, randomizations, shuffle_type)
-        eng.set_max_bp_span(span)  # (the scan's --span is engine state; the whole-record model has none, or this flag's)
-        if span > 0:
-            eng.set_temperature(int(temperature))
-            E = sff._dcal_to_float(eng.fold_banded_batch([seq] + shuffles))
-        else:
-            E = sff.energies([seq] + shuffles, int(temperature))
     finally:
         random.setstate(state0)
-        if eng.params is not params0:
-            eng._load(params0)
-            eng.params = params0
-        eng.set_max_bp_span(span0)
+    with eng.saved_model():
+        eng.set_max_bp_span(span)  # (the scan's --span is engine state; the whole-record model has none, or this flag's)
+        eng.set_temperature(int(temperature))
+        E = sff._dcal_to_float(whole.fold_rows(eng, [seq] + shuffles, whole.ALWAYS if span > 0 else whole.NEVER))
     z = sff.zscore_function(E, randomizations)
     p = sff.pvalue_function(E, randomizations)
     row = [str(name), str(len(seq)), str(int(temperature)), str(randomizations), str(shuffle_type)]
@@ -368,22 +329,29 @@ def main(argv=None):
         raise ValueError("--global_ensemble and --global_ensemble_banded write the same file: give one of them")
     if args.global_span is not None and (not args.global_refold or args.global_span < 1):
         raise ValueError("--global_span N (N >= 1) sets the base-pair span of the folds of --global_refold: give both")
-    if args.global_span is not None and (args.global_ensemble or args.global_zscore):  # refused before any record is scanned
-        for read_name, seq in scanmod.read_fasta(args.filename):
-            if len(seq) > _lib.SF_MAX_LONG:
-                raise ValueError("--global_span: record %s has %d nt; %s stops at %d nt"
-                                 % (read_name, len(seq), "--global_ensemble (the partition function in full tables; "
-                                    "--global_ensemble_banded has no such limit)" if args.global_ensemble
-                                    else "--global_zscore (the batched fold of the shuffles) has no banded form yet and",
-                                    _lib.SF_MAX_LONG))
-    if args.global_ensemble_banded:  # refused before any record is scanned
-        for read_name, seq in scanmod.read_fasta(args.filename):
-            if len(seq) > _lib.SF_MAX_BANDED:
-                raise ValueError("--global_ensemble_banded: record %s has %d nt, banded folds stop at %d"
-                                 % (read_name, len(seq), _lib.SF_MAX_BANDED))
+    lengths = []
+
+    def past(route, *policy):
+        """(name, length, limit) of the first record longer than the entry point whole.<route>(L, *policy) sends it to takes,
+        or None: what is refused before any record is scanned.  The file is read once, by the first check that needs it."""
+        if not lengths:
+            lengths.extend((name, len(seq)) for name, seq in scanmod.read_fasta(args.filename))
+        return next(((name, L, route(L, *policy).limit) for name, L in lengths if L > route(L, *policy).limit), None)
+
+    if args.global_span is not None and (args.global_ensemble or args.global_zscore):
+        hit = past(whole.pf_route if args.global_ensemble else whole.mfe_route, args.global_span, True, whole.NEVER)
+        if hit:
+            raise ValueError("--global_span: record %s has %d nt; %s stops at %d nt"
+                             % (hit[0], hit[1], "--global_ensemble (the partition function in full tables; "
+                                "--global_ensemble_banded has no such limit)" if args.global_ensemble
+                                else "--global_zscore (the batched fold of the shuffles) has no banded form yet and", hit[2]))
+    if args.global_ensemble_banded:
+        hit = past(whole.pf_route, args.global_span, True, whole.ALWAYS)
+        if hit:
+            raise ValueError("--global_ensemble_banded: record %s has %d nt, banded folds stop at %d" % hit)
     if args.global_zscore and args.lri:
         raise ValueError("--global_zscore z-scores the record of a window scan: not with --lri")
-    if args.global_zscore_span is not None:  # refused before any record is scanned
+    if args.global_zscore_span is not None:
         if args.global_zscore:
             raise ValueError("--global_zscore and --global_zscore_span write the same file: give one of them")
         if args.lri:
@@ -392,17 +360,15 @@ def main(argv=None):
             raise ValueError("--global_zscore_span N needs a base-pair span N >= 1")
         if args.type not in ("di", "mono"):
             raise ValueError('Shuffle type not properly designated; please input "di" or "mono"')
-        for read_name, seq in scanmod.read_fasta(args.filename):
-            if len(seq) > _lib.SF_MAX_BANDED:
-                raise ValueError("--global_zscore_span: record %s has %d nt, banded folds stop at %d"
-                                 % (read_name, len(seq), _lib.SF_MAX_BANDED))
-    if args.global_zscore:  # refused before any record is scanned
+        hit = past(whole.mfe_route, args.global_zscore_span, True, whole.ALWAYS)
+        if hit:
+            raise ValueError("--global_zscore_span: record %s has %d nt, banded folds stop at %d" % hit)
+    if args.global_zscore:
         if args.type not in ("di", "mono"):
             raise ValueError('Shuffle type not properly designated; please input "di" or "mono"')
-        for read_name, seq in scanmod.read_fasta(args.filename):
-            if len(seq) > _lib.SF_MAX_LONG:
-                raise ValueError("--global_zscore: record %s has %d nt, whole-record folds stop at %d"
-                                 % (read_name, len(seq), _lib.SF_MAX_LONG))
+        hit = past(whole.mfe_route, 0, True, whole.NEVER)
+        if hit:
+            raise ValueError("--global_zscore: record %s has %d nt, whole-record folds stop at %d" % hit)
     if args.lri:
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             raise ValueError("--lri runs on one GPU: start it without a multi-process launcher")

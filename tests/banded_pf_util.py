@@ -443,12 +443,11 @@ def run_global_ensemble_banded(engine, tmp_path, monkeypatch, seq, S, scan_args)
     monkeypatch.chdir(tmp_path)
     (tmp_path / "in.fa").write_text(">recE\n" + seq + "\n")
     engine.set_max_bp_span(0)
-    if hasattr(engine, "_span"):
-        del engine._span
+    engine.md_span = 0
     params0 = engine.params
     assert sfd.main(["in.fa"] + scan_args + ["--name", "ge", "--dont_extract", "--global_refold", "--global_span", str(S),
                                              "--global_ensemble_banded"]) == 0
-    assert engine.max_bp_span == 0 and not hasattr(engine, "_span") and engine.params is params0
+    assert engine.max_bp_span == 0 and engine.md_span == 0 and engine.params is params0
     base = [f[:-len(".out")] for f in os.listdir(tmp_path) if f.endswith(".out")][0]
     want = ""
     engine.set_max_bp_span(S)

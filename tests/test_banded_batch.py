@@ -285,8 +285,7 @@ def check_driver_zscore_span(engine, oracle, tmp_path, monkeypatch):
             outs[bool(flag)] = {f: (d / f).read_bytes() for f in os.listdir(d)}
     finally:
         engine.set_max_bp_span(0)
-        if hasattr(engine, "_span"):
-            del engine._span
+        engine.md_span = 0
     base = "rec1.win_40.stp_40.rnd_5.shfl_di"
     plain, z = outs[False], outs[True]
     assert sorted(set(z) - set(plain)) == [base + ".global_zscore.txt"]

@@ -270,11 +270,10 @@ def run_global_span(engine, oracle, tmp_path, monkeypatch, seq, S, scan_args, ex
     monkeypatch.chdir(tmp_path)
     (tmp_path / "in.fa").write_text(">recS\n" + seq + "\n")
     engine.set_max_bp_span(0)
-    if hasattr(engine, "_span"):
-        del engine._span
+    engine.md_span = 0
     params0 = engine.params
     assert sfd.main(["in.fa"] + scan_args + ["--name", "gs", "--dont_extract", "--global_refold", "--global_span", str(S)]) == 0
-    assert engine.max_bp_span == 0 and not hasattr(engine, "_span") and engine.params is params0
+    assert engine.max_bp_span == 0 and engine.md_span == 0 and engine.params is params0
     base = [f[:-len(".out")] for f in os.listdir(tmp_path) if f.endswith(".out")][0]
     want = ""
     for label, tag in (("Global Full", None), ("Refolded with -1 constraints", "-1"), ("Refolded with -2 constraints", "-2")):
@@ -371,8 +370,7 @@ def check_facade_routing(engine, monkeypatch, L, S_banded, S_long):
             assert got == (db, RNA._f32(e))
     finally:
         engine.set_max_bp_span(0)
-        if hasattr(engine, "_span"):
-            del engine._span
+        engine.md_span = 0
 
 
 def test_rna_facade_routes_by_span(emul, monkeypatch):

@@ -160,8 +160,7 @@ def test_combined_driver_global_zscore(gpu_engine, oracle, tmp_path, monkeypatch
             outs[bool(flag)] = {f: (d / f).read_bytes() for f in os.listdir(d)}
     finally:
         gpu_engine.set_max_bp_span(0)
-        if hasattr(gpu_engine, "_span"):
-            del gpu_engine._span
+        gpu_engine.md_span = 0
     base = "rec1.win_60.stp_40.rnd_6.shfl_di"
     plain, z = outs[False], outs[True]
     assert sorted(set(z) - set(plain)) == [base + ".global_zscore.txt"]

@@ -215,8 +215,7 @@ def test_combined_driver_global_zscore(emul, oracle, tmp_path, monkeypatch):
             outs[bool(flag)] = {f: (d / f).read_bytes() for f in os.listdir(d)}
     finally:
         emul.set_max_bp_span(0)
-        if hasattr(emul, "_span"):
-            del emul._span
+        emul.md_span = 0
     base = "rec1.win_40.stp_40.rnd_6.shfl_di"
     plain, z = outs[False], outs[True]
     assert sorted(set(z) - set(plain)) == [base + ".global_zscore.txt"]

@@ -270,8 +270,7 @@ def test_global_refold_leaves_every_other_output_unchanged(emul, tmp_path, monke
         assert emul.max_bp_span == 25
     finally:
         emul.set_max_bp_span(0)
-        if hasattr(emul, "_span"):
-            del emul._span
+        emul.md_span = 0
     plain, refold = outs[False], outs[True]
     extra = sorted(set(refold) - set(plain))
     assert extra == sorted("r%d.win_40.stp_10.rnd_6.shfl_mono.%s" % (k, f) for k in (0, 1)
