@@ -170,6 +170,44 @@ int sf_pf_banded_times(double *inside_ms, double *outside_ms, int *attempts, dou
  * Needs sf_init only; nothing is allocated.  L < 1, L > SF_MAX_BANDED, span < 1, bytes NULL: SF_ERR_BAD_ARG. */
 int sf_pf_banded_bytes(int L, int span, size_t *bytes);
 
+/* One base pair of the sparse list of sf_pf_banded_probs: positions 1-based, i < j, p = its probability in the ensemble. */
+typedef struct { int32_t i, j; double p; } sf_pair_prob;
+
+/* sf_pf_banded with the base-pair probabilities brought out: the dot plot of RNAfold -p / RNAplfold, the probability that
+ * a nucleotide is unpaired, and the positional entropy.  Arguments, limits, attempts and errors are sf_pf_banded's, and
+ * ens_dG, mean_bp_dist, the centroid and centroid_dist are bit for bit what sf_pf_banded returns for the same arguments:
+ * both run one host path, and the extraction reads the tables of the attempt that succeeded after its outside pass.
+ * sf_pf_banded_times reports for this call what it reports for sf_pf_banded.  S >= L is legal (B = L): a short record gets
+ * its unrestricted probabilities.
+ * cutoff: a pair is listed when p >= cutoff; it must lie in (0, 1] (a NaN, 0, a negative value or one above 1:
+ * SF_ERR_BAD_ARG before anything is launched).
+ * unpaired_out[k-1] = clamp(1 - sum_j p(k, j) - sum_i p(i, k), 0, 1), L doubles.
+ * entropy_out[k-1] = - sum p log2 p over the pairs of k - unpaired log2 unpaired, L doubles, in BITS, with 0 log 0 = 0 (the
+ * Shannon entropy of "k pairs with ..., or with nothing").  No parity with another package's entropy track is claimed.
+ * *n_pairs: the length of the pair list, which is staged in host memory owned by the library and read with
+ * sf_pf_probs_pairs: every pair with p >= cutoff, ascending in i and then in j, p being the very double the centroid was
+ * decided on (ob qb, a cell with qb = 0 skipped).  Since sum_j p(i, j) <= 1 a position has at most floor(1 / cutoff)
+ * listed partners, so the list holds at most L * floor(1 / cutoff) / 2 records.
+ * Any output pointer may be NULL; nothing reaches the caller, and the staged list does not change, unless the call
+ * succeeds.  Two calls with the same arguments on the same device return the same bits in all three arrays.
+ * Device memory on top of SF_PF_BANDED_BYTES(L, B), alive beside the band tables while the extraction runs: the rows' counts
+ * (4 L) and 64-bit offsets (8 L), two vectors of L doubles (16 L) and the list (16 n), allocated once n is known:
+ * 28 L + 16 n bytes, reported as measured by sf_pf_banded_probs_times.  The counts are scanned on the host. */
+int sf_pf_banded_probs(const uint8_t *seq, int L, const char *cons, const int32_t *mfe_dcal_hint, double cutoff,
+                       double *ens_dG, double *mean_bp_dist, char *centroid_out, double *centroid_dist,
+                       double *unpaired_out /* L */, double *entropy_out /* L */, size_t *n_pairs);
+
+/* The pair list of the last successful sf_pf_banded_probs: copies its first min(cap, n) records to out and always reports
+ * n (out may be NULL with cap 0; cap > 0 with out NULL: SF_ERR_BAD_ARG).  Before any successful call n = 0.  The list lives
+ * until the next successful sf_pf_banded_probs or until the library is unloaded; a call that fails, for whatever reason,
+ * leaves the previous list in place. */
+int sf_pf_probs_pairs(sf_pair_prob *out, size_t cap, size_t *n);
+
+/* Of the last successful sf_pf_banded_probs: the device-event time (ms) of the extraction's launches (per-nucleotide pass,
+ * count, writing pass; the host's scan between them is left out), which sf_pf_banded_times's outside_ms does not contain;
+ * the length of its list; and the device bytes it allocated on top of SF_PF_BANDED_BYTES.  Any pointer may be NULL. */
+int sf_pf_banded_probs_times(double *extract_ms, size_t *n_pairs, size_t *extra_bytes);
+
 /* One row of sf_pf_long_batch: sf_pf_long's three numbers, the final per-nucleotide scale ln s and the number of inside
  * passes the row took (what sf_pf_long_times reports for the row folded alone). */
 typedef struct { double ens_dG, mean_bp_dist, centroid_dist, lns; int32_t attempts, reserved; } sf_pf_long_row;

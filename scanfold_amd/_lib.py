@@ -98,6 +98,11 @@ _LONG_EXPORTS = {
     "sf_pf_banded_times": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double)] * 2 + [ctypes.POINTER(ctypes.c_int),
                                           ctypes.POINTER(ctypes.c_double)] + [ctypes.POINTER(ctypes.c_int)] * 2),
     "sf_pf_banded_bytes": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
+    "sf_pf_banded_probs": (ctypes.c_int, [_c_u8p, ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_double]
+                           + [ctypes.c_void_p] * 6 + [ctypes.POINTER(ctypes.c_size_t)]),
+    "sf_pf_probs_pairs": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
+    "sf_pf_banded_probs_times": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_size_t),
+                                                ctypes.POINTER(ctypes.c_size_t)]),
     "sf_pf_long_batch": (ctypes.c_int, [_c_u8p, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 5),
     "sf_pf_long_batch_times": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                               ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
@@ -106,6 +111,8 @@ _LONG_EXPORTS = {
 PF_LONG_ROW_DTYPE = np.dtype([("ens_dG", np.float64), ("mean_bp_dist", np.float64), ("centroid_dist", np.float64),
                               ("lns", np.float64), ("attempts", np.int32), ("reserved", np.int32)])
 SF_PF_LONG_NO_HINT = -2 ** 31
+# one listed base pair of sf_pf_banded_probs (struct sf_pair_prob): 1-based positions, i < j
+PAIR_PROB_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("p", "<f8")])
 
 
 # include/scanfold_hip_duplex.h: likewise optional (duplex folds and the LRI scan)
@@ -157,10 +164,11 @@ _FOLD_LONG_BATCH = ("sf_fold_long_batch", "folds of sequences past %d nt" % SF_M
 _FOLD_BANDED_BATCH = ("sf_fold_banded_batch", "batched whole-record folds under a base-pair span in banded tables")
 _PF_LONG = ("sf_pf_long", "whole-record partition functions")
 _PF_BANDED = ("sf_pf_banded", "whole-record partition functions under a base-pair span in banded tables")
+_PF_BANDED_PROBS = ("sf_pf_banded_probs", "base-pair probabilities of a whole record under a base-pair span")
 _PF_LONG_BATCH = ("sf_pf_long_batch", "partition functions of many sequences past %d nt" % SF_MAX_W)
 _DUPLEX = ("duplex entry points (sf_duplex_batch, sf_lri_scan, sf_lri_background)", "duplex folds and --lri",
            tuple(_DUPLEX_EXPORTS))
-_D, _I = ctypes.c_double, ctypes.c_int  # Engine._times' field types
+_D, _I, _Z = ctypes.c_double, ctypes.c_int, ctypes.c_size_t  # Engine._times' field types
 
 
 def _share_hip_runtime_with_torch():
@@ -542,6 +550,39 @@ class Engine:
         n = ctypes.c_size_t()
         self._check(self.lib.sf_pf_banded_bytes(int(L), int(span), ctypes.byref(n)))
         return int(n.value)
+
+    def has_pf_banded_probs(self):
+        return getattr(self.lib, "sf_pf_banded_probs", None) is not None
+
+    def pf_banded_probs(self, seq, cons=None, mfe_hint=None, cutoff=0.01):
+        """pf_banded with the base-pair probabilities brought out (sf_pf_banded_probs) -> pf_banded's dict, its four values
+        bit for bit pf_banded's, plus
+          unpaired  float64 (L,): the probability that nucleotide k + 1 is unpaired
+          entropy   float64 (L,): its positional entropy in bits, -sum p log2 p over its pairs - unpaired log2 unpaired
+          pairs     PAIR_PROB_DTYPE (n,): every pair with p >= cutoff (0 < cutoff <= 1), 1-based i < j, ascending in (i, j);
+                    at most L * floor(1 / cutoff) / 2 of them.
+        A span of at least the record's length gives the unrestricted probabilities.  Raises ScanFoldHipError where no span
+        is set or the cutoff is out of range, and on a library without the entry point (there is no fallback)."""
+        self._need(*_PF_BANDED_PROBS)
+        arr, L, c = _record(seq, cons)
+        hint = None if mfe_hint is None else np.array([int(mfe_hint)], dtype=np.int32)
+        out = np.zeros(3)
+        cen = np.zeros(L + 1, dtype=np.uint8)
+        unp, ent = np.zeros(L), np.zeros(L)
+        n = ctypes.c_size_t(0)
+        self._check(self.lib.sf_pf_banded_probs(arr.ctypes.data, L, c, None if hint is None else hint.ctypes.data,
+                                                float(cutoff), out[0:].ctypes.data, out[1:].ctypes.data, cen.ctypes.data,
+                                                out[2:].ctypes.data, unp.ctypes.data, ent.ctypes.data, ctypes.byref(n)))
+        pairs = np.zeros(n.value, dtype=PAIR_PROB_DTYPE)
+        self._check(self.lib.sf_pf_probs_pairs(pairs.ctypes.data, n.value, ctypes.byref(n)))
+        return dict(dG=float(out[0]), mean_bp_dist=float(out[1]), centroid=bytes(cen[:L]).decode(),
+                    centroid_dist=float(out[2]), unpaired=unp, entropy=ent, pairs=pairs)
+
+    def pf_banded_probs_times(self):
+        """-> dict(extract_ms, n_pairs, extra_bytes) of the last pf_banded_probs: the device-event time of the extraction's
+        launches (pf_banded_times has the passes before it), the length of the list, and the device bytes allocated on top
+        of pf_banded_bytes."""
+        return self._times(_PF_BANDED_PROBS, extract_ms=_D, n_pairs=_Z, extra_bytes=_Z)
 
     def has_pf_long_batch(self):
         return getattr(self.lib, "sf_pf_long_batch", None) is not None

@@ -27,6 +27,7 @@
 #include "sf_pf_long.hip.h"
 #include "sf_pf_long_batch.hip.h"
 #include "sf_pf_banded.hip.h"
+#include "sf_pf_probs.hip.h"
 #include "sf_pf_fast.hip.h"
 #include "sf_pf_lds.hip.h"
 #include "sf_shuffle.hip.h"
@@ -2042,21 +2043,86 @@ double g_pfb_lns = 0.0;
 // |ln Z_s / L| B above which an inside pass is repeated with the scale it measured: a cell of B nucleotides is then within
 // e^+-300 of its neighbours' weights, which leaves the outside pass (products of two such cells) inside FP64
 const double kPfBandEpsB = 300.0;
-}  // namespace
 
-extern "C" {
+// What sf_pf_banded_probs asks of the shared host path on top of sf_pf_banded's outputs, and where it is staged: unp / ent
+// hold L doubles, pairs the list; ms, bytes: the extraction's device-event time and its device allocations.
+struct PfbProbs {
+  double cutoff;
+  std::vector<double> unp, ent;
+  std::vector<sf_pair_prob> pairs;
+  std::vector<int32_t> cnt;             // the rows' counts and their scan (they outlive the call's device buffers, whose
+  std::vector<unsigned long long> off;  // destructor drains the copies on an early return)
+  double ms = 0;
+  size_t bytes = 0;
+};
+static_assert(sizeof(sf_pair_prob) == 16 && sizeof(SfPairProb) == 16 && offsetof(sf_pair_prob, p) == offsetof(SfPairProb, p),
+              "the device's pair record is the header's");
+// of the last successful sf_pf_banded_probs: its list (host memory of the library's, freed with it) and its figures
+std::vector<sf_pair_prob> g_pfbp_pairs;
+double g_pfbp_ms = 0;
+size_t g_pfbp_bytes = 0;
 
-int sf_pf_banded_bytes(int L, int span, size_t *bytes) {
-  SF_ENTER();
-  if (L < 1 || L > SF_MAX_BANDED || span < 1 || !bytes) return SF_ERR_BAD_ARG;
-  *bytes = SF_PF_BANDED_BYTES(L, std::min(span, L));
+// The extraction passes of sf_pf_probs.hip.h over the tables of the attempt that succeeded, before they are freed: the
+// per-nucleotide pass, the count, the scan of the counts (here, on the host), the list's allocation and the writing pass.
+// Bf's events are free again by now; the two timed stretches leave out the host's scan between them.
+int pfb_extract(CallBufs &Bf, const SfPfBand &F, int waves, PfbProbs &P) {
+  int rc;
+  const size_t nL = (size_t)F.L;
+  double *d_unp, *d_ent;
+  int32_t *d_cnt;
+  unsigned long long *d_off;
+  SfPairProb *d_list;
+  if ((rc = Bf.alloc(&d_unp, nL, "unpaired probabilities"))) return rc;
+  if ((rc = Bf.alloc(&d_ent, nL, "positional entropies"))) return rc;
+  if ((rc = Bf.alloc(&d_cnt, nL, "pairs per row"))) return rc;
+  if ((rc = Bf.alloc(&d_off, nL, "offsets of the rows in the pair list"))) return rc;
+  const int col_waves = (int)std::min((nL + 63) / 64, (size_t)waves);
+  float ms0 = 0, ms1 = 0;
+  HIPCHK(hipEventRecord(Bf.ev[0], g.stream));
+  SF_LAUNCH(sf_pfband_nuc_rows_kernel, waves, 64, 0, g.stream, F, d_unp, d_ent);
+  SF_LAUNCH(sf_pfband_nuc_cols_kernel, col_waves, 64, 0, g.stream, F, d_unp, d_ent);
+  SF_LAUNCH(sf_pfband_pairs_count_kernel, waves, 64, 0, g.stream, F, P.cutoff, d_cnt);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(Bf.ev[1], g.stream));
+  std::vector<int32_t> &cnt = P.cnt;
+  std::vector<unsigned long long> &off = P.off;
+  cnt.resize(nL);
+  off.resize(nL);
+  P.unp.resize(nL);
+  P.ent.resize(nL);
+  HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt, nL * sizeof(int32_t), hipMemcpyDeviceToHost, g.stream));
+  HIPCHK(hipMemcpyAsync(P.unp.data(), d_unp, nL * sizeof(double), hipMemcpyDeviceToHost, g.stream));
+  HIPCHK(hipMemcpyAsync(P.ent.data(), d_ent, nL * sizeof(double), hipMemcpyDeviceToHost, g.stream));
+  HIPCHK(hipStreamSynchronize(g.stream));
+  unsigned long long total = 0;
+  for (size_t k = 0; k < nL; k++) {
+    off[k] = total;
+    total += (unsigned long long)cnt[k];
+  }
+  P.pairs.resize((size_t)total);
+  P.bytes = nL * (2 * sizeof(double) + sizeof(int32_t) + sizeof(unsigned long long)) + (size_t)total * sizeof(SfPairProb);
+  if (total) {
+    if ((rc = Bf.alloc(&d_list, (size_t)total, "pair list"))) return rc;
+    HIPCHK(hipMemcpyAsync(d_off, off.data(), nL * sizeof(unsigned long long), hipMemcpyHostToDevice, g.stream));
+    HIPCHK(hipEventRecord(Bf.ev[2], g.stream));
+    SF_LAUNCH(sf_pfband_pairs_write_kernel, waves, 64, 0, g.stream, F, P.cutoff, (const unsigned long long *)d_off, total, d_list);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(Bf.ev[3], g.stream));
+    HIPCHK(hipMemcpyAsync(P.pairs.data(), d_list, (size_t)total * sizeof(SfPairProb), hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipStreamSynchronize(g.stream));
+    HIPCHK(hipEventElapsedTime(&ms1, Bf.ev[2], Bf.ev[3]));
+  }
+  HIPCHK(hipEventElapsedTime(&ms0, Bf.ev[0], Bf.ev[1]));
+  P.ms = (double)ms0 + (double)ms1;
   return SF_OK;
 }
 
-int sf_pf_banded(const uint8_t *seq, int L, const char *cons, const int32_t *mfe_dcal_hint, double *ens_dG, double *mean_bp_dist,
-                 char *centroid_out, double *centroid_dist) {
-  int rc = check_ready();
-  if (rc) return rc;
+// The host path of sf_pf_banded and sf_pf_banded_probs, after check_ready.  probs == NULL: sf_pf_banded, whose
+// allocations (SF_PF_BANDED_BYTES) and launches are exactly these; else the extraction follows the outside pass of the
+// attempt that succeeded and is staged in *probs.  `who` names the entry point in an out-of-memory text.
+int pf_banded_run(const char *who, const uint8_t *seq, int L, const char *cons, const int32_t *mfe_dcal_hint, double *ens_dG,
+                  double *mean_bp_dist, char *centroid_out, double *centroid_dist, PfbProbs *probs) {
+  int rc;
   if (!seq || L < 1 || L > SF_MAX_BANDED || g.max_bp_span < 1) return SF_ERR_BAD_ARG;
   const int B = std::min(g.max_bp_span, L);
   BandHc H;  // unbalanced brackets end the call before any launch
@@ -2082,7 +2148,7 @@ int sf_pf_banded(const uint8_t *seq, int L, const char *cons, const int32_t *mfe
   memset(&F, 0, sizeof F);
   F.L = L;
   F.B = B;
-  CallBufs Bf("sf_pf_banded");
+  CallBufs Bf(who);
   double *d_tab[SF_PFBAND_NTAB], *d_f64;
   uint8_t *d_u8;
   for (int k = 0; k < SF_PFBAND_NTAB; k++)
@@ -2173,6 +2239,7 @@ int sf_pf_banded(const uint8_t *seq, int L, const char *cons, const int32_t *mfe
     if (fabs(eps) * B < 1.0) return leave(SF_ERR_RANGE);  // Z_s is centred and the outside tables still leave the range
     lns += eps;
   }
+  if (probs && (rc = pfb_extract(Bf, F, prob_waves, *probs))) return rc;
   if ((rc = leave(SF_OK))) return rc;
   // staged until here: nothing reaches the caller unless the call succeeds
   hcen[nL] = 0;
@@ -2180,6 +2247,66 @@ int sf_pf_banded(const uint8_t *seq, int L, const char *cons, const int32_t *mfe
   if (mean_bp_dist) *mean_bp_dist = hout[1];
   if (centroid_dist) *centroid_dist = hout[2];
   if (centroid_out) memcpy(centroid_out, hcen.data(), nL + 1);
+  return SF_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int sf_pf_banded_bytes(int L, int span, size_t *bytes) {
+  SF_ENTER();
+  if (L < 1 || L > SF_MAX_BANDED || span < 1 || !bytes) return SF_ERR_BAD_ARG;
+  *bytes = SF_PF_BANDED_BYTES(L, std::min(span, L));
+  return SF_OK;
+}
+
+int sf_pf_banded(const uint8_t *seq, int L, const char *cons, const int32_t *mfe_dcal_hint, double *ens_dG, double *mean_bp_dist,
+                 char *centroid_out, double *centroid_dist) {
+  const int rc = check_ready();
+  if (rc) return rc;
+  return pf_banded_run("sf_pf_banded", seq, L, cons, mfe_dcal_hint, ens_dG, mean_bp_dist, centroid_out, centroid_dist, nullptr);
+}
+
+int sf_pf_banded_probs(const uint8_t *seq, int L, const char *cons, const int32_t *mfe_dcal_hint, double cutoff, double *ens_dG,
+                       double *mean_bp_dist, char *centroid_out, double *centroid_dist, double *unpaired_out,
+                       double *entropy_out, size_t *n_pairs) {
+  int rc = check_ready();
+  if (rc) return rc;
+  if (!(cutoff > 0.0 && cutoff <= 1.0)) return SF_ERR_BAD_ARG;  // (a NaN fails both comparisons)
+  // the vectors and the list are staged like the four classic outputs, which wait in locals until the extraction is in
+  PfbProbs P;
+  P.cutoff = cutoff;
+  double dG = 0, mbd = 0, cd = 0;
+  std::vector<char> cen(centroid_out ? (size_t)std::max(L, 0) + 1 : 0);
+  rc = pf_banded_run("sf_pf_banded_probs", seq, L, cons, mfe_dcal_hint, &dG, &mbd, centroid_out ? cen.data() : nullptr, &cd, &P);
+  if (rc) return rc;  // (the list of the last successful call stays as it is)
+  g_pfbp_pairs.swap(P.pairs);
+  g_pfbp_ms = P.ms;
+  g_pfbp_bytes = P.bytes;
+  if (ens_dG) *ens_dG = dG;
+  if (mean_bp_dist) *mean_bp_dist = mbd;
+  if (centroid_dist) *centroid_dist = cd;
+  if (centroid_out) memcpy(centroid_out, cen.data(), (size_t)L + 1);
+  if (unpaired_out) memcpy(unpaired_out, P.unp.data(), (size_t)L * sizeof(double));
+  if (entropy_out) memcpy(entropy_out, P.ent.data(), (size_t)L * sizeof(double));
+  if (n_pairs) *n_pairs = g_pfbp_pairs.size();
+  return SF_OK;
+}
+
+int sf_pf_probs_pairs(sf_pair_prob *out, size_t cap, size_t *n) {
+  SF_ENTER();
+  if (cap && !out) return SF_ERR_BAD_ARG;
+  const size_t have = g_pfbp_pairs.size(), m = std::min(cap, have);
+  if (m) memcpy(out, g_pfbp_pairs.data(), m * sizeof(sf_pair_prob));
+  if (n) *n = have;
+  return SF_OK;
+}
+
+int sf_pf_banded_probs_times(double *extract_ms, size_t *n_pairs, size_t *extra_bytes) {
+  SF_ENTER();
+  if (extract_ms) *extract_ms = g_pfbp_ms;
+  if (n_pairs) *n_pairs = g_pfbp_pairs.size();
+  if (extra_bytes) *extra_bytes = g_pfbp_bytes;
   return SF_OK;
 }
 

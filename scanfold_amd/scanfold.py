@@ -15,7 +15,8 @@ then with the -1 and the -2 filter's dot-bracket lines as hard constraints (whol
 as the RNA facade routes them), into `<that>.<--dbn_file_path>` and `<that>.AllDBN.txt`.  ScanFold.py's per-record
 directories and IGV wig exports are not reproduced.
 --global_span N (not upstream) runs those three folds under max bp span N in banded tables (sf_fold_banded), and
---global_ensemble_banded adds their ensembles from the banded partition function (sf_pf_banded), at any record length.
+--global_ensemble_banded adds their ensembles from the banded partition function (sf_pf_banded), at any record length, and
+--global_bpp CUTOFF with it their base pairs with probability >= CUTOFF and positional entropy tracks (sf_pf_banded_probs).
 --global_zscore (not upstream) z-scores the whole record against shuffles of itself (one batched whole-record fold,
 sf_fold_long_batch) into `<that>.global_zscore.txt`; --global_zscore_span N (not upstream) does so under max bp span N in
 banded tables (one sf_fold_banded_batch: linear in the record's length, records past 32767 nt).
@@ -156,7 +157,7 @@ def read_reactivities(path):
 
 
 def global_refold(seq, name, outname, temperature, dbn_file_path="AllDBN-global_refold.txt", ensemble=False, span=0,
-                  ensemble_banded=False):
+                  ensemble_banded=False, bpp=None):
     """ScanFold.py:1509-1547 (--global_refold): a fresh RNA.md() at md.temperature = int(-t) — no --span, exactly as
     upstream — folds the whole record unconstrained and with line 3 of `<outname>.ScanFold.-1.dbn` / `.-2.dbn` as
     hc_add_from_db constraint, and writes the three records to `<outname>.<dbn_file_path>`; `<outname>.AllDBN.txt` is the
@@ -176,7 +177,12 @@ def global_refold(seq, name, outname, temperature, dbn_file_path="AllDBN-global_
     memory and work linear in the record's length, records past SF_MAX_LONG), and the header lines gain " span=N".
     ensemble_banded (--global_ensemble_banded, not upstream; needs span): the same ensemble file from Engine.pf_banded, the
     partition function under the span in banded tables, each fold's MFE as hint: any record fold_banded takes, where
-    --global_ensemble stops at SF_MAX_LONG.  Its header lines carry " span=N" too."""
+    --global_ensemble stops at SF_MAX_LONG.  Its header lines carry " span=N" too.
+    bpp (--global_bpp CUTOFF, not upstream; needs ensemble_banded): the three ensembles go through Engine.pf_banded_probs,
+    whose four classic values are pf_banded's bit for bit, so the ensemble file is the same bytes; for each fold (tags
+    full, -1, -2) two more files: `<outname>.global_refold.<tag>.bpp.txt`, a header line "i\tj\tp span=N" and one
+    "%d\t%d\t%.6g" line per pair with p >= CUTOFF, ascending in (i, j) and 1-based, and
+    `<outname>.global_refold.<tag>.entropy.wig`, the positional entropy in bits, one value per nucleotide."""
     from . import RNA
     span = int(span or 0)
     tail = " span=%d" % span if span > 0 else ""
@@ -193,9 +199,11 @@ def global_refold(seq, name, outname, temperature, dbn_file_path="AllDBN-global_
         (e1, s1), (e2, s2), (e0, s0) = ((RNA._f32(e), db) for e, db in (
             whole.fold(eng, seq, c, whole.ALWAYS if span > 0 else whole.AUTO) for c in (cons[0], cons[1], None)))
         ens = []
-        if ensemble or ensemble_banded:
-            ens = whole.pf_rows(eng, seq, [None, cons[0], cons[1]], [int(round(e * 100)) for e in (e0, e1, e2)],
-                                whole.ALWAYS if ensemble_banded else whole.NEVER)
+        hints = [int(round(e * 100)) for e in (e0, e1, e2)]
+        if ensemble_banded and bpp is not None:
+            ens = [whole.pf_probs(eng, seq, c, h, bpp) for c, h in zip([None, cons[0], cons[1]], hints)]
+        elif ensemble or ensemble_banded:
+            ens = whole.pf_rows(eng, seq, [None, cons[0], cons[1]], hints, whole.ALWAYS if ensemble_banded else whole.NEVER)
     with open(outname + "." + dbn_file_path, "w") as w:
         w.write(">" + str(name) + "\tGlobal Full MFE=" + str(e0) + tail + "\n" + seq + "\n" + s0 + "\n")
         w.write(">" + str(name) + "\tRefolded with -1 constraints MFE=" + str(e1) + tail + "\n" + seq + "\n" + s1 + "\n")
@@ -207,6 +215,12 @@ def global_refold(seq, name, outname, temperature, dbn_file_path="AllDBN-global_
             for label, r in zip(("Global Full", "Refolded with -1 constraints", "Refolded with -2 constraints"), ens):
                 w.write(">%s\t%s ensemble dG=%.2f ED=%.2f centroid distance=%.2f%s\n%s\n%s\n"
                         % (name, label, r["dG"], r["mean_bp_dist"], r["centroid_dist"], ens_tail, seq, r["centroid"]))
+    if ensemble_banded and bpp is not None:
+        for tag, r in zip(("full", "-1", "-2"), ens):
+            with open(outname + ".global_refold." + tag + ".bpp.txt", "w") as w:
+                w.write("i\tj\tp" + tail + "\n")
+                w.write("".join("%d\t%d\t%.6g\n" % (i, j, p) for i, j, p in r["pairs"].tolist()))
+            writers.write_wig(r["entropy"].tolist(), 1, name, outname + ".global_refold." + tag + ".entropy.wig")
     with open(outname + ".AllDBN.txt", "w") as w:
         for tag in ("no_filter", "-1", "-2"):
             with open(outname + ".ScanFold." + tag + ".dbn") as f:
@@ -290,6 +304,9 @@ def build_parser():
     p.add_argument('--global_ensemble_banded', action='store_true',
                    help='not in upstream ScanFold: with --global_refold and --global_span N, write the ensemble file of '
                         '--global_ensemble from the partition function under the span in banded tables (records past 32767 nt)')
+    p.add_argument('--global_bpp', type=float, default=None, metavar='CUTOFF',
+                   help='not in upstream ScanFold: with --global_ensemble_banded, also write the base pairs with probability '
+                        '>= CUTOFF (0 < CUTOFF <= 1) and the positional entropy track of each of the three ensembles')
     p.add_argument('--global_zscore', action='store_true',
                    help='not in upstream ScanFold: z-score of the whole record (its MFE at -t, no --span, against -r shuffles of '
                         '--type seeded with --seed) into <output prefix>.global_zscore.txt; costs r + 1 whole-record folds')
@@ -327,6 +344,14 @@ def main(argv=None):
                          "give all three")
     if args.global_ensemble_banded and args.global_ensemble:
         raise ValueError("--global_ensemble and --global_ensemble_banded write the same file: give one of them")
+    if args.global_bpp is not None:
+        if not args.global_ensemble_banded:
+            raise ValueError("--global_bpp CUTOFF lists the base-pair probabilities of the ensembles of "
+                             "--global_ensemble_banded: give both")
+        if not 0.0 < args.global_bpp <= 1.0:  # (a NaN fails both comparisons)
+            raise ValueError("--global_bpp CUTOFF: a probability, 0 < CUTOFF <= 1")
+        if args.lri:
+            raise ValueError("--global_bpp lists the pairs of the record of a window scan: not with --lri")
     if args.global_span is not None and (not args.global_refold or args.global_span < 1):
         raise ValueError("--global_span N (N >= 1) sets the base-pair span of the folds of --global_refold: give both")
     lengths = []
@@ -436,7 +461,7 @@ def main(argv=None):
             if args.global_refold:
                 print("Refolding full sequence using ScanFold results as constraints...")
                 global_refold(seq, args.name, outname, args.t, args.dbn_file_path, ensemble=args.global_ensemble,
-                              span=args.global_span or 0, ensemble_banded=args.global_ensemble_banded)
+                              span=args.global_span or 0, ensemble_banded=args.global_ensemble_banded, bpp=args.global_bpp)
             if args.c == 1 and not args.dont_extract:
                 with open(outname + ".ScanFold.-2.dbn") as f:
                     line = f.readlines()[2]

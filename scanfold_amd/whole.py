@@ -3,8 +3,9 @@
 Up to SF_MAX_W nt a sequence is a window and folds on the window kernels.  Past that the library has seven whole-record entry
 points: full tables (fold_long, pf_long; up to SF_MAX_LONG), banded tables under the resident base-pair span (fold_banded,
 pf_banded; up to SF_MAX_BANDED), and their batches.  mfe_route and pf_route choose among them ("Routes of the
-whole-record folds"; tests/test_whole_routes.py pins the table); fold, fold_rows, pf and pf_rows run what they chose.  No other
-module of the package calls one of the seven on an engine.
+whole-record folds"; tests/test_whole_routes.py pins the table); fold, fold_rows, pf and pf_rows run what they chose; pf_probs
+runs the banded partition function with its base-pair probabilities brought out (pf_banded_probs: pf_banded's route, no
+route of its own).  No other module of the package calls one of them on an engine.
 
 A caller states its banded policy:
   AUTO    the RNA facade's rule: banded tables when the record is past SF_MAX_LONG, or when a span is resident, the record is
@@ -125,3 +126,15 @@ def pf_rows(eng, seq, cons, mfe_hints, banded=NEVER):
 def pf(eng, seq, cons=None, mfe_hint=None, banded=NEVER):
     """pf_rows of one row -> its dict"""
     return pf_rows(eng, seq, [cons], [mfe_hint], banded)[0]
+
+
+def pf_probs(eng, seq, cons=None, mfe_hint=None, cutoff=0.01):
+    """One record under the resident span -> Engine.pf_banded_probs's dict: pf_banded's plus the unpaired probabilities, the
+    positional entropies and the sparse pair list.  The banded policy is ALWAYS (the probabilities leave the device from
+    banded tables only; a span of at least the record's length gives the unrestricted ones), so the route is pf_route's
+    banded one with the probabilities asked for; a library without sf_pf_banded_probs is a ScanFoldHipError."""
+    call = _routed(pf_route, eng, len(seq), False, ALWAYS) + "_probs"
+    if not getattr(eng, "has_" + call)():
+        raise _lib.ScanFoldHipError("base-pair probabilities of a whole record need sf_%s, which this library (%s) does not "
+                                    "export" % (call, getattr(eng.lib, "_name", "?")))
+    return getattr(eng, call)(seq, cons, mfe_hint=mfe_hint, cutoff=cutoff)
