@@ -12,6 +12,8 @@
 #include <algorithm>
 #include <map>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/scanfold_hip_long.h"
@@ -1203,65 +1205,89 @@ int long_for_chunks(const LongRows &R, RowBytes row_bytes, char *str_out, int *c
   return SF_OK;
 }
 
-// The head of a chunk's byte block, the same in both families: every row's sequence (codes, zero on both sides: L + 2 bytes),
-// then the constraint rows as given, then their parsed form (L + 2 each); a family's own bytes follow from o_end.
+// The head of a chunk's byte block, the same in every family: every row's sequence (codes, zero on both sides: L + 2
+// bytes); a family's own bytes follow from o_end.
 struct LongPack {
-  int Lmax = 0, n_hc = 0;
-  size_t n_L = 0, n_hcL = 0;  // nucleotides of all rows, of the constrained rows
-  size_t o_src, o_hc, o_end;
-  std::vector<uint8_t> h8;    // sequences and constraint rows, copied up in one piece
+  int Lmax = 0;
+  size_t n_L = 0;           // nucleotides of all rows
+  size_t o_end;
+  std::vector<uint8_t> h8;  // the sequences, copied up in one piece
 };
 
-// with_cons false: the sequences alone (the banded folds parse their constraints on the host and keep them elsewhere)
-LongPack long_pack(const LongRows &R, int s0, int n, bool with_cons = true) {
+LongPack long_pack(const LongRows &R, int s0, int n) {
   LongPack K;
   for (int k = 0; k < n; k++) {
-    const int L = R.len[s0 + k];
-    K.Lmax = std::max(K.Lmax, L);
-    K.n_L += (size_t)L;
-    if (with_cons && R.constrained[s0 + k]) { K.n_hc++; K.n_hcL += (size_t)L; }
+    K.Lmax = std::max(K.Lmax, (int)R.len[s0 + k]);
+    K.n_L += (size_t)R.len[s0 + k];
   }
-  K.o_src = K.n_L + 2 * (size_t)n;
-  K.o_hc = K.o_src + K.n_hcL;
-  K.o_end = K.o_hc + K.n_hcL + 2 * (size_t)K.n_hc;
-  K.h8.assign(K.o_hc, 0);
-  size_t a_L = 0, a_hcL = 0;
+  K.o_end = K.n_L + 2 * (size_t)n;
+  K.h8.assign(K.o_end, 0);
+  size_t a_L = 0;
   for (int k = 0; k < n; k++) {
     const int L = R.len[s0 + k];
     const uint8_t *row = R.seqs + (size_t)(s0 + k) * R.ld;
     uint8_t *hS = K.h8.data() + a_L + 2 * (size_t)k;
     for (int x = 0; x < L; x++) hS[x + 1] = sf_encode_nt(row[x]);
-    if (with_cons && R.constrained[s0 + k]) {
-      memcpy(K.h8.data() + K.o_src + a_hcL, R.cons + (size_t)(s0 + k) * R.ld, (size_t)L);
-      a_hcL += (size_t)L;
-    }
     a_L += (size_t)L;
   }
   return K;
 }
 
-// Parses one constraint on the device and binds it to a fold's state.  src: its L characters as given; c: L + 2 bytes for
-// the parsed characters; i16: 3 (L + 2) int16 for the bracket partners, the enclosing pairs and the parse's stack.
-void long_parse_hc(SfHc &hc, const char *src, int L, char *c, int16_t *i16) {
-  int16_t *encl = i16 + (size_t)L + 2, *stack = encl + (size_t)L + 2;
-  SF_LAUNCH(sf_long_hc_kernel, 1, 64, 0, g.stream, src, L, c, i16, encl, stack, (int *)g.status.p);
-  hc.c = c;
-  hc.partner = i16;
-  hc.encl = encl;
+// The constraint of one whole record as the device reads it (sf_hc_parse of sf_energy.h, on the host): c[1 .. L] its
+// characters, partner[i] the bracket partner of i, encl[i] the opening position of the innermost bracket pair around i,
+// all 1-based and 0 for none; entries 0 and L + 1 of the three arrays are zero.  Pos: int16 in full tables (SfHc), int32 in
+// banded ones (SfHc32), whose positions pass 32 767.  SF_ERR_CONSTRAINT for unbalanced brackets.
+static_assert(SF_MAX_LONG <= INT16_MAX, "a position in full tables fits SfHc's int16");
+template <class Pos>
+int hc_parse_host(const char *cons, int L, char *c, Pos *partner, Pos *encl) {
+  std::fill(c, c + L + 2, (char)0);
+  std::fill(partner, partner + L + 2, (Pos)0);
+  std::fill(encl, encl + L + 2, (Pos)0);
+  std::vector<Pos> stack;
+  for (int i = 1; i <= L; i++) {
+    const char ch = cons[i - 1];
+    c[i] = ch;
+    if (ch == ')') {
+      if (stack.empty()) return SF_ERR_CONSTRAINT;
+      const Pos o = stack.back();
+      stack.pop_back();
+      partner[o] = (Pos)i;
+      partner[i] = o;
+    }
+    encl[i] = stack.empty() ? (Pos)0 : stack.back();
+    if (ch == '(') stack.push_back((Pos)i);
+  }
+  return stack.empty() ? SF_OK : SF_ERR_CONSTRAINT;
 }
 
-// Clears the chunk's row states (SfLong or SfPfLong) and sets what both have: L, S and hc.  Copies the packed bytes to
-// d_u8, allocates the int16 block of the constrained rows (3 (L + 2) each) and parses each of them on the device.
+// The parsed constraints of a chunk's constrained rows as they are copied up: the bracket partners of all of them, then
+// their enclosing pairs (pos), and their characters (c), L + 2 of each a row.  A caller declares it BEFORE the call's
+// CallBufs: that destructor drains the async copies out of these vectors, so they must still stand when it runs.
 template <class State>
-int long_bind_rows(CallBufs &B, const LongPack &K, const LongRows &R, int s0, uint8_t *d_u8, std::vector<State> &hF) {
-  int16_t *d_i16 = nullptr;
-  if (K.n_hc) {
-    const int rc = B.alloc(&d_i16, 3 * (K.n_hcL + 2 * (size_t)K.n_hc), "bracket partners");
-    if (rc) return rc;
-  }
+struct HcStage {
+  typedef typename std::remove_const<typename std::remove_pointer<decltype(std::declval<State>().hc.partner)>::type>::type Pos;
+  std::vector<Pos> pos;
+  std::vector<char> c;
+};
+
+// Binds the rows s0 .. s0 + hF.size() - 1 of R to the chunk's row states (SfLong, SfPfLong, SfBand or SfPfBand): clears each
+// state and sets what all four have, L, S and hc.  Copies the packed sequences to d_u8, parses the constrained rows into H
+// and copies them into one allocation of their own, (2 sizeof(Pos) + 1) (L + 2) bytes a constrained row.  A row of dots, or
+// a row without a constraint, has none (hc.c == nullptr).
+template <class State>
+int bind_rows(CallBufs &B, const LongPack &K, const LongRows &R, int s0, uint8_t *d_u8, std::vector<State> &hF, HcStage<State> &H) {
+  typedef typename HcStage<State>::Pos Pos;
+  int rc;
+  size_t n_hc = 0, a_L = 0, a = 0;
+  for (size_t k = 0; k < hF.size(); k++)
+    if (R.constrained[s0 + k]) n_hc += (size_t)R.len[s0 + k] + 2;
+  H.pos.resize(2 * n_hc);
+  H.c.resize(n_hc);
+  char *p = nullptr;
+  if (n_hc && (rc = B.alloc(&p, (2 * sizeof(Pos) + 1) * n_hc, "bracket partners, enclosing pairs, constraints"))) return rc;
+  const Pos *d_part = (const Pos *)p, *d_encl = d_part + n_hc;
+  const char *d_c = (const char *)(d_encl + n_hc);
   HIPCHK(hipMemcpyAsync(d_u8, K.h8.data(), K.h8.size(), hipMemcpyHostToDevice, g.stream));
-  size_t a_L = 0, a_hcL = 0;
-  int a_hc = 0;
   for (size_t k = 0; k < hF.size(); k++) {
     const int L = R.len[s0 + k];
     State &F = hF[k];
@@ -1269,16 +1295,22 @@ int long_bind_rows(CallBufs &B, const LongPack &K, const LongRows &R, int s0, ui
     F.L = L;
     F.S = d_u8 + a_L + 2 * k;
     if (R.constrained[s0 + k]) {
-      long_parse_hc(F.hc, (const char *)d_u8 + K.o_src + a_hcL, L, (char *)d_u8 + K.o_hc + a_hcL + 2 * (size_t)a_hc,
-                    d_i16 + 3 * (a_hcL + 2 * (size_t)a_hc));
-      a_hcL += (size_t)L;
-      a_hc++;
+      if ((rc = hc_parse_host(R.cons + (size_t)(s0 + k) * R.ld, L, H.c.data() + a, H.pos.data() + a, H.pos.data() + n_hc + a)))
+        return rc;
+      F.hc.partner = d_part + a;
+      F.hc.encl = d_encl + a;
+      F.hc.c = d_c + a;
+      a += (size_t)L + 2;
     }
     a_L += (size_t)L;
   }
-  HIPCHK(hipGetLastError());
+  if (n_hc) {
+    HIPCHK(hipMemcpyAsync(p, H.pos.data(), 2 * sizeof(Pos) * n_hc, hipMemcpyHostToDevice, g.stream));
+    HIPCHK(hipMemcpyAsync(p + 2 * sizeof(Pos) * n_hc, H.c.data(), n_hc, hipMemcpyHostToDevice, g.stream));
+  }
   return SF_OK;
 }
+
 // Hairpin initiation by loop size 0..n for the whole-record folds (the resident model's table only reaches SF_MAX_W + 1).
 std::vector<int32_t> long_hairpin_table(const sf_params_blob *P, int n) {
   std::vector<int32_t> hp((size_t)n + 1);
@@ -1293,15 +1325,15 @@ std::vector<int32_t> long_hairpin_table(const sf_params_blob *P, int n) {
 // has drained, which read_status waits for.  ms_out grows by the device-event times of fill, f5 and traceback.  A fixed
 // number of device allocations whatever n is, all freed on return: c, fML, fMLt (ops.entries(L) a row), the DML rings, one
 // int32 block (a hairpin table of ops.hairpin_entries(Lmax) + 1 entries, energies, f5, traceback stacks), one byte block
-// (the packed rows, structures), what ops.bind allocates for the constraints, and the row states unless the kernels take
-// the state by value (Ops::by_value).  The caller's ops supply what differs between the layouts (Ops::State, host_hc,
-// entries, hairpin_entries, bind: a row's L / B / S / hc) and the launches over the states at F, in host memory when they
-// go by value and on the device otherwise: fill (every diagonal), f5 (energies to d_mfe) and trace.
+// (the packed rows, structures), what bind_rows allocates for the constraints, and the row states unless the kernels take
+// the state by value (Ops::by_value).  The caller's ops supply what differs between the layouts (Ops::State, entries,
+// hairpin_entries, band: a banded row's B) and the launches over the states at F, in host memory when they go by value and
+// on the device otherwise: fill (every diagonal), f5 (energies to d_mfe) and trace.
 template <class Ops>
 int fold_rows(const LongRows &R, int s0, int n, Ops &ops, int32_t *e_host, char *db_host, double ms_out[3]) {
   typedef typename Ops::State State;
   int rc;
-  const LongPack K = long_pack(R, s0, n, !Ops::host_hc);
+  const LongPack K = long_pack(R, s0, n);
   const int Lmax = K.Lmax;
   const size_t n_L = K.n_L;
   size_t cells = 0, n_stk = 0;
@@ -1316,6 +1348,7 @@ int fold_rows(const LongRows &R, int s0, int n, Ops &ops, int32_t *e_host, char 
   const size_t n_i32 = o_stk + (trace ? n_stk : 0);
   const size_t o_db = K.o_end, n_u8 = o_db + (trace ? n_L + (size_t)n : 0);
   std::vector<State> hF((size_t)n);
+  HcStage<State> H;  // (before B: see HcStage)
 
   CallBufs B(R.who);
   int32_t *d_tab[3], *d_dml, *d_i32;
@@ -1326,15 +1359,16 @@ int fold_rows(const LongRows &R, int s0, int n, Ops &ops, int32_t *e_host, char 
     if ((rc = B.alloc(&d_tab[k], cells, names[k]))) return rc;
   if ((rc = B.alloc(&d_dml, 3 * (n_L + 2 * (size_t)n), "DML rings"))) return rc;
   if ((rc = B.alloc(&d_i32, n_i32, "hairpin table, energies, f5, traceback stacks"))) return rc;
-  if ((rc = B.alloc(&d_u8, n_u8, "sequences, constraints, structures"))) return rc;
+  if ((rc = B.alloc(&d_u8, n_u8, "sequences, structures"))) return rc;
   if (!Ops::by_value && (rc = B.alloc(&d_F, (size_t)n, "fold states"))) return rc;
   const State *F = Ops::by_value ? hF.data() : d_F;
-  if ((rc = ops.bind(B, K, R, s0, d_u8, hF))) return rc;
+  if ((rc = bind_rows(B, K, R, s0, d_u8, hF, H))) return rc;
 
   size_t a_cells = 0, a_L = 0, a_stk = 0;
   for (int k = 0; k < n; k++) {
     const int L = R.len[s0 + k];
     State &Fk = hF[k];
+    ops.band(Fk);
     Fk.hp = d_i32 + o_hp;
     Fk.c = d_tab[0] + a_cells;
     Fk.fML = d_tab[1] + a_cells;
@@ -1397,15 +1431,12 @@ int fold_single(LongRows &R, int max_len, Ops &ops, int32_t *mfe_out, char *db_o
 }
 
 // What the triangular folds hand the driver: a row's tables hold SF_LONG_TRI(L) entries, the hairpin table reaches the
-// longest row, and the constraints are parsed on the device (int16 positions) by long_bind_rows.
+// longest row, and there is no band.
 struct TriRows {
   typedef SfLong State;
-  static const bool host_hc = false;
   size_t entries(int L) const { return SF_LONG_TRI(L); }
   int hairpin_entries(int Lmax) const { return Lmax; }
-  int bind(CallBufs &B, const LongPack &K, const LongRows &R, int s0, uint8_t *d_u8, std::vector<SfLong> &hF) {
-    return long_bind_rows(B, K, R, s0, d_u8, hF);
-  }
+  void band(SfLong &) const {}
 };
 
 // sf_fold_long's launches: the one row's state goes to its kernels by value, with the row's own lane groups and grids.
@@ -1465,97 +1496,14 @@ int band_group(int d, size_t cells) {
   return G;
 }
 
-// A constraint of any length, parsed on the host (sf_hc_parse with int32 positions) for sf_fold_banded and sf_pf_banded:
-// the host walks the row for balance anyway, and positions pass 32 767.
-struct BandHc {
-  std::vector<int32_t> part, encl;
-  std::vector<char> c;
-  // SF_ERR_CONSTRAINT for unbalanced brackets
-  int parse(const char *cons, int L) {
-    part.assign((size_t)L + 2, 0);
-    encl.assign((size_t)L + 2, 0);
-    c.assign((size_t)L + 2, 0);
-    std::vector<int32_t> stack;
-    for (int i = 1; i <= L; i++) {
-      const char ch = cons[i - 1];
-      c[i] = ch;
-      if (ch == ')') {
-        if (stack.empty()) return SF_ERR_CONSTRAINT;
-        const int o = stack.back();
-        stack.pop_back();
-        part[o] = i;
-        part[i] = o;
-      }
-      encl[i] = stack.empty() ? 0 : stack.back();
-      if (ch == '(') stack.push_back(i);
-    }
-    return stack.empty() ? SF_OK : SF_ERR_CONSTRAINT;
-  }
-  // uploads the three arrays (9 (L + 2) bytes) into allocations of Bf and binds them
-  int bind(CallBufs &Bf, SfHc32 &hc) const {
-    int rc;
-    char *dc;
-    int32_t *dp, *de;
-    const size_t n = c.size();
-    if ((rc = Bf.upload(&dc, c.data(), n, "constraint")) || (rc = Bf.upload(&dp, part.data(), n, "bracket partners")) ||
-        (rc = Bf.upload(&de, encl.data(), n, "enclosing pairs")))
-      return rc;
-    hc.c = dc;
-    hc.partner = dp;
-    hc.encl = de;
-    return SF_OK;
-  }
-};
-
-// What the banded folds hand fold_rows: a row's tables hold L B entries, B = min(S, L), the hairpin table reaches the widest
-// band, and the constraints are parsed here (BandHc), into one allocation of their own: the constrained rows' bracket
-// partners, enclosing pairs and characters, L + 2 of each a row.  long_rows_check has seen that every row balances.
+// What the banded folds hand fold_rows: a row's tables hold L B entries, B = min(S, L), and the hairpin table reaches the
+// widest band.
 struct BandRows {
   typedef SfBand State;
-  static const bool host_hc = true;
   const int S = g.max_bp_span;
-  std::vector<int32_t> h32;  // the parsed constraints as they are copied up (they outlive the driver's buffers)
-  std::vector<char> h8;
   size_t entries(int L) const { return (size_t)L * (size_t)std::min(S, L); }
   int hairpin_entries(int Lmax) const { return std::min(S, Lmax); }
-  int bind(CallBufs &B, const LongPack &K, const LongRows &R, int s0, uint8_t *d_u8, std::vector<SfBand> &hF) {
-    int rc;
-    size_t n_hc = 0, a_L = 0, a = 0;
-    for (size_t k = 0; k < hF.size(); k++)
-      if (R.constrained[s0 + k]) n_hc += (size_t)R.len[s0 + k] + 2;
-    h32.assign(2 * n_hc, 0);
-    h8.assign(n_hc, 0);
-    char *p = nullptr;
-    if (n_hc && (rc = B.alloc(&p, 9 * n_hc, "bracket partners, enclosing pairs, constraints"))) return rc;
-    const int32_t *d_part = (const int32_t *)p, *d_encl = d_part + n_hc;
-    const char *d_c = (const char *)(d_encl + n_hc);
-    HIPCHK(hipMemcpyAsync(d_u8, K.h8.data(), K.h8.size(), hipMemcpyHostToDevice, g.stream));
-    BandHc H;
-    for (size_t k = 0; k < hF.size(); k++) {
-      const int L = R.len[s0 + k];
-      SfBand &F = hF[k];
-      memset(&F, 0, sizeof F);
-      F.L = L;
-      F.B = std::min(S, L);
-      F.S = d_u8 + a_L + 2 * k;
-      if (R.constrained[s0 + k]) {
-        if ((rc = H.parse(R.cons + (size_t)(s0 + k) * R.ld, L))) return rc;
-        memcpy(h32.data() + a, H.part.data(), ((size_t)L + 2) * sizeof(int32_t));
-        memcpy(h32.data() + n_hc + a, H.encl.data(), ((size_t)L + 2) * sizeof(int32_t));
-        memcpy(h8.data() + a, H.c.data(), (size_t)L + 2);
-        F.hc.partner = d_part + a;
-        F.hc.encl = d_encl + a;
-        F.hc.c = d_c + a;
-        a += (size_t)L + 2;
-      }
-      a_L += (size_t)L;
-    }
-    if (n_hc) {
-      HIPCHK(hipMemcpyAsync(p, h32.data(), 8 * n_hc, hipMemcpyHostToDevice, g.stream));
-      HIPCHK(hipMemcpyAsync((char *)p + 8 * n_hc, h8.data(), n_hc, hipMemcpyHostToDevice, g.stream));
-    }
-    return SF_OK;
-  }
+  void band(SfBand &F) const { F.B = std::min(S, F.L); }
 };
 
 // sf_fold_banded's launches: the one row's state by value, one fill launch per diagonal of its band.
@@ -1836,6 +1784,7 @@ int pf_long_rows(const LongRows &R, const int32_t *hint, int s0, int n, Launch &
   const std::vector<double> hhp = pfl_hairpin_table(M, Lmax);
   std::vector<double> hpow(n_pow), hout(3 * (size_t)n);
   std::vector<SfPfLong> hF((size_t)n);
+  HcStage<SfPfLong> H;  // (before B: see HcStage)
   std::vector<char> hcen(n_L + (size_t)n);
 
   CallBufs B(R.who);
@@ -1844,8 +1793,8 @@ int pf_long_rows(const LongRows &R, const int32_t *hint, int s0, int n, Launch &
   for (int k = 0; k < SF_PFLONG_NTRI; k++)
     if ((rc = B.alloc(&d_tri[k], tri, kPfTableNames[k]))) return rc;
   if ((rc = B.alloc(&d_f64, n_f64, "results, scale powers, hairpin weights, q5, q3, partial sums"))) return rc;
-  if ((rc = B.alloc(&d_u8, n_u8, "sequences, constraints, centroids"))) return rc;
-  if ((rc = long_bind_rows(B, K, R, s0, d_u8, hF))) return rc;
+  if ((rc = B.alloc(&d_u8, n_u8, "sequences, centroids"))) return rc;
+  if ((rc = bind_rows(B, K, R, s0, d_u8, hF, H))) return rc;
 
   std::vector<size_t> pow_off((size_t)n), cen_off((size_t)n);
   size_t a_tri = 0, a_L = 0, a_part = 0;
@@ -2125,17 +2074,18 @@ int pf_banded_run(const char *who, const uint8_t *seq, int L, const char *cons, 
   int rc;
   if (!seq || L < 1 || L > SF_MAX_BANDED || g.max_bp_span < 1) return SF_ERR_BAD_ARG;
   const int B = std::min(g.max_bp_span, L);
-  BandHc H;  // unbalanced brackets end the call before any launch
-  if (cons && (rc = H.parse(cons, L))) return rc;
+  LongRows R = {seq, 1, L, &L, cons, who};  // the record as a batch's one row; unbalanced brackets end the call here
+  if ((rc = long_rows_check(R, SF_MAX_BANDED))) return rc;
 
   const Ctx::ModelSlot &M = g.slot[g.cur];
   const double kT = M.pf_kT, ln_mlbase = log(M.pf_MLbase);
   const size_t nL = (size_t)L, nB = (size_t)B, lanes = pfl_lanes();
   const int prob_waves = std::min(pfl_prob_waves(L, lanes), SF_PFBAND_MAX_WAVES);
-  std::vector<uint8_t> hS(nL + 2, 0);
-  for (int x = 0; x < L; x++) hS[x + 1] = sf_encode_nt(seq[x]);
+  const LongPack K = long_pack(R, 0, 1);
   const std::vector<double> hhp = pfl_hairpin_table(M, B);
-  // (these outlive Bf: the copies into them are drained by its destructor on an early return)
+  // (these outlive Bf: the copies out of and into them are drained by its destructor on an early return)
+  std::vector<SfPfBand> hF(1);
+  HcStage<SfPfBand> H;
   std::vector<double> hpow(2 * (nB + 2));
   std::vector<char> hcen(nL + 1);
   double hout[3] = {0, 0, 0};
@@ -2144,21 +2094,19 @@ int pf_banded_run(const char *who, const uint8_t *seq, int L, const char *cons, 
   // the partial sums of the probability pass.  SF_PF_BANDED_BYTES counts exactly these allocations.
   const size_t o_out = 0, o_pow = o_out + 4, o_hp = o_pow + 2 * (nB + 2), o_m5 = o_hp + nB + 1, o_m3 = o_m5 + nL + 2;
   const size_t o_part = o_m3 + nL + 2, n_f64 = o_part + 2 * (size_t)SF_PFBAND_MAX_WAVES;
-  SfPfBand F;
-  memset(&F, 0, sizeof F);
-  F.L = L;
-  F.B = B;
   CallBufs Bf(who);
   double *d_tab[SF_PFBAND_NTAB], *d_f64;
   uint8_t *d_u8;
   for (int k = 0; k < SF_PFBAND_NTAB; k++)
     if ((rc = Bf.alloc(&d_tab[k], nL * nB, kPfTableNames[k]))) return rc;
   if ((rc = Bf.alloc(&d_f64, n_f64, "results, scale powers, hairpin weights, q5, q3, partial sums"))) return rc;
+  if ((rc = Bf.alloc(&d_u8, K.o_end + nL + 1, "sequence, centroid"))) return rc;
+  if ((rc = bind_rows(Bf, K, R, 0, d_u8, hF, H))) return rc;
+  SfPfBand &F = hF[0];
+  F.B = B;
   if ((rc = Bf.alloc(&F.e5, 2 * (nL + 2), "exponents of q5 and q3"))) return rc;
   F.e3 = F.e5 + nL + 2;
-  if ((rc = Bf.alloc(&d_u8, 2 * nL + 3, "sequence, centroid"))) return rc;
-  F.S = d_u8;
-  F.cen = (char *)d_u8 + nL + 2;
+  F.cen = (char *)d_u8 + K.o_end;
   pfl_bind_tables(F, d_tab, 0);
   F.out = d_f64 + o_out;
   F.sc = d_f64 + o_pow;
@@ -2167,9 +2115,7 @@ int pf_banded_run(const char *who, const uint8_t *seq, int L, const char *cons, 
   F.m5 = d_f64 + o_m5;
   F.m3 = d_f64 + o_m3;
   F.part = d_f64 + o_part;
-  HIPCHK(hipMemcpyAsync(d_u8, hS.data(), nL + 2, hipMemcpyHostToDevice, g.stream));
   HIPCHK(hipMemcpyAsync(d_f64 + o_hp, hhp.data(), hhp.size() * sizeof(double), hipMemcpyHostToDevice, g.stream));
-  if (cons && (rc = H.bind(Bf, F.hc))) return rc;
   for (auto &e : Bf.ev) HIPCHK(hipEventCreate(&e));
 
   const SfDevParams *D = (const SfDevParams *)g.dP;

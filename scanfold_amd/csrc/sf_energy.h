@@ -232,8 +232,10 @@ __device__ __forceinline__ int sf_hc_type_of(const H &h, int t, int i, int j, bo
   return t;
 }
 
-// The same for records of any length (sf_mfe_banded.hip.h): positions past 32 767 need int32 partners.  The host parses the
-// constraint (it walks every row for balance anyway) and uploads the three arrays, filled for 1..L.
+// The same for records of any length (sf_mfe_banded.hip.h): positions past 32 767 need int32 partners.  For a whole record
+// the host parses the constraint (hc_parse_host in scanfold_hip.hip: it walks every row for balance anyway) and uploads the
+// three arrays, L + 2 entries each with 0 and L + 1 zero; with int32 positions here, with int16 ones into an SfHc in full
+// tables.
 struct SfHc32 {
   const char *c;           // 1-based (c[1..L]); null: no constraint
   const int32_t *partner;  // 0: none

@@ -26,7 +26,8 @@
 // value is an integer minimum: no grouping changes a result.
 // Then f5 (sequential in j, at most B terms a step) in one workgroup, and the traceback (sft_trace) in one workgroup.
 //
-// Bracket partners and enclosing pairs are int32 here (SfHc32), built on the host: positions pass 32 767.
+// Bracket partners and enclosing pairs are int32 here (SfHc32): positions pass 32 767.  The host builds them, as it does
+// the int16 ones of the full tables (hc_parse_host in scanfold_hip.hip).
 // Device memory of one call: 12 L B + 75 L + 4 B + 153 bytes (SF_BANDED_BYTES; the constraint's 9 (L + 2) included).
 #pragma once
 #include "sf_mfe_trace.hip.h"

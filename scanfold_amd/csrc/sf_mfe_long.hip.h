@@ -58,11 +58,6 @@ __device__ __forceinline__ const int32_t *sft_colp(const SfLong &, const int32_t
 __device__ __forceinline__ int sft_lo(const SfLong &, int) { return 1; }
 __device__ __forceinline__ bool sft_in(const SfLong &, int, int) { return true; }
 
-// The bracket partners and enclosing pairs of the constraint (sf_hc_parse) into device memory; one thread.
-__global__ void sf_long_hc_kernel(const char *src, int L, char *c, int16_t *partner, int16_t *encl, int16_t *stack, int *status) {
-  if (threadIdx.x == 0 && blockIdx.x == 0 && sf_hc_parse(src, L, c, partner, encl, stack)) atomicOr(status, 2);
-}
-
 // Cell i = cell + 1 of diagonal d, as lane r of the cell's group of G lanes (shared with sf_mfe_long_batch.hip.h).  Every lane
 // of a wave comes here, with or without a cell: the group's minimum is a butterfly over the wave.
 __device__ __forceinline__ void sfl_fill_cell(const SfLong &F, int d, int G, int r, size_t cell, const SfDevParams *__restrict__ D) {

@@ -23,7 +23,7 @@
 // of a cell's group stays inside one row.  A row with L_s <= d, and a workgroup whose first group lies past the row's cells,
 // return at once; in the row's last live workgroup the lanes past L_s - d walk the butterflies without a cell.
 // q5 / q3: one wave per row.  Probabilities: four waves per workgroup, the waves past the row's count return.  No grid
-// barrier and no floating-point atomics; the only atomic is the shared status word (sf_long_hc_kernel's).
+// barrier, no floating-point atomics and, since the host parses the constraints, no atomic at all.
 #pragma once
 #include "sf_pf_long.hip.h"
 

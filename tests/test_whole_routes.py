@@ -6,8 +6,8 @@ its neighbours: a record sent to the wrong one is only slower, or single where i
 length past the window limit, and compares the log, consecutive repeats collapsed, to a literal.  Span 100 is the widest with
 4 span <= 401 (banded tables), span 101 the first that stays in full tables.  The long and banded partition functions launch
 their inside and outside diagonals through a parameter, which the log spells `kernel`; the exterior kernel after it names the
-family.  A constraint with anything but dots in it adds `sf_long_hc_kernel`, which sets up its arrays, before a fold or a
-partition function in full tables (the banded ones have no such launch).  For the two drivers the Engine calls themselves are
+family.  A constraint adds no launch in either layout: the host parses it and copies its arrays up.  For the two drivers
+the Engine calls themselves are
 recorded too, with their constraints: the MFE folds run in the order -1, -2, free and the ensembles in the order free, -1, -2.
 The first half of this file (15 cases) was written against the code as it stood before scanfold_amd/whole.py owned the
 routing and passes there unchanged; the second half checks the router's pure functions at every edge, the pre-flight checks
@@ -36,7 +36,7 @@ PF_LONG = ["kernel", "sf_pflong_exterior_kernel", "kernel", "sf_pflong_prob_kern
 PF_BAND = ["kernel", "sf_pfband_exterior_kernel", "kernel", "sf_pfband_prob_kernel", "sf_pfband_finish_kernel"]
 PF_LONGB = ["sf_pflongb_inside_kernel", "sf_pflongb_exterior_kernel", "sf_pflongb_outside_kernel", "sf_pflongb_prob_kernel",
             "sf_pflongb_finish_kernel"]
-HC = ["sf_long_hc_kernel"]  # a constraint with anything but dots in it: its arrays, before a fold in full tables
+HC = []  # a constraint adds no launch: the host parses it
 LONG_MFE_X3 = (HC + LONG) * 2 + LONG  # the driver's three folds: -1, -2, free
 WHOLE = ("fold_long", "fold_long_batch", "fold_banded", "fold_banded_batch", "pf_long", "pf_long_batch", "pf_banded")
 
