@@ -1486,6 +1486,18 @@ enum SfStep {
 };
 template <SfStep K>
 using SfStepTag = std::integral_constant<SfStep, K>;
+// Narrow kernel, split steps: what a wave does there, decided once per fold (wave-uniform: the wave's index in the workgroup).  The
+// step body is instantiated per role, with the role's conditions compile-time constants, and every role runs split loops of its
+// own: what only another role keeps across steps is not live in this one's loops.
+enum SfRole {
+  SF_ROLE_ALL,        // every other loop, and the wide kernel: the roles are wave-uniform branches of one body
+  SF_ROLE_MAIN_EVEN,  // wave 0: the cells of d0 — two-cells-per-lane multiloop split, recurrence, finish, fML fix-up of d0 + 1
+  SF_ROLE_MAIN_ODD,   // wave 2: the cells of d0 + 1 — the same without the fix-up
+  SF_ROLE_HELP_EVEN,  // wave 1: the special loops and bulges of wave 0's cells, or of the merged list's entries 0..63
+  SF_ROLE_HELP_ODD,   // wave 3: the same for wave 2's cells (merged: entries 64..), the next step's list, the trailing sweep
+};
+template <SfRole R>
+using SfRoleTag = std::integral_constant<SfRole, R>;
 
 // the poison build's pattern for int16 entry x (see PZ below)
 __device__ __forceinline__ int16_t sf_poison16(const int poison, const int x) {
@@ -1557,6 +1569,8 @@ __global__ __launch_bounds__(2 * NG, SF_FAST_WAVES_PER_SIMD) void sf_mfe_fast_ke
   // split, the width a compile-time constant in each (W = 120: 56.2 -> 55.4 ms per 262 144 folds, W = 100 +1.4 %; the instantiation
   // without the merged helper, W = 118 .. 128, measured 1.2 % slower with it)
   constexpr bool LGLOOPS = MG && (NG == 128);
+  // ... and, in the narrow kernel, every split loop once per role of a wave (SfRole)
+  constexpr bool ROLE_LOOPS = (NG == 128);
   // rolling-row offsets from SfFastRows (see sf_fast_cell): 1 = yes, 2 = yes + the long read batches of the generic merged-helper
   // instantiation, 0 = no (the generic wide kernel)
   constexpr int TBLK = WT > 0 ? 1 : (NG == 128 ? (MG ? 2 : 1) : 0);
@@ -1733,15 +1747,26 @@ __global__ __launch_bounds__(2 * NG, SF_FAST_WAVES_PER_SIMD) void sf_mfe_fast_ke
     };
 // @section step_control
     // One step = the diagonals d0 (even group) and d0 + 1 (odd group).  The body is instantiated once per kind of step (SfStep).
+    // It is also instantiated once per role of a wave (SfRole; the narrow kernel's split steps): group, helper and sweeper are
+    // compile-time constants there, and the body keeps only that role's code — with the same two barriers in the same order.
     SfHU HU;
-    auto step = [&](const int d0, auto kind_tag) {
+    const int grp_wave = grp;
+    const bool sweeper_wave = sweeper;
+    auto step = [&](const int d0, auto kind_tag, auto role_tag) {
       constexpr SfStep KIND = decltype(kind_tag)::value;
+      constexpr SfRole ROLE = decltype(role_tag)::value;
+      constexpr bool ROLES = ROLE != SF_ROLE_ALL;
+      static_assert(!ROLES || (NG == 128 && KIND >= SF_STEP_SPLIT && KIND <= SF_STEP_SPLIT8), "roles: the narrow kernel's split steps");
+      const int grp = ROLES ? (int)(ROLE == SF_ROLE_MAIN_ODD || ROLE == SF_ROLE_HELP_ODD) : grp_wave;
+      const bool hwave = ROLES ? ROLE >= SF_ROLE_HELP_EVEN : tg >= 64;  // narrow kernel: the second wave of a group
+      const bool sweeper = ROLES ? ROLE == SF_ROLE_HELP_ODD : sweeper_wave;
       // lanes per chunk of the two-cells-per-lane multiloop split, as a power of two (0: sf_fast_dml2 derives it from d)
       constexpr int LGC = KIND == SF_STEP_SPLIT16 ? 4 : (KIND == SF_STEP_SPLIT8 ? 3 : (KIND == SF_STEP_SPLIT && LGLOOPS ? 5 : 0));
       constexpr bool DO_G = KIND == SF_STEP_SIZED, DO_CH = KIND == SF_STEP_GUARDED;
       const int d = d0 + grp;
-      if (d0 == SFD_TURN + 1 + 2 && tid == 0) *next_slot = fetched;            // the barriers of this step publish it
-      if (d0 == SFD_TURN + 1 + 4) next_seq = SF_WAVE_UNIFORM(*next_slot);
+      // (the second and third step of a fold, long before the split steps — split_d0 > SFD_MAXLOOP: not in the role bodies)
+      if (!ROLES && d0 == SFD_TURN + 1 + 2 && tid == 0) *next_slot = fetched;  // the barriers of this step publish it
+      if (!ROLES && d0 == SFD_TURN + 1 + 4) next_seq = SF_WAVE_UNIFORM(*next_slot);
       // Split steps (the long diagonals, d0 >= split_d0): the cells of a group fit its first wave, so the second wave — which would
       // idle — mirrors it (same lane -> same cell) and takes the special loops and the bulge / 1xn minima of
       // those cells, while the first does the generic-loop recurrence and the multiloop split; the partial
@@ -1769,7 +1794,7 @@ __global__ __launch_bounds__(2 * NG, SF_FAST_WAVES_PER_SIMD) void sf_mfe_fast_ke
         }
         __syncthreads();
       }
-      const bool helper = split && (NG == 256 ? (narrow ? tg < 64 : (tg < 64 || tg >= 192)) : tg >= 64);
+      const bool helper = split && (NG == 256 ? (narrow ? tg < 64 : (tg < 64 || tg >= 192)) : hwave);
       const int vh = NG == 256 ? (narrow ? v + 96 : (tg < 64 ? v + 64 : v - 64)) : v - 64;
       // (narrow: lanes 64..127 take the cells of lanes 96..159, lanes 0..63 mirror them; lanes >= 128 have no cell)
       const int vm = narrow ? ((v + 32) & (NG - 1)) : v;
@@ -1869,7 +1894,7 @@ __global__ __launch_bounds__(2 * NG, SF_FAST_WAVES_PER_SIMD) void sf_mfe_fast_ke
       }
       if (sweep_now && sweep_rows > 0) sf_trail_rows<NQ, DROWS>(T, tid & 63, sweep_rows, dc);
       // merged helper: wave 3 lists the next step's cells (the barriers of this step order the list before its readers)
-      if (MERGE && grp == 1 && tg >= 64 && d0 + 2 >= split_d0 && d0 + 2 < W) build_list(d0 + 2);
+      if (MERGE && grp == 1 && hwave && (ROLES || d0 + 2 >= split_d0) && d0 + 2 < W) build_list(d0 + 2);
 // @section exchange
       if (split) {
         __syncthreads();
@@ -1918,22 +1943,47 @@ __global__ __launch_bounds__(2 * NG, SF_FAST_WAVES_PER_SIMD) void sf_mfe_fast_ke
       // One loop per kind of step, in SfStep's order.
       // UNPK: the state is unpacked at d0 = 36 — the first diagonal pair on which every loop size exists (the guarded code before it
       // needs the saturating packed adds; unpacked with v_add_i16 clamp it measured slower: 58.8 ms).
-      for (; d0 < SF_FAST_TINY_D0 && d0 < W; d0 += 2) step(d0, SfStepTag<SF_STEP_SIZED>{});
-      for (; d0 < SF_FAST_CHUNK_D0 && d0 < W; d0 += 2) step(d0, SfStepTag<SF_STEP_GUARDED>{});
+      constexpr SfRoleTag<SF_ROLE_ALL> all_roles{};
+      for (; d0 < SF_FAST_TINY_D0 && d0 < W; d0 += 2) step(d0, SfStepTag<SF_STEP_SIZED>{}, all_roles);
+      for (; d0 < SF_FAST_CHUNK_D0 && d0 < W; d0 += 2) step(d0, SfStepTag<SF_STEP_GUARDED>{}, all_roles);
       if constexpr (UNPK) {
 #pragma unroll
         for (int x = 0; x < 27; x++) HU.v[x] = (short)((x & 1) ? (H[x >> 1] >> 16) : (H[x >> 1] & 0xffffu));
       }
-      for (; d0 < split_d0 && d0 < W; d0 += 2) step(d0, SfStepTag<SF_STEP_UNSPLIT>{});
-      if constexpr (LGLOOPS) {
-        // (chunks of 32 lanes while a diagonal has more than 30 cells, 16 down to 15 cells, then 8: d0 >= W - 30 / W - 14)
-        for (; d0 < W - 30 && d0 < W; d0 += 2) step(d0, SfStepTag<SF_STEP_SPLIT>{});
-        for (; d0 < W - 14 && d0 < W; d0 += 2) step(d0, SfStepTag<SF_STEP_SPLIT16>{});
-        for (; d0 < W; d0 += 2) step(d0, SfStepTag<SF_STEP_SPLIT8>{});
+      for (; d0 < split_d0 && d0 < W; d0 += 2) step(d0, SfStepTag<SF_STEP_UNSPLIT>{}, all_roles);
+      // The split steps: in the narrow kernel (ROLE_LOOPS) every wave runs them as loops of its own role — a wave-uniform branch
+      // taken once per fold, then the role's instantiation of the step body.  The waves of a workgroup meet at the barriers of
+      // different loops: every role body has the exchange barrier and the end-of-step barrier, in that order, once per step.
+      // The main waves' loops no longer carry the sweeper's rows in flight and list code, the helpers' loops not the recurrence
+      // state: W = 120 53.4 -> 51.6 ms per 262 144 folds, W = 64 / 100 / 117 +3.8 / 4.3 / 4.1 %, W = 118 / 128 +1.4 / 1.6 %; with ONE main
+      // role for both groups (the group a wave-uniform value) W = 120 measured 51.9 ms (profiles/role_loops/README.md).
+      auto split_loops = [&](auto role_tag) {
+        if constexpr (LGLOOPS) {
+          // (chunks of 32 lanes while a diagonal has more than 30 cells, 16 down to 15 cells, then 8: d0 >= W - 30 / W - 14)
+          for (; d0 < W - 30 && d0 < W; d0 += 2) step(d0, SfStepTag<SF_STEP_SPLIT>{}, role_tag);
+          for (; d0 < W - 14 && d0 < W; d0 += 2) step(d0, SfStepTag<SF_STEP_SPLIT16>{}, role_tag);
+          for (; d0 < W; d0 += 2) step(d0, SfStepTag<SF_STEP_SPLIT8>{}, role_tag);
+        }
+        for (; d0 < W; d0 += 2) step(d0, SfStepTag<SF_STEP_SPLIT>{}, role_tag);
+      };
+      if constexpr (ROLE_LOOPS) {
+        const int wave = SF_WAVE_UNIFORM(tid >> 6);
+        if (wave == 0) split_loops(SfRoleTag<SF_ROLE_MAIN_EVEN>{});
+        else if (wave == 2) split_loops(SfRoleTag<SF_ROLE_MAIN_ODD>{});
+        else if (wave == 1) split_loops(SfRoleTag<SF_ROLE_HELP_EVEN>{});
+        else split_loops(SfRoleTag<SF_ROLE_HELP_ODD>{});
+        // (only wave 3 has a trailing sweep: in the others its state never leaves these values, and saying so here keeps it out of
+        // their loops' registers)
+        if (wave != 3) {
+#pragma unroll
+          for (int q = 0; q < NQ; q++) T.F[q] = 0;
+          T.f3n = 0; T.row = 0;
+        }
+      } else {
+        for (; d0 < (NARROW ? narrow_d0 : W) && d0 < W; d0 += 2) step(d0, SfStepTag<SF_STEP_SPLIT>{}, all_roles);
       }
-      for (; d0 < (NARROW ? narrow_d0 : W) && d0 < W; d0 += 2) step(d0, SfStepTag<SF_STEP_SPLIT>{});
       if constexpr (NARROW)
-        for (; d0 < W; d0 += 2) step(d0, SfStepTag<SF_STEP_NARROW>{});
+        for (; d0 < W; d0 += 2) step(d0, SfStepTag<SF_STEP_NARROW>{}, all_roles);
     }
 
 // @section fold_epilogue
