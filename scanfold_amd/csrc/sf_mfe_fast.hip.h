@@ -5,8 +5,9 @@
 //
 // One workgroup folds one sequence at a time (persistent grid; a workgroup's first fold is its block index, every further one comes
 // from a device-wide counter); two anti-diagonals per step (two thread groups), one barrier per step (two on the long diagonals).
-// The steps of a fold run as one loop PER KIND of step — size-tested / guarded / unsplit / split (and finer: SfStep, the
-// loops at the end of the kernel) — because each loop then gets its own register allocation and schedule: +5-8 % at every width.
+// The steps of a fold run as one loop PER KIND of step — size-tested / short (guarded in the wide and the constrained kernels) /
+// unsplit / split (and finer: SfStep, the loops at the end of the kernel) — because each loop then gets its own register
+// allocation and schedule: +5-8 % at every width.
 // Thread mapping: a thread owns a CENTRE s = i+j (two centres, one per parity of d):
 // on diagonal d it handles the cell i = v - d/2, j = i+d with v = (tid+OFF) mod NT.  The cell of the same
 // thread two diagonals later is (i-1, j+1), the cell that encloses it — which makes the interior-loop search
@@ -48,6 +49,9 @@
 // sets whose entries exceed SF_FAST_MAXPARAM in magnitude are routed to the int32 kernel entirely.
 #pragma once
 #include <type_traits>
+#ifdef SF_EMUL
+#include <vector>
+#endif
 #include "sf_energy.h"
 #include "sf_pk16.h"
 
@@ -62,8 +66,24 @@
 // even diagonals below this one skip whole batches of loop sizes above the limit (CH); from here to 36 the skipped
 // work is small and the unbroken straight-line code is faster (measured: 20 / 24 / 28 / 36 -> 87.5 / 87.1 / 87.0 / 87.9 ms)
 #define SF_FAST_CHUNK_D0 36
+// Narrow kernels without a per-fold constraint: the steps from SF_FAST_TINY_D0 on run the all-sizes code, unguarded and unpacked, on
+// the plain size tables — a size that does not exist on a diagonal reads ring rows no diagonal of the fold has written yet, which
+// the fold's prologue set to "none" (tests/test_unguarded_sizes.py holds that, read by read).  Three loops (SF_STEP_SHORT_A / B / C):
+// d0 < D1 with the loop sizes above D1 - 7 not instantiated, d0 < D2 with those above D2 - 7, d0 < D3 with all; from D3 = 32 on
+// the unsplit loop's own body is safe as it stands (see the bulge / 1xn rows in sf_fast_cell).
+// (boundaries measured: profiles/guarded_unpacked/README.md)
+#ifndef SF_FAST_SHORT
+#define SF_FAST_SHORT 1
+#endif
+#ifndef SF_FAST_SHORT_D1
+#define SF_FAST_SHORT_D1 18
+#endif
+#ifndef SF_FAST_SHORT_D2
+#define SF_FAST_SHORT_D2 26
+#endif
+#define SF_FAST_SHORT_D3 32
 #ifndef SF_FAST_UNPACK
-#define SF_FAST_UNPACK 1  // narrow kernels, from d0 = 36 on: the generic-loop recurrence on full-rate 16-bit instructions (SfHU)
+#define SF_FAST_UNPACK 1  // narrow kernels, from d0 = 10 on (constrained: 36): the generic-loop recurrence on full-rate 16-bit instructions (SfHU)
 #endif
 #ifndef SF_UNP_PB
 #define SF_UNP_PB 4  // size pairs per batch of reads in the unpacked recurrence (3 / 4 / 6 / 12: 58.0 / 57.5 / 58.6 / 58.3 ms per 262 144 folds)
@@ -272,9 +292,17 @@ static inline __host__ __device__ SfFastLayout sf_fast_layout(int W, bool hc = f
   if (W < SF_HELP_MERGE_MAXW) o += 2 * 128;
   // (What follows the rolling tables matters: on the short diagonals the straight-line cell code reads candidates of
   // loop sizes that do not exist yet — up to 23 words past the end of a row, past the end of the last row into
-  // whatever comes next — and relies on finding energy-sized values there (they get a weight of 32767 and saturate).
-  // The mirror row and the parameter tables are that; the cell list is never in reach where it is written (W >= 64),
-  // and is filled with "no structure" where it is not; the two control words below sit behind the tables.)
+  // whatever comes next.  Two kinds of code do that, and they rely on different things:
+  //  - the guarded steps (SF_STEP_GUARDED: the wide kernel and the constrained instantiations) charge such a size 32767 and
+  //    saturate, so they only need energy-sized values there: the mirror row and the parameter tables are that; the cell list is
+  //    never in reach where it is written (W >= 64), and is filled with "no structure" where it is not;
+  //  - the unguarded steps (SF_STEP_SHORT_A / B / C, the other narrow instantiations) need exactly "none" there.  Everything from
+  //    off_ci up to off_tab starts every fold as "none" (the fold prologue), every row such a read addresses is the ring slot of a
+  //    diagonal still to come, and no such read gets past off_tab — the one that would, the bulge / 1xn size d - 2 through the
+  //    mirror row, takes its own row instead (sf_fast_cell, SHORT).  With W <= 36 the last four lanes of size d - 1 read up to
+  //    four words of the cell lists, which are not written before d0 = 34.  tests/test_unguarded_sizes.py checks all of it
+  //    read by read (sf_emul_check_absent).
+  // The two control words below sit behind the tables.)
   L.off_tab = o; o += SF_FAST_TAB_BYTES;
   L.off_flag = o; o += 4;
   L.off_next = o; o += 4;  // index of the workgroup's next fold (dynamic distribution)
@@ -391,13 +419,6 @@ __device__ __forceinline__ void sf_fast_split_stretch(const int16_t *pa, const i
 #undef SF_SPLIT_REDUCE
 }
 
-// (CB, C1N) of the cell at column i0 of a row into the interleaved bulge / 1xn table; w points at the cell's own word.
-// The C1N half belongs in the previous word (column 0's is never read: 1xn candidates start at column 2).
-__device__ __forceinline__ void sf_fast_publish_bn(int16_t *w, const int i0, const uint32_t bn) {
-  w[0] = (int16_t)sf_lo(bn);
-  if (i0 > 0) w[-1] = (int16_t)sf_hi(bn);
-}
-
 // Entry idx of an int16 table inside the parameter block (wave-uniform base F): the byte offset — the table's place in the block
 // included — is formed in 32 bits, so that the load is "scalar base + 32-bit vector offset" (global_load saddr).  From
 // F->tab[idx] the compiler builds a 64-bit address per lane (v_mad_u64_u32, v_lshl_add_u64, add / addc with carry: ~5
@@ -438,7 +459,75 @@ static inline void sf_emul_check_ci_row(const int16_t *row_ptr, long lane_entrie
     abort();
   }
 }
+// TEST BUILD ONLY: a shadow byte per int16 entry of what a fold's prologue sets to "none" — the two rolling tables with their mirror
+// rows and, where the layout has them there, the cell lists behind them (SfFastLayout: off_ci up to off_tab).  0: initialised by this
+// fold's prologue; 1: written by a diagonal of this fold (or by a helper / the list builder); 2: left over from the previous fold.
+// The unguarded all-sizes code reads candidates of loop sizes that do not exist on its diagonal (sf_fast_cell): every such read of a
+// valid lane must lie inside that span and find shadow 0 — then the value it reads is "none" whatever the sequence.
+static thread_local std::vector<unsigned char> sf_emul_shadow;
+static thread_local const char *sf_emul_span_lo = nullptr, *sf_emul_span_hi = nullptr;
+static inline void sf_emul_shadow_span(const char *lo, const char *hi) {
+  sf_emul_span_lo = lo; sf_emul_span_hi = hi;
+  if (sf_emul_shadow.size() != (size_t)(hi - lo) / 2) sf_emul_shadow.assign((size_t)(hi - lo) / 2, 2);
+}
+static inline void sf_emul_shadow_set(const void *p, int n16, unsigned char v) {
+  const char *q = (const char *)p;
+  if (!sf_emul_span_lo || q < sf_emul_span_lo || q + 2 * n16 > sf_emul_span_hi) return;  // (stores outside the span are not its business)
+  for (int k = 0; k < n16; k++) sf_emul_shadow[(size_t)(q - sf_emul_span_lo) / 2 + k] = v;
+}
+static inline void sf_emul_check_absent(const void *p, int n16, int d, int u) {
+  const char *q = (const char *)p;
+  if (!sf_emul_span_lo) return;
+  if (q < sf_emul_span_lo || q + 2 * n16 > sf_emul_span_hi) {
+    fprintf(stderr, "sf_mfe_fast (emulation): read for loop size %d, absent on diagonal %d, outside the rolling tables and their mirror rows (%ld bytes past their end)\n",
+            u, d, (long)(q + 2 * n16 - sf_emul_span_hi));
+    abort();
+  }
+  for (int k = 0; k < n16; k++) {
+    const int s = sf_emul_shadow[(size_t)(q - sf_emul_span_lo) / 2 + k];
+    if (s != 0) {
+      fprintf(stderr, "sf_mfe_fast (emulation): read for loop size %d, absent on diagonal %d, finds an entry %s (entry %ld of the rolling tables)\n",
+              u, d, s == 1 ? "a diagonal of this fold has written" : "this fold's prologue has not initialised", (long)((q - sf_emul_span_lo) / 2 + k));
+      abort();
+    }
+  }
+}
+// The check's own test (tests/test_unguarded_sizes.py; does not return when the check works).  On the layout of width W, freshly
+// "initialised": what = 0 — a read for size 5, absent on diagonal 10, aimed at an entry marked written; what = 1 — one aimed behind
+// the bulge / 1xn mirror row and what the prologue initialises behind it (W = 120: the first word of the parameter tables).
+extern "C" int sfemul_absent_check_selftest(int W, int what) {
+  const SfFastLayout L = sf_fast_layout(W);
+  static std::vector<char> lds;
+  lds.assign((size_t)L.total, 0);
+  sf_emul_shadow_span(lds.data() + L.off_ci, lds.data() + L.off_tab);
+  sf_emul_shadow_set(lds.data() + L.off_ci, (L.off_tab - L.off_ci) / 2, 0);
+  if (what == 0) {
+    const int16_t *e = (const int16_t *)(lds.data() + L.off_ci) + 3 * (W - 4) + 3;
+    sf_emul_check_absent(e, 1, 10, 5);  // untouched: passes
+    sf_emul_shadow_set(e, 1, 1);
+    sf_emul_check_absent(e, 1, 10, 5);
+  } else {
+    sf_emul_check_absent(lds.data() + L.off_tab - 4, 2, 10, 8);  // the last initialised word: passes
+    sf_emul_check_absent(lds.data() + L.off_tab, 2, 10, 8);
+  }
+  return 0;
+}
+#define SF_EMUL_WROTE(p, n16) sf_emul_shadow_set((p), (n16), 1)
+// reads of n16 int16 entries at p for loop size u on diagonal d, by the unguarded all-sizes code (CHK: that code, compile time)
+#define SF_EMUL_ABSENT(CHK, p, n16, d, u) do { if ((CHK) && (u) > (d) - 2 - (SFD_TURN + 1)) sf_emul_check_absent((p), (n16), (d), (u)); } while (0)
+#else
+#define SF_EMUL_WROTE(p, n16) ((void)0)
+#define SF_EMUL_ABSENT(CHK, p, n16, d, u) ((void)0)
 #endif
+
+// (CB, C1N) of the cell at column i0 of a row into the interleaved bulge / 1xn table; w points at the cell's own word.
+// The C1N half belongs in the previous word (column 0's is never read: 1xn candidates start at column 2).
+__device__ __forceinline__ void sf_fast_publish_bn(int16_t *w, const int i0, const uint32_t bn) {
+  w[0] = (int16_t)sf_lo(bn);
+  if (i0 > 0) w[-1] = (int16_t)sf_hi(bn);
+  SF_EMUL_WROTE(w, 1);
+  if (i0 > 0) SF_EMUL_WROTE(w - 1, 1);
+}
 
 // One anti-diagonal for one thread.  H: this parity's per-size minima of the generic candidates of the
 // enclosed cell (i+1, j-1) on entry, of (i, j) on exit.  slot2 = (d-2) mod NR, slotd = d mod NR.
@@ -458,13 +547,13 @@ static inline void sf_emul_check_ci_row(const int16_t *row_ptr, long lane_entrie
 //                dependent LDS round trips
 enum { SF_SEC_P1 = 1, SF_SEC_HELP = 2, SF_SEC_DML = 4, SF_SEC_FIN = 8, SF_SEC_C0 = 16, SF_SEC_ALL = 31, SF_SEC_PRE = 32,
        SF_SEC_POST = 64 };
-// UNP (the narrow kernels' steps from d0 = 36 on): the per-size minima of the generic-loop recurrence one int16 per register
+// UNP (the narrow kernels' steps from d0 = 10 on; from 36 on in the constrained instantiations): the per-size minima of the generic-loop recurrence one int16 per register
 // instead of two.  On MI355X every packed (VOP3P) instruction and the v_lshl_or that packs two 16-bit reads issue at half the rate
 // of the 16-bit VOP2 forms v_min_i16 / v_add_u16 (profiles/r04/mfe_issue_rates.json), so a size pair costs 5 half-rate + 1
 // full-rate vector instructions packed and 7 full-rate ones unpacked: 10.6 against 7.4 ns of a SIMD's vector time.  27
-// registers instead of 14: affordable because the unsplit and the split steps are loops of their own (the kernel converts the
-// state once, where the guarded steps end).  No saturation is needed: every size exists on these diagonals (no guarded weights),
-// and INF16 + a parameter < 32767.  The guarded steps (v_add_i16 clamp: half-rate again) and the wide kernel measured slower
+// registers instead of 14: affordable because the steps that use it are loops of their own (the kernel converts the state once,
+// where they begin).  No saturation is needed: the size terms are the plain ones (no guarded weights) — a size that does not exist
+// on a short diagonal reads "none" (SHORT below) — and INF16 + a parameter < 32767.  The guarded steps (v_add_i16 clamp: half-rate again) and the wide kernel measured slower
 // with it and stay packed (profiles/r05/EXPERIMENTS.md).
 struct SfHU {
   short v[27];  // v[x]: minimum over the generic candidates of total size x + 4
@@ -476,16 +565,20 @@ struct SfPub {
   int type;    // the cell's pair type (constraint applied): the finish after the barrier does not look it up again — two
                // dependent LDS round trips (nucleotides, then the pair table) at the head of a phase every other wave waits for
 };
-// UCAP (G code only): compile-time bound on the loop sizes that can exist — d <= 7: 1, d <= 11: 5 — so that the unrolled
+// UCAP: compile-time bound on the loop sizes that can exist.  G code — d <= 7: 1, d <= 11: 5 — so that the unrolled
 // size tests above it (a scalar compare + branch each, ~110 of them) disappear from the first four steps of a fold, which
-// cost as much as full steps before (profiles/r03/mfe_step_profile.txt).
+// cost as much as full steps before (profiles/r03/mfe_step_profile.txt).  All-sizes code (the SHORT loops): the sizes above it are
+// not instantiated — on no diagonal of the loop's range do they exist, and their minima keep the "none" they start a fold with.
+// SHORT (narrow kernels, SF_FAST_TINY_D0 <= d < 36, all-sizes code): some loop sizes do not exist on the diagonal yet.  Nothing tests
+// for them: the rows they address are ring slots of diagonals still to come, "none" since the fold's prologue, and "none" plus the
+// plain size terms stays "none" without saturation.  The one read that would leave those rows is dealt with at the bulge / 1xn rows.
 // TBLK: the rolling rows' offsets come from the SfFastRows table (scalar loads) instead of the ring arithmetic — the kernel
 // decides per instantiation (measured: +4 % at W = 120 / 200, +3 % at W = 128; the merged-helper instantiation lost 1-2 % while it
 // spilled and gains 1-3 % since the round-4 pins — W = 64 +1.0, 77 +1.8, 100 +1.4, 117 +3.1 %; the generic wide instantiation, which
 // still spills, keeps the arithmetic)
 // @section cell_setup
 template <bool G, int WT, int SEC, bool CH = false, bool FOLD = false, int UCAP = SFD_MAXLOOP, int TBLK = 1, bool MGH = false,
-          bool UNP = false>
+          bool UNP = false, bool SHORT = false>
 __device__ __forceinline__ void sf_fast_cell(const SfFastCtx &X, const int d, const int i, const bool valid,
                                              const int slot2, const int slotd, uint32_t (&HP)[14], SfHU &HU, int &ovf,
                                              const bool final_fml, const int fnb, int &fpart, int &dec, int &eh, int &e0,
@@ -560,6 +653,8 @@ __device__ __forceinline__ void sf_fast_cell(const SfFastCtx &X, const int d, co
 #define ROW(u) ((slot2 - (u) < 0 ? slot2 - (u) + SF_FAST_NR : slot2 - (u)) * RW)
   // TBL (the all-sizes code): the rows' byte offsets come from SfFastRows — scalar loads of consecutive entries
   constexpr bool TBL = !G && TBLK != 0;
+  constexpr int UTOP = (!G && UCAP < SFD_MAXLOOP) ? UCAP : SFD_MAXLOOP;  // all-sizes code: the largest size instantiated
+  constexpr bool UNG = !G && !CH;  // unguarded: what it reads for a size absent on the diagonal must be "none" (SF_EMUL_ABSENT)
   const SfFastRows *const Rc = TBL ? sf_const_base(X.R) : X.R;  // (the base is pinned by a volatile asm: only where it is used)
   const int32_t *const rci_o = Rc->ci_odd[slot2], *const rci_e = Rc->ci_even[slot2];
   const int32_t *const rbn_o = Rc->bn_odd[slot2], *const rbn_e = Rc->bn_even[slot2];
@@ -575,9 +670,11 @@ __device__ __forceinline__ void sf_fast_cell(const SfFastCtx &X, const int d, co
     const int32_t *const nin = Fc->NIN;  // wave-uniform: scalar loads of whole runs of the table
     // every candidate read of a batch is issued before the first is used: a pass is SF_UNP_PB-pair batches = that many dependent
     // LDS round trips — under load the round trip, not the arithmetic, is what a main wave's step consists of
+    static_assert(!UNP || UTOP >= 7, "the unpacked recurrence keeps at least the sizes 6 and 7");
     short r30a = 0, r30b = 0;
-    {
+    if (UTOP >= 30) {
       const int16_t *row = CIROW(30) + i0;
+      SF_EMUL_ABSENT(true, row + 3, 1, d, 30); SF_EMUL_ABSENT(true, row + 29, 1, d, 30);
       r30a = row[3]; r30b = row[29];
     }
     constexpr int PB = SF_UNP_PB;
@@ -586,23 +683,25 @@ __device__ __forceinline__ void sf_fast_cell(const SfFastCtx &X, const int d, co
       short a3[PB], au[PB], b3[PB], bu[PB];
 #pragma unroll
       for (int k = 0; k < PB; k++) {
-        if (pb - k >= 1) {
+        if (pb - k >= 1 && 2 * (pb - k) + 4 <= UTOP) {  // (a pair (u, u + 1) goes with its even size)
           const int u = 2 * (pb - k) + 4;
           const int16_t *rb = CIROW(u + 1) + i0, *ra = rb + RW;  // row u is the row after row u + 1 (mirror row at the ring's seam)
 #ifdef SF_EMUL
           sf_emul_check_ci_row(ra, i0, RW, FOLD); sf_emul_check_ci_row(rb, i0, RW, FOLD);
 #endif
+          SF_EMUL_ABSENT(true, ra + 3, 1, d, u); SF_EMUL_ABSENT(true, ra + u - 1, 1, d, u);
+          SF_EMUL_ABSENT(true, rb + 3, 1, d, u + 1); SF_EMUL_ABSENT(true, rb + u, 1, d, u + 1);
           a3[k] = ra[3]; au[k] = ra[u - 1];  // size u:     u1 = 2, u2 = 2
           b3[k] = rb[3]; bu[k] = rb[u];      // size u + 1
         }
       }
-      if (pb == 12) {
+      if (pb == 12 && UTOP >= 30) {
         const short e = (short)(sf_opaque16(sfd_min16(r30a, r30b)) + (short)nin[26]);
         HU.v[26] = sf_opaque16(sfd_min16(e, HU.v[24]));
       }
 #pragma unroll
       for (int k = 0; k < PB; k++) {
-        if (pb - k >= 1) {
+        if (pb - k >= 1 && 2 * (pb - k) + 4 <= UTOP) {
           const int x = 2 * (pb - k);  // size u = x + 4
           const short ea = (short)(sf_opaque16(sfd_min16(a3[k], au[k])) + (short)nin[x]);
           const short eb = (short)(sf_opaque16(sfd_min16(b3[k], bu[k])) + (short)nin[x + 1]);
@@ -613,6 +712,7 @@ __device__ __forceinline__ void sf_fast_cell(const SfFastCtx &X, const int d, co
     }
     {
       const int16_t *row = CIROW(5) + i0;
+      SF_EMUL_ABSENT(true, row + 3, 2, d, 5); SF_EMUL_ABSENT(true, CIROW(4) + i0 + 3, 1, d, 4);
       HU.v[1] = (short)(sfd_min16((short)row[3], (short)row[4]) + (short)nin[1]);
       HU.v[0] = (short)((short)(CIROW(4) + i0)[3] + (short)nin[0]);
     }
@@ -731,7 +831,8 @@ __device__ __forceinline__ void sf_fast_cell(const SfFastCtx &X, const int d, co
       }
       if (!G || (UCAP >= 5 && umax >= 5)) {  // 2 x 3 and 3 x 2
         const int16_t *row = BNROWB(ROWB_BN(5));
-        const int m23 = X.t23[SF_TIDX(type, si1, sj1)] + Fc->L23;
+        SF_EMUL_ABSENT(UNG, row + 2 * 3, 1, d, 5); SF_EMUL_ABSENT(UNG, row + 2 * 4, 1, d, 5);  // (d = 10: the one special size that can be absent in this code)
+        const int m23= X.t23[SF_TIDX(type, si1, sj1)] + Fc->L23;
         const int ta = RP[S[i + 3] * 8 + S[j - 4]];  // (i+3, j-4); sp1 = S[i+2], sq1 = S[j-3]
         eh = sfd_min(eh, row[2 * 3] + m23 + X.t23in[SF_TIDX(ta, S[j - 3], S[i + 2])]);
         const int tb = RP[S[i + 4] * 8 + S[j - 3]];  // (i+4, j-3); sp1 = S[i+3], sq1 = S[j-2]
@@ -765,18 +866,25 @@ __device__ __forceinline__ void sf_fast_cell(const SfFastCtx &X, const int d, co
         // (TBLK == 2: the merged-helper instantiation of the generic narrow kernel, W < 118)
         constexpr int SF_HELP_NB = FOLD ? SF_HELP_NB_256 : (TBLK == 2 ? SF_HELP_NB_128G : SF_HELP_NB_128);
 #pragma unroll
-        for (int ub = 2; ub <= 30; ub += SF_HELP_NB) {
+        for (int ub = 2; ub <= UTOP; ub += SF_HELP_NB) {
           if (CH && ub > um) continue;
           uint32_t w0[SF_HELP_NB], w2[SF_HELP_NB], w3[SF_HELP_NB], wt[SF_HELP_NB], t[SF_HELP_NB];
 #pragma unroll
           for (int k = 0; k < SF_HELP_NB; k++) {
             const int u = ub + k;
-            if (u <= 30) {
+            if (u <= UTOP) {
               // (!FOLD: sizes (u, u+1), u even, share a base — row u is the row after row u+1, the mirror row at the ring's seam)
-              const int16_t *tp = (FOLD || MGH || u == 30) ? BNROWB(ROWB_BN(u)) : BNROWB(ROWB_BN(u | 1)) + ((u & 1) ? 0 : 2 * RW);
+              // (SHORT: every size from its own row.  On an even diagonal d <= 30 the size d - 2 — absent — has the mirror row for
+              // "the row after row d - 1", and its columns, up to W - 2, run past the mirror's W - 34 words into what follows: at
+              // W >= 118 the parameter tables, energy-sized values that an unguarded sum would take for candidates.  Its own row is
+              // ring slot 0, which no diagonal before 34 writes: the read finds "none" there and in the slot behind it.  Chosen over
+              // keeping that one size guarded: the size changes with d, so the guard would be a run-time select per even size.
+              // The unsplit loop, d >= 32, needs nothing: d - 2 = 30 is addressed directly anyway.)
+              const int16_t *tp = (FOLD || MGH || SHORT || u == 30) ? BNROWB(ROWB_BN(u)) : BNROWB(ROWB_BN(u | 1)) + ((u & 1) ? 0 : 2 * RW);
 #ifdef SF_EMUL
               sf_emul_check_bn_row((const char *)tp, 4 * i0, 4 * RW, FOLD);
 #endif
+              SF_EMUL_ABSENT(UNG, tp + 2 * 1, 2, d, u); SF_EMUL_ABSENT(UNG, tp + 2 * (u - 1), 2, d, u); SF_EMUL_ABSENT(UNG, tp + 2 * (u + 1), 2, d, u);
               w0[k] = sf_ldw(tp + 2 * 1);
               w2[k] = sf_ldw(tp + 2 * (u - 1)); w3[k] = sf_ldw(tp + 2 * (u + 1));
               wt[k] = sf_ldw(uBN + 2 * u);
@@ -786,7 +894,7 @@ __device__ __forceinline__ void sf_fast_cell(const SfFastCtx &X, const int d, co
 #pragma unroll
             for (int k = 0; k < SF_HELP_NB; k++) {
               const int u = ub + k;
-              if (u <= 30) {
+              if (u <= UTOP) {
                 const uint32_t x = w0[k];  // (CB[1], C1N[2])
                 const uint32_t y = (w3[k] & 0xffffu) | (w2[k] & 0xffff0000u);  // (CB[1+u], C1N[u])
                 t[k] = sf_pkmin(x, y);
@@ -795,20 +903,20 @@ __device__ __forceinline__ void sf_fast_cell(const SfFastCtx &X, const int d, co
             SF_VALU_FENCE();
 #pragma unroll
             for (int k = 0; k < SF_HELP_NB; k++)
-              if (ub + k <= 30) t[k] = sf_pkadd(t[k], wt[k]);
+              if (ub + k <= UTOP) t[k] = sf_pkadd(t[k], wt[k]);
             SF_VALU_FENCE();
 #pragma unroll
             for (int k = 0; k + 1 < SF_HELP_NB; k += 2)
-              if (ub + k + 1 <= 30) t[k] = sf_pkmin(t[k], t[k + 1]);
+              if (ub + k + 1 <= UTOP) t[k] = sf_pkmin(t[k], t[k + 1]);
             SF_VALU_FENCE();
 #pragma unroll
             for (int k = 0; k < SF_HELP_NB; k += 2)
-              if (ub + k <= 30) { if (k & 2) accb = sf_pkmin(accb, t[k]); else acc = sf_pkmin(acc, t[k]); }
+              if (ub + k <= UTOP) { if (k & 2) accb = sf_pkmin(accb, t[k]); else acc = sf_pkmin(acc, t[k]); }
           } else {
 #pragma unroll
             for (int k = 0; k < SF_HELP_NB; k++) {
               const int u = ub + k;
-              if (u <= 30) {
+              if (u <= UTOP) {
                 const uint32_t x = w0[k];  // (CB[1], C1N[2])
                 const uint32_t y = (w3[k] & 0xffffu) | (w2[k] & 0xffff0000u);  // (CB[1+u], C1N[u])
                 acc = sf_pkmin(acc, sf_pkadd(sf_pkmin(x, y), wt[k]));
@@ -936,8 +1044,8 @@ __device__ __forceinline__ void sf_fast_cell(const SfFastCtx &X, const int d, co
           short g0 = (short)(HU.v[2] + (short)il[6]), g1 = (short)(HU.v[3] + (short)il[7]);
 #pragma unroll
           for (int x = 4; x <= 26; x += 2) {
-            g0 = sfd_min16(g0, sf_opaque16((short)(HU.v[x] + (short)il[x + 4])));
-            if (x + 1 <= 26) g1 = sfd_min16(g1, sf_opaque16((short)(HU.v[x + 1] + (short)il[x + 5])));
+            if (x + 4 <= UTOP) g0 = sfd_min16(g0, sf_opaque16((short)(HU.v[x] + (short)il[x + 4])));
+            if (x + 1 <= 26 && x + 5 <= UTOP) g1 = sfd_min16(g1, sf_opaque16((short)(HU.v[x + 1] + (short)il[x + 5])));
           }
           gg = sfd_min16(g0, g1);
         } else if (G) {
@@ -1013,6 +1121,8 @@ __device__ __forceinline__ void sf_fast_cell(const SfFastCtx &X, const int d, co
     if (!FOLD && slotd == 0) X.CI[SF_FAST_NR * RW + i0] = SF_INF16;
     if (X.bn_dup && slotd == 0) sf_fast_publish_bn(X.BN + 2 * (SF_FAST_NR * RW + i0), i0, sf_pk(SF_INF16, SF_INF16));
   }
+  SF_EMUL_WROTE(X.CI + rbd, 1);
+  if (!FOLD && slotd == 0) SF_EMUL_WROTE(X.CI + SF_FAST_NR * RW + i0, 1);
   // the scratch (row i, column j: the exterior sweep reads rows coalesced) takes c + ExtLoop, the only form the
   // sweep needs; the traceback (native windows only) subtracts the term again (sf_fast_c).  (Storing only the cells
   // that can pair — 3 of 8 — and masking the rest in the sweeps was measured: -5 % speed, and MORE memory traffic,
@@ -1478,6 +1588,10 @@ __device__ __forceinline__ void sf_trail_result(const SfTrail<NQ> &T, const int 
 enum SfStep {
   SF_STEP_SIZED,    // d0 < SF_FAST_TINY_D0: the cell code that tests every loop size against the diagonal
   SF_STEP_GUARDED,  // d0 < SF_FAST_CHUNK_D0: straight-line code with guarded size tables, batches above the limit skipped
+                    // (the wide kernel and the constrained instantiations; the other narrow ones run the three SHORT loops instead)
+  SF_STEP_SHORT_A,  // d0 < SF_FAST_SHORT_D1: the all-sizes code, unguarded and unpacked, loop sizes above D1 - 7 not instantiated
+  SF_STEP_SHORT_B,  // d0 < SF_FAST_SHORT_D2: ... above D2 - 7
+  SF_STEP_SHORT_C,  // d0 < SF_FAST_SHORT_D3: ... every size
   SF_STEP_UNSPLIT,  // every loop size exists; every wave works on cells of its own
   SF_STEP_SPLIT,    // d0 >= split_d0: a diagonal's cells fit the main waves, the others help (merged helper: dml2 chunks of 32 lanes)
   SF_STEP_SPLIT16,  // ... merged-helper instantiations, d0 >= W - 30: dml2 chunks of 16 lanes
@@ -1541,6 +1655,7 @@ __global__ __launch_bounds__(2 * NG, SF_FAST_WAVES_PER_SIMD) void sf_mfe_fast_ke
   X.BN = (int16_t *)(smem + Lo.off_c1n);  // spans the two areas
 #ifdef SF_EMUL
   sf_emul_bn_base = (const char *)X.BN; sf_emul_ci_base = (const char *)X.CI;
+  sf_emul_shadow_span((const char *)(smem + Lo.off_ci), (const char *)(smem + Lo.off_tab));
 #endif
   X.DMLr = nullptr;  // (the multiloop split of the enclosed cell is carried in a register: same thread, two diagonals earlier)
   int16_t *tab = (int16_t *)(smem + Lo.off_tab);
@@ -1564,6 +1679,12 @@ __global__ __launch_bounds__(2 * NG, SF_FAST_WAVES_PER_SIMD) void sf_mfe_fast_ke
   // (every narrow instantiation: +2-3 % at W = 64 .. 117 on top of the loops by kind, W = 128 +-0; the wide kernel measured 0.5-1.5 %
   // SLOWER with it — W = 200: 55.1 -> 55.6 ms per 65 536 folds, the generic wide instantiation at W = 136 .. 250 — and stays packed)
   constexpr bool UNPK = SF_FAST_UNPACK && (NG == 128);
+  // ... and from SF_FAST_TINY_D0 on, in place of the guarded steps (SF_STEP_SHORT_A / B / C).  Not the constrained instantiations: the
+  // argument holds for them too — a constraint only turns cells to "none" — but they spill more and were not measured; they keep
+  // the guarded steps, like the wide kernel
+  constexpr bool SHORTU = SF_FAST_SHORT && UNPK && !HC;
+  static_assert(SF_FAST_TINY_D0 >= 10 && SF_FAST_TINY_D0 <= SF_FAST_SHORT_D1 && SF_FAST_SHORT_D1 <= SF_FAST_SHORT_D2 &&
+                SF_FAST_SHORT_D2 <= SF_FAST_SHORT_D3 && SF_FAST_SHORT_D1 >= 14, "SHORT loops: d0 >= 10 (no tabulated hairpin, sizes 0 .. 4 exist), caps >= 7");
   // The steps of a fold run as one loop per kind of step (SfStep, the loops at the end of the kernel) — and the split steps of
   // the merged-helper instantiations as three, by the chunk width of their two-cells-per-lane multiloop
   // split, the width a compile-time constant in each (W = 120: 56.2 -> 55.4 ms per 262 144 folds, W = 100 +1.4 %; the instantiation
@@ -1671,6 +1792,10 @@ __global__ __launch_bounds__(2 * NG, SF_FAST_WAVES_PER_SIMD) void sf_mfe_fast_ke
     constexpr bool PINF = true;
     int tidf = tid;
     if (PINF) SF_PIN(tidf);
+#ifdef SF_EMUL
+    // (every fiber of the workgroup has left the previous fold's steps: what that fold wrote is "left over" now)
+    if (tid == 0) sf_emul_shadow_set(smem + Lo.off_ci, (Lo.off_tab - Lo.off_ci) / 2, 2);
+#endif
     __syncthreads();
     if (PZ) {
       for (int x = tid; x < Lo.off_tab / 2; x += NT) ((int16_t *)smem)[x] = sf_poison16(poison, x);
@@ -1685,7 +1810,12 @@ __global__ __launch_bounds__(2 * NG, SF_FAST_WAVES_PER_SIMD) void sf_mfe_fast_ke
     // finds is energy-sized.  Until round 4 the tables were initialised once per workgroup and later folds found the
     // previous fold's energies there — as good, unless that fold had left the int16 range.  24 dword stores per thread
     // and fold (0.05 % of a fold) make a fold's result a function of its own sequence only.
-    for (int x = tidf; x < (Lo.off_tab - Lo.off_ci) / 4; x += NT) ((uint32_t *)X.CI)[x] = sf_pk(SF_INF16, SF_INF16);
+    for (int x = tidf; x < (Lo.off_tab - Lo.off_ci) / 4; x += NT) {
+      ((uint32_t *)X.CI)[x] = sf_pk(SF_INF16, SF_INF16);
+#ifdef SF_EMUL
+      sf_emul_shadow_set((uint32_t *)X.CI + x, 2, 0);
+#endif
+    }
     int fetched = 0;
     if (tid == 0) {
       S[0] = 0; S[W + 1] = 0; flag[0] = 0;
@@ -1744,6 +1874,7 @@ __global__ __launch_bounds__(2 * NG, SF_FAST_WAVES_PER_SIMD) void sf_mfe_fast_ke
       if (tA) list[__popcll(mA & below)] = (uint8_t)iH;
       if (tB) list[cA + __popcll(mB & below)] = (uint8_t)(iH | 128);
       if (lane == 0) list[127] = (uint8_t)(cA + __popcll(mB));
+      if (lane == 0) SF_EMUL_WROTE(list, 64);  // (the whole 128-byte list counts as written)
     };
 // @section step_control
     // One step = the diagonals d0 (even group) and d0 + 1 (odd group).  The body is instantiated once per kind of step (SfStep).
@@ -1764,6 +1895,8 @@ __global__ __launch_bounds__(2 * NG, SF_FAST_WAVES_PER_SIMD) void sf_mfe_fast_ke
       constexpr int LGC = KIND == SF_STEP_SPLIT16 ? 4 : (KIND == SF_STEP_SPLIT8 ? 3 : (KIND == SF_STEP_SPLIT && LGLOOPS ? 5 : 0));
       constexpr bool DO_G = KIND == SF_STEP_SIZED, DO_CH = KIND == SF_STEP_GUARDED;
       const int d = d0 + grp;
+      constexpr bool DO_SH = KIND >= SF_STEP_SHORT_A && KIND <= SF_STEP_SHORT_C;
+      constexpr int SHCAP = KIND == SF_STEP_SHORT_A ? SF_FAST_SHORT_D1 - 7 : (KIND == SF_STEP_SHORT_B ? SF_FAST_SHORT_D2 - 7 : SFD_MAXLOOP);
       // (the second and third step of a fold, long before the split steps — split_d0 > SFD_MAXLOOP: not in the role bodies)
       if (!ROLES && d0 == SFD_TURN + 1 + 2 && tid == 0) *next_slot = fetched;  // the barriers of this step publish it
       if (!ROLES && d0 == SFD_TURN + 1 + 4) next_seq = SF_WAVE_UNIFORM(*next_slot);
@@ -1831,6 +1964,7 @@ __global__ __launch_bounds__(2 * NG, SF_FAST_WAVES_PER_SIMD) void sf_mfe_fast_ke
         if (DO_G && d0 < 8) sf_fast_cell<true, WT, SF_SEC_ALL, false, FOLD, 1>(X, d, i, valid, slot2, slotd, H, HU, ovf, grp == 0, fnb, fpart, dec, eh, e0, dprev, pub);
         else if (DO_G && d0 < SF_FAST_TINY_D0) sf_fast_cell<true, WT, SF_SEC_ALL, false, FOLD, 5>(X, d, i, valid, slot2, slotd, H, HU, ovf, grp == 0, fnb, fpart, dec, eh, e0, dprev, pub);
         else if (DO_CH && d0 < SF_FAST_CHUNK_D0) sf_fast_cell<false, WT, SF_SEC_ALL, true, FOLD, SFD_MAXLOOP, TBLK>(X, d, i, valid, slot2, slotd, H, HU, ovf, grp == 0, fnb, fpart, dec, eh, e0, dprev, pub);
+        else if (DO_SH) sf_fast_cell<false, WT, SF_SEC_ALL, false, FOLD, SHORTU ? SHCAP : SFD_MAXLOOP, TBLK, false, SHORTU, SHORTU>(X, d, i, valid, slot2, slotd, H, HU, ovf, grp == 0, fnb, fpart, dec, eh, e0, dprev, pub);
         else if (!split) sf_fast_cell<false, WT, SF_SEC_ALL, false, FOLD, SFD_MAXLOOP, TBLK, false, UNPK && KIND == SF_STEP_UNSPLIT>(X, d, i, valid, slot2, slotd, H, HU, ovf, grp == 0, fnb, fpart, dec, eh, e0, dprev, pub);
         else if (DML4 && narrow) {
           // terms m = 4 .. d-5: main [4, cA), wave 2 [cA, cB), wave 3 [cB, d-5]
@@ -1874,7 +2008,7 @@ __global__ __launch_bounds__(2 * NG, SF_FAST_WAVES_PER_SIMD) void sf_mfe_fast_ke
             SfFastCtx Xh = X;
             Xh.BN = X.BN + 2 * g * (W - 4);
             sf_fast_cell<false, WT, SF_SEC_HELP, false, FOLD, SFD_MAXLOOP, TBLK, true>(Xh, d0 + g, iC, vC, s2, sd0, H, HU, ovf, false, fnb, fpart, dec, eh, e0, dprev, pub);
-            if (vC) X.BN[2 * ((g ? sd1 : sd0) * (W - 4) + iC - 1)] = (int16_t)sfd_min(eh, 32000);
+            if (vC) { X.BN[2 * ((g ? sd1 : sd0) * (W - 4) + iC - 1)] = (int16_t)sfd_min(eh, 32000); SF_EMUL_WROTE(X.BN + 2 * ((g ? sd1 : sd0) * (W - 4) + iC - 1), 1); }
           }
         } else {
           // the helper's results -> the cell's OWN entries of the row it is about to publish (unread until the next
@@ -1888,7 +2022,7 @@ __global__ __launch_bounds__(2 * NG, SF_FAST_WAVES_PER_SIMD) void sf_mfe_fast_ke
             }
           } else {
             sf_fast_cell<false, WT, SF_SEC_HELP, false, FOLD, SFD_MAXLOOP, TBLK>(X, d, i, valid, slot2, slotd, H, HU, ovf, grp == 0, fnb, fpart, dec, eh, e0, dprev, pub);
-            if (valid) X.BN[2 * (slotd * (W - 4) + i - 1)] = (int16_t)sfd_min(eh, 32000);
+            if (valid) { X.BN[2 * (slotd * (W - 4) + i - 1)] = (int16_t)sfd_min(eh, 32000); SF_EMUL_WROTE(X.BN + 2 * (slotd * (W - 4) + i - 1), 1); }
           }
         }
       }
@@ -1941,14 +2075,23 @@ __global__ __launch_bounds__(2 * NG, SF_FAST_WAVES_PER_SIMD) void sf_mfe_fast_ke
     {
       int d0 = SFD_TURN + 1;
       // One loop per kind of step, in SfStep's order.
-      // UNPK: the state is unpacked at d0 = 36 — the first diagonal pair on which every loop size exists (the guarded code before it
-      // needs the saturating packed adds; unpacked with v_add_i16 clamp it measured slower: 58.8 ms).
+      // UNPK: the state is unpacked where the unpacked code begins.  SHORTU: right after the size-tested steps, which have not touched
+      // it yet (a generic loop needs d >= 10).  Otherwise at d0 = 36 — the first diagonal pair on which every loop size exists (the
+      // guarded code before it needs the saturating packed adds; unpacked with v_add_i16 clamp it measured slower: 58.8 ms).
       constexpr SfRoleTag<SF_ROLE_ALL> all_roles{};
-      for (; d0 < SF_FAST_TINY_D0 && d0 < W; d0 += 2) step(d0, SfStepTag<SF_STEP_SIZED>{}, all_roles);
-      for (; d0 < SF_FAST_CHUNK_D0 && d0 < W; d0 += 2) step(d0, SfStepTag<SF_STEP_GUARDED>{}, all_roles);
-      if constexpr (UNPK) {
+      auto unpack_state = [&]() {
 #pragma unroll
         for (int x = 0; x < 27; x++) HU.v[x] = (short)((x & 1) ? (H[x >> 1] >> 16) : (H[x >> 1] & 0xffffu));
+      };
+      for (; d0 < SF_FAST_TINY_D0 && d0 < W; d0 += 2) step(d0, SfStepTag<SF_STEP_SIZED>{}, all_roles);
+      if constexpr (SHORTU) {
+        unpack_state();
+        for (; d0 < SF_FAST_SHORT_D1 && d0 < W; d0 += 2) step(d0, SfStepTag<SF_STEP_SHORT_A>{}, all_roles);
+        for (; d0 < SF_FAST_SHORT_D2 && d0 < W; d0 += 2) step(d0, SfStepTag<SF_STEP_SHORT_B>{}, all_roles);
+        for (; d0 < SF_FAST_SHORT_D3 && d0 < W; d0 += 2) step(d0, SfStepTag<SF_STEP_SHORT_C>{}, all_roles);
+      } else {
+        for (; d0 < SF_FAST_CHUNK_D0 && d0 < W; d0 += 2) step(d0, SfStepTag<SF_STEP_GUARDED>{}, all_roles);
+        if constexpr (UNPK) unpack_state();
       }
       for (; d0 < split_d0 && d0 < W; d0 += 2) step(d0, SfStepTag<SF_STEP_UNSPLIT>{}, all_roles);
       // The split steps: in the narrow kernel (ROLE_LOOPS) every wave runs them as loops of its own role — a wave-uniform branch

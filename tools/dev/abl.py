@@ -142,6 +142,16 @@ VARIANTS = {
     "pb4": ([], ["-DSF_UNP_PB=4"]),
     "pb6": ([], ["-DSF_UNP_PB=6"]), "pb12": ([], ["-DSF_UNP_PB=12"]),
     "nounpack": ([], ["-DSF_FAST_UNPACK=0"]),
+    # the unguarded short-diagonal loops (SF_STEP_SHORT_A / B / C): off = the guarded steps up to d0 = 36 as before; boundaries
+    # "shD1_D2": loop A d0 < D1 with sizes <= D1 - 7, loop B d0 < D2 with sizes <= D2 - 7, loop C up to 32 with every size
+    # (D2 = 32: no loop C; D1 = D2: no loop B).  profiles/guarded_unpacked/README.md has the figures
+    "short0": ([], ["-DSF_FAST_SHORT=0"]),
+    "sh14_22": ([], ["-DSF_FAST_SHORT_D1=14", "-DSF_FAST_SHORT_D2=22"]),
+    "sh18_26": ([], ["-DSF_FAST_SHORT_D1=18", "-DSF_FAST_SHORT_D2=26"]),
+    "sh20_28": ([], ["-DSF_FAST_SHORT_D1=20", "-DSF_FAST_SHORT_D2=28"]),
+    "sh18_32": ([], ["-DSF_FAST_SHORT_D1=18", "-DSF_FAST_SHORT_D2=32"]),
+    "sh22_32": ([], ["-DSF_FAST_SHORT_D1=22", "-DSF_FAST_SHORT_D2=32"]),
+    "sh32_32": ([], ["-DSF_FAST_SHORT_D1=32", "-DSF_FAST_SHORT_D2=32"]),
     # sections: instructions per fold of a section = product - ablation, by SQ counters (tools/pmc_cmp.sh; profiles/r05/mfe_section_budget.txt)
     "secP1": ([(FAST, "  if (SEC & SF_SEC_P1) {\n", "  if (false) {\n")], []),
     "secHELP": ([(FAST, "  if (SEC & SF_SEC_HELP) {\n", "  eh = SF_FAST_BIG;\n  if (false) {\n")], []),

@@ -1,7 +1,7 @@
 """Per-basic-block instruction statistics of one kernel in a `hipcc -S --cuda-device-only` listing.
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -S --cuda-device-only -o /tmp/sf.s scanfold_amd/csrc/scanfold_hip.hip
-    python tools/isa_blocks.py /tmp/sf.s sf_mfe_fast_kernelILi128ELi120ELb0ELb0ELb0 [n_blocks] [--dump LABEL]
+    python tools/isa_blocks.py /tmp/sf.s sf_mfe_fast_kernelILi128ELi120ELb0ELb0ELb0 [n_blocks] [--dump LABEL] [--loops]
 
 For the largest blocks: vector / scalar / LDS / scalar-memory / vector-memory instructions, and the issue slots that do no
 work — s_waitcnt and s_nop (on gfx950 a packed VOP3P result read by the very next instruction costs one s_nop: chains of
@@ -78,6 +78,31 @@ def main():
         for name, ins in blocks:
             if name == lab:
                 print("\n".join(ins))
+        return
+    if "--loops" in args:
+        # the step loops of the MFE kernel: every back edge whose body holds one or two s_barrier — blocks, instructions, vector
+        # instructions by issue rate, scratch instructions, the largest block (profiles/guarded_unpacked/isa_loops_w120.txt)
+        idx = {b[0]: k for k, b in enumerate(blocks)}
+        for k, (_, ins) in enumerate(blocks):
+            for t in ins:
+                m = re.match(r"s_c?branch\w*\s+(\.LBB\d+_\d+)", t)
+                if not m or m.group(1) not in idx or idx[m.group(1)] > k:
+                    continue
+                a = idx[m.group(1)]
+                body = [i for b in blocks[a:k + 1] for i in b[1]]
+                nb = sum(i.startswith("s_barrier") for i in body)
+                if nb not in (1, 2):
+                    continue
+                ops = [i.split()[0] for i in body]
+                c = collections.Counter(classify(o) for o in ops)
+                valu = [o for o in ops if classify(o) == "valu"]
+                full = sum(valu_ns(o) < 1.5 for o in valu)
+                big = max(blocks[a:k + 1], key=lambda b: len(b[1]))
+                print("%s..%s blocks %d insts %d barriers %d | valu %d (full %d + half %d) valu_ns %.0f | salu %d lds %d smem %d vmem %d "
+                      "scratch %d wait %d nop %d | largest block %s %d"
+                      % (blocks[a][0], blocks[k][0], k - a + 1, len(body), nb, len(valu), full, len(valu) - full,
+                         sum(valu_ns(o) for o in valu), c["salu"], c["lds"], c["smem"], c["vmem"],
+                         sum(o.startswith("scratch_") for o in ops), c["wait"], c["nop"], big[0], len(big[1])))
         return
     n = int(args[0]) if args else 12
     tot = collections.Counter()
