@@ -95,6 +95,18 @@
 // instantiation stops here; the W = 120 instantiation runs the merged helper all the same, its cell lists in the place of the LDS
 // copy of the size tables (see cell_list in the kernel).  (The figures per width: profiles/HISTORY.md, "Switches settled".)
 #define SF_HELP_MERGE_MAXW 118
+// Split steps of the narrow kernels without a per-fold constraint — a step lasts as long as its longest wave's instruction stream,
+// and there that is a main wave (profiles/main_wave_diet/README.md):
+//  - the publish terms of a cell (SfPub) are looked up by the helper wave, which visits every cell that can pair anyway, and cross
+//    to the main wave with eh at the exchange barrier (HT in the kernel: where they cross);
+//  - the fML triangle's bases of the diagonals d0 and d0 + 1, which the finish and the fix-up — the two phases every other wave of
+//    the workgroup waits for — derived from d0 with two multiplications each, are loop state updated by one add per step.
+#ifndef SF_FAST_HELPER_TERMS
+#define SF_FAST_HELPER_TERMS 1
+#endif
+#ifndef SF_FAST_FBASE_CARRY
+#define SF_FAST_FBASE_CARRY 1
+#endif
 // split steps of the wide kernel (NG = 256, where the split is most of a cell): the helper waves take (terms / 2 - bias)
 // terms of the multiloop split, the ones with the largest m.  The narrow kernel's helpers take none: their special-loop
 // work already balances the main wave (any share measured the same or worse in rounds 2 and 3).
@@ -515,9 +527,18 @@ extern "C" int sfemul_absent_check_selftest(int W, int what) {
 #define SF_EMUL_WROTE(p, n16) sf_emul_shadow_set((p), (n16), 1)
 // reads of n16 int16 entries at p for loop size u on diagonal d, by the unguarded all-sizes code (CHK: that code, compile time)
 #define SF_EMUL_ABSENT(CHK, p, n16, d, u) do { if ((CHK) && (u) > (d) - 2 - (SFD_TURN + 1)) sf_emul_check_absent((p), (n16), (d), (u)); } while (0)
+// The lanes of a wave run in lockstep: every lane has executed a load before any lane executes a store that depends on its result.
+// The emulation's fibers do not — a fiber runs on to the next barrier or wave-level exchange — so where the kernel relies on it
+// (the main waves fetch what the helper left in the high half of their cell's word, which the NEXT lane's publish overwrites)
+// the emulation gets a wave-level meeting point.
+#define SF_LOCKSTEP() ((void)__ballot(1))
+#define SF_PIN_S(x) ((void)0)
 #else
 #define SF_EMUL_WROTE(p, n16) ((void)0)
 #define SF_EMUL_ABSENT(CHK, p, n16, d, u) ((void)0)
+#define SF_LOCKSTEP() ((void)0)
+// the wave-uniform value must be computed by this point (SF_PIN for a scalar register)
+#define SF_PIN_S(x) asm volatile("" : "+s"(x))
 #endif
 
 // (CB, C1N) of the cell at column i0 of a row into the interleaved bulge / 1xn table; w points at the cell's own word.
@@ -545,8 +566,12 @@ __device__ __forceinline__ void sf_fast_publish_bn(int16_t *w, const int i0, con
 //                BEFORE the exchange barrier, in the shadow of the cell's other LDS waits, and handed to the SF_SEC_FIN
 //                call in `pub` (SF_SEC_POST): the finish after the barrier, which nothing can overlap, loses its three
 //                dependent LDS round trips
+//   SF_SEC_TERMS  (split steps, with SF_SEC_HELP) the HELPER looks those terms up, for the main wave to fetch with eh (pub.a, pub.stem,
+//                 pub.ext); the main wave's call then has SF_SEC_TYPE in the place of SF_SEC_PRE — the pair type, which it needs
+//                 anyway, and TerminalAU — and its finish SF_SEC_XTERMS: stem / exterior terms in pub.stem / pub.ext
+//   SF_SEC_FB     (finish) the fML base of diagonal d comes in `fbd` (the kernel carries it from step to step)
 enum { SF_SEC_P1 = 1, SF_SEC_HELP = 2, SF_SEC_DML = 4, SF_SEC_FIN = 8, SF_SEC_C0 = 16, SF_SEC_ALL = 31, SF_SEC_PRE = 32,
-       SF_SEC_POST = 64 };
+       SF_SEC_POST = 64, SF_SEC_TERMS = 128, SF_SEC_TYPE = 256, SF_SEC_XTERMS = 512, SF_SEC_FB = 1024 };
 // UNP (the narrow kernels' steps from d0 = 10 on; from 36 on in the constrained instantiations): the per-size minima of the generic-loop recurrence one int16 per register
 // instead of two.  On MI355X every packed (VOP3P) instruction and the v_lshl_or that packs two 16-bit reads issue at half the rate
 // of the 16-bit VOP2 forms v_min_i16 / v_add_u16 (profiles/r04/mfe_issue_rates.json), so a size pair costs 5 half-rate + 1
@@ -564,6 +589,7 @@ struct SfPub {
   int tau;     // TerminalAU of the pair: what CB adds
   int type;    // the cell's pair type (constraint applied): the finish after the barrier does not look it up again — two
                // dependent LDS round trips (nucleotides, then the pair table) at the head of a phase every other wave waits for
+  int stem, ext;  // SF_SEC_TERMS / SF_SEC_XTERMS: the two halves of b, one register each (they cross in two int16 entries)
 };
 // UCAP: compile-time bound on the loop sizes that can exist.  G code — d <= 7: 1, d <= 11: 5 — so that the unrolled
 // size tests above it (a scalar compare + branch each, ~110 of them) disappear from the first four steps of a fold, which
@@ -583,7 +609,7 @@ __device__ __forceinline__ void sf_fast_cell(const SfFastCtx &X, const int d, co
                                              const int slot2, const int slotd, uint32_t (&HP)[14], SfHU &HU, int &ovf,
                                              const bool final_fml, const int fnb, int &fpart, int &dec, int &eh, int &e0,
                                              int &dprev, SfPub &pub, const int dml_lo = SFD_TURN + 1,
-                                             const int dml_hi = 1 << 20) {
+                                             const int dml_hi = 1 << 20, const int fbd = 0) {
   // size tables: NIN[32] asymmetry | IL[32] loop initiation | 32 pairs (bulge[u], 1xn term of total size u — 32767 for u < 4)
   // third table: 32-bit pairs (bulge[u], 1xn term of total size u — 32767 for u < 4, where no 1xn loop exists)
   // The size tables are the same for every lane: they are read from DEVICE memory with wave-uniform addresses — scalar loads
@@ -625,18 +651,29 @@ __device__ __forceinline__ void sf_fast_cell(const SfFastCtx &X, const int d, co
   }
   const int si1 = S[i + 1], sj1 = S[j - 1];
 // @section publish_terms
-  if (SEC & SF_SEC_PRE) pub.type = type;
-  if ((SEC & SF_SEC_PRE) && type) {
+  if (SEC & (SF_SEC_PRE | SF_SEC_TYPE)) pub.type = type;
+  if (SEC & SF_SEC_TYPE) pub.tau = type > 2 ? X.TAU : 0;  // (the reversed type is above 2 exactly when the type is)
+  if ((SEC & (SF_SEC_PRE | SF_SEC_TERMS)) && type) {
     const int tr = X.tRPair[S[i] * 8 + S[j]];
     const int sp1 = S[i - 1], sq1 = S[j + 1];
     const int tau_in = tr > 2 ? X.TAU : 0;
     int stem, ext;
+    if (SEC & SF_SEC_TERMS) {
+      // (the helper: all four look-ups in flight at once and selects — the cells in row 1 and column W are lanes of the same wave
+      // as the others, so the branches below would be executed one after the other; S[0] = S[W + 1] = 0 keep every index in its table)
+      const int km = SF_TIDX(type, sp1, sq1);
+      const int mm = X.tM[km], me = X.tE[km], e5 = X.tD5[type * 5 + sp1], e3 = X.tD3[type * 5 + sq1];
+      const bool in5 = i > 1, in3 = j < W;
+      const int dg = in5 ? e5 : (in3 ? e3 : 0);
+      stem = (in5 && in3) ? mm : dg; ext = (in5 && in3) ? me : dg;
+    } else
     if (i > 1 && j < W) { stem = X.tM[SF_TIDX(type, sp1, sq1)]; ext = X.tE[SF_TIDX(type, sp1, sq1)]; }
     else if (i > 1) stem = ext = X.tD5[type * 5 + sp1];
     else if (j < W) stem = ext = X.tD3[type * 5 + sq1];
     else stem = ext = 0;
     pub.a = sf_pk(X.tI[SF_TIDX(tr, sq1, sp1)], X.t1n[SF_TIDX(tr, sq1, sp1)]);
-    pub.b = sf_pk(stem + tau_in + X.MLintern, ext + tau_in);
+    if (SEC & SF_SEC_TERMS) { pub.stem = stem + tau_in + X.MLintern; pub.ext = ext + tau_in; }
+    else pub.b = sf_pk(stem + tau_in + X.MLintern, ext + tau_in);
     pub.tau = tau_in;
   }
 // @section cell_setup
@@ -1096,8 +1133,8 @@ __device__ __forceinline__ void sf_fast_cell(const SfFastCtx &X, const int d, co
     const uint32_t bn = sf_pk(c + pub.tau, c + sf_hi(pub.a));  // (CB, C1N)
     sf_fast_publish_bn(X.BN + 2 * rbd, i0, bn);
     if (X.bn_dup && slotd == 0) sf_fast_publish_bn(X.BN + 2 * (SF_FAST_NR * RW + i0), i0, bn);
-    f = c + sf_lo(pub.b);
-    cx = sfd_min(c + sf_hi(pub.b), SF_INF16);
+    f = c + ((SEC & SF_SEC_XTERMS) ? pub.stem : sf_lo(pub.b));
+    cx = sfd_min(c + ((SEC & SF_SEC_XTERMS) ? pub.ext : sf_hi(pub.b)), SF_INF16);
   } else if (type) {
     const int tr = X.tRPair[S[i] * 8 + S[j]];
     const int sp1 = S[i - 1], sq1 = S[j + 1];
@@ -1137,7 +1174,7 @@ __device__ __forceinline__ void sf_fast_cell(const SfFastCtx &X, const int d, co
   fpart = f;
   if (final_fml && f < SF_FAST_OVF) ovf = 1;
   // final on the even diagonal; provisional (neighbour term still missing) on the odd one
-  X.fML[FBASE(d) + i0] = (int16_t)(f > SF_FAST_THRESH ? SF_INF16 : f);
+  X.fML[((SEC & SF_SEC_FB) ? fbd : FBASE(d)) + i0] = (int16_t)(f > SF_FAST_THRESH ? SF_INF16 : f);
 #undef ROW
 #undef ROWB_CI
 #undef ROWB_BN
@@ -1529,6 +1566,14 @@ __device__ __forceinline__ void sf_fast_exterior(const SfFastCtx &X, const int W
 // it), and only the rows the last step completes are left for the end of the fold.  One scratch per workgroup.
 // State: lane l holds f3[j+1] of its columns j = l+1, l+65, ...; f3 of the row above the next one.
 #define SF_DEFER_ROWS_256 3  // rows in flight per step in the W = 200 instantiation (four columns per lane)
+// ... and in the W = 120 instantiation, per split loop (dml2 chunks of 32 / 16 / 8 lanes: d0 = 58 .. 88 / 90 .. 104 / 106 .. 118).
+// 4 / 4 / 4 is the schedule the kernel always had (min(rows needed per step, 4) is 4 at W = 120); more rows while the sweeper
+// waits longest and fewer where it arrives last measured the same (profiles/main_wave_diet/README.md)
+#ifndef SF_SWEEP_ROWS_120_A
+#define SF_SWEEP_ROWS_120_A 4
+#define SF_SWEEP_ROWS_120_B 4
+#define SF_SWEEP_ROWS_120_C 4
+#endif
 template <int NQ>
 struct SfTrail {
   int F[NQ];   // lane l: f3[j+1] for the columns j = l+1+64q (0 until row j+1 has been swept)
@@ -1692,6 +1737,10 @@ __global__ __launch_bounds__(2 * NG, SF_FAST_WAVES_PER_SIMD) void sf_mfe_fast_ke
   constexpr bool LGLOOPS = MG && (NG == 128);
   // ... and, in the narrow kernel, every split loop once per role of a wave (SfRole)
   constexpr bool ROLE_LOOPS = (NG == 128);
+  // ... with the publish terms looked up by the helpers and the fML bases carried (SF_FAST_HELPER_TERMS, SF_FAST_FBASE_CARRY).  Not the
+  // constrained instantiations: they were not measured with either and keep their instruction streams
+  constexpr bool HTERMS = SF_FAST_HELPER_TERMS && (NG == 128) && !HC;
+  constexpr bool FBCARRY = SF_FAST_FBASE_CARRY && (NG == 128) && !HC;
   // rolling-row offsets from SfFastRows (see sf_fast_cell): 1 = yes, 2 = yes + the long read batches of the generic merged-helper
   // instantiation, 0 = no (the generic wide kernel)
   constexpr int TBLK = WT > 0 ? 1 : (NG == 128 ? (MG ? 2 : 1) : 0);
@@ -1883,6 +1932,9 @@ __global__ __launch_bounds__(2 * NG, SF_FAST_WAVES_PER_SIMD) void sf_mfe_fast_ke
     SfHU HU;
     const int grp_wave = grp;
     const bool sweeper_wave = sweeper;
+    // FBCARRY: FBASE(d0) through the split steps — set where they begin, + 2 (W - d0) per step (the triangle's second difference
+    // is a constant)
+    int fb0 = 0;
     auto step = [&](const int d0, auto kind_tag, auto role_tag) {
       constexpr SfStep KIND = decltype(kind_tag)::value;
       constexpr SfRole ROLE = decltype(role_tag)::value;
@@ -1908,6 +1960,40 @@ __global__ __launch_bounds__(2 * NG, SF_FAST_WAVES_PER_SIMD) void sf_mfe_fast_ke
       // helper lanes mirror a main lane 64 away: NG = 128: wave 1 -> wave 0; NG = 256: wave 0 -> wave 1, wave 3 -> wave 2
       constexpr bool split = KIND >= SF_STEP_SPLIT;
       constexpr bool narrow = KIND == SF_STEP_NARROW;  // (see NARROW above; its first step moves the centres' state)
+      // HT: the helpers look up the publish terms.  What a helper hands over for the cell at column x of a diagonal of n = W - d cells
+      // goes where nothing valid is read before the cell is published, in the ring row the diagonal is about to take and in the cell's
+      // own fML entry: the cell's word of the interleaved table = (mismatchI, mismatch1nI) terms, its generic-loop entry = eh, its fML
+      // entry = the stem term, and the exterior term in int16 entry 2 n + x of the interleaved row — behind the n words of the cells,
+      // where no candidate read of a valid lane reaches (a row of diagonal dd is read up to word W - dd - 2).  3 n <= 2 (W - 4) on
+      // every split diagonal of every narrow width (tests/test_helper_terms_emul.py checks the arithmetic; the emulation build
+      // stops on a step that breaks it).
+      // (Only the merged-helper instantiations, and only in their loop with dml2 chunks of 32 lanes, d0 < W - 30.  In the two loops
+      // after it the main waves' multiloop split is shorter and the helper wave arrives last at the exchange barrier as soon as it
+      // carries the terms, which makes those steps longer; the mirroring helpers, W = 118 .. 128 except 120, measured slower with
+      // the terms as well.  The figures: profiles/main_wave_diet/README.md.  What the hand-over leaves behind: DESIGN.md §4.1.)
+      constexpr bool HT = HTERMS && split && ROLES && LGLOOPS && KIND == SF_STEP_SPLIT, FB = FBCARRY && split && ROLES;
+      constexpr int SEC_MAIN = SF_SEC_P1 | SF_SEC_C0 | (HT ? SF_SEC_TYPE : SF_SEC_PRE);
+      constexpr int SEC_HELP = SF_SEC_HELP | (HT ? SF_SEC_TERMS : 0);
+      constexpr int SEC_FIN = SF_SEC_FIN | SF_SEC_POST | (HT ? SF_SEC_XTERMS : 0) | (FB ? SF_SEC_FB : 0);
+      // fML bases of d0 and d0 + 1 (FB: carried, and formed before the exchange barrier — not in the finish or the fix-up)
+      int fbA = 0, fbB = 0;
+      if (HT || FB) {
+        fbA = FB ? fb0 : FBASE(d0);
+        fbB = FB ? fb0 + FLEN(d0) : FBASE(d0 + 1);
+        if (FB) SF_PIN_S(fbB);
+      }
+      const int fbd = grp ? fbB : fbA;
+      // a helper lane's results for the cell at column x of the n-cell diagonal whose ring row starts at entry `row`, fML base fb
+      auto hand_over = [&](const int row, const int x, const int n, const int fb, const int eh_, const SfPub &p) {
+        *(uint32_t *)(X.BN + 2 * (row + x)) = p.a;
+        X.CI[row + x] = (int16_t)sfd_min(eh_, 32000);
+        X.fML[fb + x] = (int16_t)p.stem;
+        X.BN[2 * row + 2 * n + x] = (int16_t)p.ext;
+        SF_EMUL_WROTE(X.BN + 2 * (row + x), 2); SF_EMUL_WROTE(X.CI + row + x, 1); SF_EMUL_WROTE(X.BN + 2 * row + 2 * n + x, 1);
+      };
+#ifdef SF_EMUL
+      if (HT && d < W && 3 * (W - d) > 2 * (W - 4)) { fprintf(stderr, "sf_mfe_fast (emulation): W %d diagonal %d: no room for the helper's terms\n", W, d); abort(); }
+#endif
       if (NARROW && d0 == narrow_d0) {
         // the one-time move of the centres' state: old owners tg = 96..159 -> new owners tg - 32 = 64..127
         uint32_t *const xa = (uint32_t *)X.BN;  // dword = cell of the interleaved ring; row r, cell 100 + lane
@@ -1949,15 +2035,19 @@ __global__ __launch_bounds__(2 * NG, SF_FAST_WAVES_PER_SIMD) void sf_mfe_fast_ke
       int fpart = SF_FAST_BIG;
       int dec = SF_FAST_BIG, eh = SF_FAST_BIG, e0 = SF_FAST_BIG;
       SfPub pub;
-      pub.a = pub.b = 0; pub.tau = 0; pub.type = 0;
+      pub.a = pub.b = 0; pub.tau = 0; pub.type = 0; pub.stem = pub.ext = 0;
       // trailing sweep: the rows i >= W-d0+1 are complete (diagonals < d0 are); this step's rows are requested now, used
       // after the wave's own work
-      int dc[DROWS][NQ];
+      // (the W = 120 instantiation: rows per step a constant of each split loop, SF_SWEEP_ROWS_120_A / B / C — what the split steps
+      // leave is swept at the end of the fold)
+      constexpr bool SWK = (WT == 120) && ROLES;
+      constexpr int DR = !SWK ? DROWS : (KIND == SF_STEP_SPLIT ? SF_SWEEP_ROWS_120_A : (KIND == SF_STEP_SPLIT16 ? SF_SWEEP_ROWS_120_B : SF_SWEEP_ROWS_120_C));
+      int dc[DR][NQ];
       const bool sweep_now = defer_on && sweeper && split && T.row > 0;
-      const int sweep_rows = sweep_now ? sfd_max(sfd_min(defer_rows, T.row - (W - d0)), 0) : 0;
+      const int sweep_rows = sweep_now ? sfd_max(sfd_min(SWK ? DR : defer_rows, T.row - (W - d0)), 0) : 0;
       if (sweep_now) {
 #pragma unroll
-        for (int k = 0; k < DROWS; k++)
+        for (int k = 0; k < DR; k++)
           if (k < sweep_rows) sf_trail_load<NQ>(X.cg, W, tid & 63, T.row - k, dc[k]);
       }
       if (__ballot(valid)) {
@@ -1986,7 +2076,7 @@ __global__ __launch_bounds__(2 * NG, SF_FAST_WAVES_PER_SIMD) void sf_mfe_fast_ke
           else {
             static_assert(SHARE || DML2, "a main wave either shares the multiloop split with its helpers (NG = 256) or runs it two cells per lane (NG = 128)");
             dec = sf_fast_dml2<WT, LGC>(X, d, tid & 63, i, valid);
-            sf_fast_cell<false, WT, SF_SEC_P1 | SF_SEC_C0 | SF_SEC_PRE, false, FOLD, SFD_MAXLOOP, TBLK, false, UNPK && split>(X, d, i, valid, slot2, slotd, H, HU, ovf, grp == 0, fnb, fpart, dec, eh, e0, dprev, pub);
+            sf_fast_cell<false, WT, SEC_MAIN, false, FOLD, SFD_MAXLOOP, TBLK, false, UNPK && split>(X, d, i, valid, slot2, slotd, H, HU, ovf, grp == 0, fnb, fpart, dec, eh, e0, dprev, pub);
           }
         } else if (MERGE) {
           // Merged helper (W <= 128).  ONE helper wave serves both diagonals of the step: it works on the list of the
@@ -2007,8 +2097,9 @@ __global__ __launch_bounds__(2 * NG, SF_FAST_WAVES_PER_SIMD) void sf_mfe_fast_ke
             const int sd1 = sd0 + 1 >= SF_FAST_NR ? 0 : sd0 + 1;
             SfFastCtx Xh = X;
             Xh.BN = X.BN + 2 * g * (W - 4);
-            sf_fast_cell<false, WT, SF_SEC_HELP, false, FOLD, SFD_MAXLOOP, TBLK, true>(Xh, d0 + g, iC, vC, s2, sd0, H, HU, ovf, false, fnb, fpart, dec, eh, e0, dprev, pub);
-            if (vC) { X.BN[2 * ((g ? sd1 : sd0) * (W - 4) + iC - 1)] = (int16_t)sfd_min(eh, 32000); SF_EMUL_WROTE(X.BN + 2 * ((g ? sd1 : sd0) * (W - 4) + iC - 1), 1); }
+            sf_fast_cell<false, WT, SEC_HELP, false, FOLD, SFD_MAXLOOP, TBLK, true>(Xh, d0 + g, iC, vC, s2, sd0, H, HU, ovf, false, fnb, fpart, dec, eh, e0, dprev, pub);
+            if (vC && HT) hand_over((g ? sd1 : sd0) * (W - 4), iC - 1, W - d0 - g, g ? fbB : fbA, eh, pub);
+            else if (vC) { X.BN[2 * ((g ? sd1 : sd0) * (W - 4) + iC - 1)] = (int16_t)sfd_min(eh, 32000); SF_EMUL_WROTE(X.BN + 2 * ((g ? sd1 : sd0) * (W - 4) + iC - 1), 1); }
           }
         } else {
           // the helper's results -> the cell's OWN entries of the row it is about to publish (unread until the next
@@ -2021,26 +2112,35 @@ __global__ __launch_bounds__(2 * NG, SF_FAST_WAVES_PER_SIMD) void sf_mfe_fast_ke
               X.CI[slotd * (W - 4) + i - 1] = (int16_t)sfd_min(dec, 32000);
             }
           } else {
-            sf_fast_cell<false, WT, SF_SEC_HELP, false, FOLD, SFD_MAXLOOP, TBLK>(X, d, i, valid, slot2, slotd, H, HU, ovf, grp == 0, fnb, fpart, dec, eh, e0, dprev, pub);
-            if (valid) { X.BN[2 * (slotd * (W - 4) + i - 1)] = (int16_t)sfd_min(eh, 32000); SF_EMUL_WROTE(X.BN + 2 * (slotd * (W - 4) + i - 1), 1); }
+            sf_fast_cell<false, WT, SEC_HELP, false, FOLD, SFD_MAXLOOP, TBLK>(X, d, i, valid, slot2, slotd, H, HU, ovf, grp == 0, fnb, fpart, dec, eh, e0, dprev, pub);
+            if (valid && HT) hand_over(slotd * (W - 4), i - 1, W - d, fbd, eh, pub);
+            else if (valid) { X.BN[2 * (slotd * (W - 4) + i - 1)] = (int16_t)sfd_min(eh, 32000); SF_EMUL_WROTE(X.BN + 2 * (slotd * (W - 4) + i - 1), 1); }
           }
         }
       }
-      if (sweep_now && sweep_rows > 0) sf_trail_rows<NQ, DROWS>(T, tid & 63, sweep_rows, dc);
+      if (sweep_now && sweep_rows > 0) sf_trail_rows<NQ, DR>(T, tid & 63, sweep_rows, dc);
       // merged helper: wave 3 lists the next step's cells (the barriers of this step order the list before its readers)
       if (MERGE && grp == 1 && hwave && (ROLES || d0 + 2 >= split_d0) && d0 + 2 < W) build_list(d0 + 2);
 // @section exchange
       if (split) {
         __syncthreads();
         if (!helper && !dmlw && __ballot(valid)) {
-          if (valid) {
+          if (valid && HT) {
+            // (a cell the helper did not visit cannot pair: whatever lies there, its terms are zero and it publishes exactly "none")
+            const int row = slotd * (W - 4), x = i - 1;
+            const uint32_t wa = sf_ldw(X.BN + 2 * (row + x));
+            const int te = X.CI[row + x], ts = X.fML[fbd + x], tx = X.BN[2 * row + 2 * (W - d) + x];
+            const bool tp = pub.type != 0;
+            eh = te; pub.a = tp ? wa : 0u; pub.stem = tp ? ts : 0; pub.ext = tp ? tx : 0;
+          } else if (valid) {
             eh = X.BN[2 * (slotd * (W - 4) + i - 1)];
             if (DML4 && narrow) {
               const uint32_t *const xa = (const uint32_t *)X.BN;
               dec = sfd_min(dec, sfd_min((int)xa[(grp * 16) * (W - 4) + 100 + (tg & 63)], (int)xa[(grp * 16 + 1) * (W - 4) + 100 + (tg & 63)]));
             } else if (SHARE) dec = sfd_min(dec, (int)X.CI[slotd * (W - 4) + i - 1]);
           }
-          sf_fast_cell<false, WT, SF_SEC_FIN | SF_SEC_POST, false, FOLD, SFD_MAXLOOP, TBLK>(X, d, i, valid, slot2, slotd, H, HU, ovf, grp == 0, fnb, fpart, dec, eh, e0, dprev, pub);
+          if (HT) SF_LOCKSTEP();
+          sf_fast_cell<false, WT, SEC_FIN, false, FOLD, SFD_MAXLOOP, TBLK>(X, d, i, valid, slot2, slotd, H, HU, ovf, grp == 0, fnb, fpart, dec, eh, e0, dprev, pub, SFD_TURN + 1, 1 << 20, fbd);
         }
       }
       __syncthreads();
@@ -2059,16 +2159,17 @@ __global__ __launch_bounds__(2 * NG, SF_FAST_WAVES_PER_SIMD) void sf_mfe_fast_ke
         // a clamped or neighbouring entry and is dropped by a select — one LDS round trip where the two tested cells took two, in a
         // phase in which every other wave of the workgroup waits)
         const int d1 = d0 + 1;
-        const int16_t *pd = X.fML + FBASE(d1), *pe = X.fML + FBASE(d0);
+        const int16_t *pd = X.fML + (FB ? fbB : FBASE(d1)), *pe = X.fML + (FB ? fbA : FBASE(d0));
         const bool ex0 = i + d1 <= W, ex1 = i >= 2;  // cell (i, i + d1) / (i - 1, i + d0) exists
         const int ia = i - 1, ib = ex1 ? i - 2 : 0;
         const int p0 = pd[ia], p1 = pd[ib], q0 = pe[i], q1 = pe[ia], q2 = pe[ib];
         const int v0 = sfd_min(p0, sfd_min(q0, q1) + X.MLbase), v1 = sfd_min(p1, sfd_min(q1, q2) + X.MLbase);
         if ((ex0 && v0 < SF_FAST_OVF) || (ex1 && v1 < SF_FAST_OVF)) ovf = 1;
         const int g0 = (ex0 && v0 <= SF_FAST_THRESH) ? v0 : SF_INF16, g1 = (ex1 && v1 <= SF_FAST_THRESH) ? v1 : SF_INF16;
-        if (ex0) X.fML[FBASE(d1) + ia] = (int16_t)g0;
+        if (ex0) X.fML[(FB ? fbB : FBASE(d1)) + ia] = (int16_t)g0;
         fnb = sfd_min(g0, g1) + X.MLbase;
       }
+      if (FB) fb0 += 2 * (W - d0);
       slot2 += 2; if (slot2 >= SF_FAST_NR) slot2 -= SF_FAST_NR;
       slotd += 2; if (slotd >= SF_FAST_NR) slotd -= SF_FAST_NR;
     };
@@ -2101,6 +2202,7 @@ __global__ __launch_bounds__(2 * NG, SF_FAST_WAVES_PER_SIMD) void sf_mfe_fast_ke
       // state: W = 120 53.4 -> 51.6 ms per 262 144 folds, W = 64 / 100 / 117 +3.8 / 4.3 / 4.1 %, W = 118 / 128 +1.4 / 1.6 %; with ONE main
       // role for both groups (the group a wave-uniform value) W = 120 measured 51.9 ms (profiles/role_loops/README.md).
       auto split_loops = [&](auto role_tag) {
+        if constexpr (FBCARRY) fb0 = FBASE(d0);
         if constexpr (LGLOOPS) {
           // (chunks of 32 lanes while a diagonal has more than 30 cells, 16 down to 15 cells, then 8: d0 >= W - 30 / W - 14)
           for (; d0 < W - 30 && d0 < W; d0 += 2) step(d0, SfStepTag<SF_STEP_SPLIT>{}, role_tag);

@@ -17,9 +17,9 @@ FAST = "scanfold_amd/csrc/sf_mfe_fast.hip.h"
 CELLS = "      if (__ballot(valid)) {\n        if (DO_G && d0 < 8)"
 FIN = "        if (!helper && !dmlw && __ballot(valid)) {"
 DML2 = "            dec = sf_fast_dml2<WT, LGC>(X, d, tid & 63, i, valid);"
-MAINCALL = ("            sf_fast_cell<false, WT, SF_SEC_P1 | SF_SEC_C0 | SF_SEC_PRE, false, FOLD, SFD_MAXLOOP, TBLK, false, UNPK && split>(X, d, i, valid, "
+MAINCALL = ("            sf_fast_cell<false, WT, SEC_MAIN, false, FOLD, SFD_MAXLOOP, TBLK, false, UNPK && split>(X, d, i, valid, "
             "slot2, slotd, H, HU, ovf, grp == 0, fnb, fpart, dec, eh, e0, dprev, pub);")
-MGHCALL = "            sf_fast_cell<false, WT, SF_SEC_HELP, false, FOLD, SFD_MAXLOOP, TBLK, true>(Xh, d0 + g, iC,"
+MGHCALL = "            sf_fast_cell<false, WT, SEC_HELP, false, FOLD, SFD_MAXLOOP, TBLK, true>(Xh, d0 + g, iC,"
 
 HOST = "scanfold_amd/csrc/scanfold_hip.hip"
 # "stamps": a cycle-stamped diagnostic build.  Lane 0 of every wave of every 64th workgroup adds, per step and wave, the cycles
@@ -158,7 +158,7 @@ VARIANTS = {
     "secBN": ([(FAST, "      int gb = SF_FAST_BIG, g1 = SF_FAST_BIG;\n      if (G) {", "      int gb = SF_FAST_BIG, g1 = SF_FAST_BIG;\n      if (true) {\n      } else if (G) {")], []),
     "secDML1": ([(FAST, "    dec = SF_FAST_BIG;\n  if (FOLD) {", "    dec = SF_FAST_BIG;\n  if (true) return;\n  if (FOLD) {")], []),
     "secC0": ([(FAST, "  if (SEC & SF_SEC_C0) {\n", "  if (SEC & SF_SEC_C0) e0 = SF_FAST_BIG;\n  if (false) {\n")], []),
-    "secSWEEP": ([(FAST, "      if (sweep_now && sweep_rows > 0) sf_trail_rows<NQ, DROWS>(T, tid & 63, sweep_rows, dc);", "      (void)0;"),
+    "secSWEEP": ([(FAST, "      if (sweep_now && sweep_rows > 0) sf_trail_rows<NQ, DR>(T, tid & 63, sweep_rows, dc);", "      (void)0;"),
                   (FAST, "      const bool sweep_now = defer_on && sweeper && split && T.row > 0;", "      const bool sweep_now = false;")], []),
     # phases: which steps cost what (the other phase keeps its barriers and control code)
     "nosplitwork": ([(FAST, CELLS, "      if (!split && __ballot(valid)) {\n        if (DO_G && d0 < 8)"),
@@ -166,7 +166,14 @@ VARIANTS = {
     "nounsplitwork": ([(FAST, CELLS, "      if (split && __ballot(valid)) {\n        if (DO_G && d0 < 8)")], []),
     # split steps, by role
     "nodml2": ([(FAST, DML2, "            dec = SF_INF16;")], []),
-    "nomainp1": ([(FAST, MAINCALL, MAINCALL.replace("SF_SEC_P1 | SF_SEC_C0 | SF_SEC_PRE", "SF_SEC_PRE"))], []),
+    "nomainp1": ([(FAST, MAINCALL, MAINCALL.replace("SEC_MAIN", "(SEC_MAIN & ~(SF_SEC_P1 | SF_SEC_C0))"))], []),
+    # profiles/main_wave_diet: each item off on its own (both off = the parent's instruction streams)
+    "terms0": ([], ["-DSF_FAST_HELPER_TERMS=0"]), "fbase0": ([], ["-DSF_FAST_FBASE_CARRY=0"]),
+    # ... the sweeper's rows per step in the three split loops of the W = 120 instantiation ("swABC": d0 = 58 .. 88 / 90 .. 104 / 106 .. 118)
+    "sw444": ([], ["-DSF_SWEEP_ROWS_120_A=4", "-DSF_SWEEP_ROWS_120_B=4", "-DSF_SWEEP_ROWS_120_C=4"]),
+    "sw622": ([], ["-DSF_SWEEP_ROWS_120_A=6", "-DSF_SWEEP_ROWS_120_B=2", "-DSF_SWEEP_ROWS_120_C=2"]),
+    "sw633": ([], ["-DSF_SWEEP_ROWS_120_A=6", "-DSF_SWEEP_ROWS_120_B=3", "-DSF_SWEEP_ROWS_120_C=3"]),
+    "sw522": ([], ["-DSF_SWEEP_ROWS_120_A=5", "-DSF_SWEEP_ROWS_120_B=2", "-DSF_SWEEP_ROWS_120_C=2"]),
     "nomgh": ([(FAST, MGHCALL, "            if (false) " + MGHCALL.strip())], []),
     "nofin": ([(FAST, FIN, "        if (false) {")], []),
     # what the main waves' post-barrier work costs, piece by piece
