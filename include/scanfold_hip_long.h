@@ -208,6 +208,63 @@ int sf_pf_probs_pairs(sf_pair_prob *out, size_t cap, size_t *n);
  * the length of its list; and the device bytes it allocated on top of SF_PF_BANDED_BYTES.  Any pointer may be NULL. */
 int sf_pf_banded_probs_times(double *extract_ms, size_t *n_pairs, size_t *extra_bytes);
 
+/* ---- the maximum-expected-accuracy (MEA) structure of a pair list: RNAfold -p --MEA [gamma] ----
+ * Inputs: a record length L; a list of pairs (i, j, p), 1-based, i < j, strictly ascending in (i, j) (sf_pair_prob, the list
+ * sf_pf_banded_probs produces); L unpaired probabilities u; gamma > 0.
+ * Score.  A structure S is a nested set of listed pairs in which every position has at most one partner;
+ *   score(S) = sum over k unpaired in S of u_k + sum over (i, j) in S of w_ij,  w_ij = (2.0 * gamma) * p_ij,
+ * w rounded once and stored: every later operation is an addition or a maximum of doubles, so no expression can be
+ * contracted into an FMA and the result does not depend on how lanes are grouped.
+ * Recurrences.  B = 1 + the largest j - i in the list (1 for an empty list).  For j - i < B
+ *   M[i][j] = max( u_i + M[i+1][j] , max over listed (i, k) with k <= j of (w_ik + M[i+1][k-1]) + M[k+1][j] ),
+ * M = 0 for j < i; for the record, from i = L down to 1,
+ *   E[i] = max( u_i + E[i+1] , max over listed (i, k) of (w_ik + M[i+1][k-1]) + E[k+1] ),  E[L+1] = 0;
+ * score = E[1].  The additions are associated exactly as written.
+ * Traceback.  At a segment or suffix starting at i, position i is unpaired if the stored value equals the first candidate
+ * bit for bit; otherwise i pairs with the smallest k whose candidate equals it.  With that rule the structure and the 64
+ * bits of the score are a function of the inputs alone.
+ * On the device: one fill launch per diagonal d = 0 .. B-1 over a table of L * B doubles stored by diagonals, the exterior
+ * pass and the traceback in one workgroup each. */
+
+/* device memory of the MEA that is linear in L and in the list's length n: the weights (8 n), E (8 (L + 2)), the traceback
+ * stack (8 (L / 2 + 2)) and the structure (L + 1) */
+#define SF_MEA_BYTES(L, n) (8 * (size_t)(n) + 9 * (size_t)(L) + 8 * ((size_t)(L) / 2) + 33)
+/* device memory of one sf_mea_pairs call: the table M, the list (16 n), its rows' offsets and the unpaired vector (16 L),
+ * and the linear part */
+#define SF_MEA_PAIRS_BYTES(L, B, n) (8 * (size_t)(L) * (size_t)(B) + 16 * (size_t)(n) + 16 * (size_t)(L) + SF_MEA_BYTES(L, n))
+
+/* MEA structure of a caller's list.  pairs: n records, strictly ascending in (i, j), 1 <= i < j <= L, p finite in [0, 1];
+ * unpaired: L finite values in [0, 1]; gamma finite > 0.  mea_out: L + 1 bytes or NULL; mea_score or NULL.
+ * A position may have any number of listed partners.  Needs sf_init only: neither parameters nor a span.
+ * Device memory, allocated for the call and freed before it returns: SF_MEA_PAIRS_BYTES(L, B, n), B as above.
+ * L < 1, L > SF_MAX_BANDED, pairs NULL with n > 0, unpaired NULL, gamma NaN, infinite or <= 0, a record out of order, with
+ * i >= j, i < 1, j > L, or p outside [0, 1] or not finite, an unpaired value outside [0, 1] or not finite: SF_ERR_BAD_ARG
+ * before anything is allocated on the device or launched.  Not enough device memory: SF_ERR_HIP with the text in
+ * sf_last_hip_error().  Nothing reaches the caller unless the call succeeds. */
+int sf_mea_pairs(int L, const sf_pair_prob *pairs, size_t n, const double *unpaired, double gamma,
+                 char *mea_out, double *mea_score);
+
+/* sf_pf_banded_probs, then the MEA structure of the list and unpaired vector it produced, from device memory.
+ * The ten outputs it shares with sf_pf_banded_probs are bit for bit what that call returns for the same arguments (one host
+ * path), the list is staged for sf_pf_probs_pairs in the same way, and sf_pf_banded_times / sf_pf_banded_probs_times report
+ * for this call what they report for a probs call.  sf_mea_pairs on that list and vector returns the same structure and the
+ * same score bits: both run one device path.
+ * The table M is not a new allocation: it lives in the second of the seven band tables ("qb by columns"), all of which are
+ * dead once the extraction has read ob and qb; the band of the list is at most the band of the call.  Device memory on top
+ * of sf_pf_banded_probs's is SF_MEA_BYTES(L, n), reported by sf_mea_times.
+ * Errors are sf_pf_banded_probs's, and gamma NaN, infinite or <= 0: SF_ERR_BAD_ARG before anything is allocated or launched.
+ * Any output pointer may be NULL; nothing reaches the caller, and neither the staged list nor sf_mea_times's figures change,
+ * unless the call succeeds. */
+int sf_pf_banded_mea(const uint8_t *seq, int L, const char *cons, const int32_t *mfe_dcal_hint, double cutoff, double gamma,
+                     double *ens_dG, double *mean_bp_dist, char *centroid_out, double *centroid_dist,
+                     double *unpaired_out, double *entropy_out, size_t *n_pairs, char *mea_out, double *mea_score);
+
+/* of the last successful call of either: device-event ms of fill, exterior pass and traceback, the band B of the list,
+ * the fill launches (one per diagonal, = B; the one launch that forms the weights before them is timed with the fill but
+ * not counted), and the device bytes allocated for the MEA on top of what the call had anyway (sf_mea_pairs: all of
+ * SF_MEA_PAIRS_BYTES; sf_pf_banded_mea: SF_MEA_BYTES).  Any pointer may be NULL. */
+int sf_mea_times(double *fill_ms, double *ext_ms, double *trace_ms, int *band, int *fill_launches, size_t *extra_bytes);
+
 /* One row of sf_pf_long_batch: sf_pf_long's three numbers, the final per-nucleotide scale ln s and the number of inside
  * passes the row took (what sf_pf_long_times reports for the row folded alone). */
 typedef struct { double ens_dG, mean_bp_dist, centroid_dist, lns; int32_t attempts, reserved; } sf_pf_long_row;

@@ -103,6 +103,12 @@ _LONG_EXPORTS = {
     "sf_pf_probs_pairs": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
     "sf_pf_banded_probs_times": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_size_t),
                                                 ctypes.POINTER(ctypes.c_size_t)]),
+    "sf_mea_pairs": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_double,
+                                    ctypes.c_void_p, ctypes.c_void_p]),
+    "sf_pf_banded_mea": (ctypes.c_int, [_c_u8p, ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_double]
+                         + [ctypes.c_void_p] * 6 + [ctypes.POINTER(ctypes.c_size_t)] + [ctypes.c_void_p] * 2),
+    "sf_mea_times": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double)] * 3 + [ctypes.POINTER(ctypes.c_int)] * 2
+                     + [ctypes.POINTER(ctypes.c_size_t)]),
     "sf_pf_long_batch": (ctypes.c_int, [_c_u8p, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 5),
     "sf_pf_long_batch_times": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                               ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
@@ -165,6 +171,8 @@ _FOLD_BANDED_BATCH = ("sf_fold_banded_batch", "batched whole-record folds under 
 _PF_LONG = ("sf_pf_long", "whole-record partition functions")
 _PF_BANDED = ("sf_pf_banded", "whole-record partition functions under a base-pair span in banded tables")
 _PF_BANDED_PROBS = ("sf_pf_banded_probs", "base-pair probabilities of a whole record under a base-pair span")
+_MEA_PAIRS = ("sf_mea_pairs", "maximum-expected-accuracy structures of a pair list")
+_PF_BANDED_MEA = ("sf_pf_banded_mea", "maximum-expected-accuracy structures of a whole record under a base-pair span")
 _PF_LONG_BATCH = ("sf_pf_long_batch", "partition functions of many sequences past %d nt" % SF_MAX_W)
 _DUPLEX = ("duplex entry points (sf_duplex_batch, sf_lri_scan, sf_lri_background)", "duplex folds and --lri",
            tuple(_DUPLEX_EXPORTS))
@@ -583,6 +591,66 @@ class Engine:
         launches (pf_banded_times has the passes before it), the length of the list, and the device bytes allocated on top
         of pf_banded_bytes."""
         return self._times(_PF_BANDED_PROBS, extract_ms=_D, n_pairs=_Z, extra_bytes=_Z)
+
+    def has_mea_pairs(self):
+        return getattr(self.lib, "sf_mea_pairs", None) is not None
+
+    def mea_pairs(self, L, pairs, unpaired, gamma=1.0):
+        """The maximum-expected-accuracy structure of a pair list (sf_mea_pairs; RNAfold -p --MEA gamma) -> (dot-bracket,
+        score).  pairs: PAIR_PROB_DTYPE records (or anything np.asarray turns into them), 1-based i < j <= L, strictly
+        ascending in (i, j), p in [0, 1]; unpaired: L values in [0, 1]; gamma > 0.  The structure maximises the sum of u over
+        its unpaired positions plus 2 gamma p over its pairs, ties broken as include/scanfold_hip_long.h states, so structure
+        and score are a function of the arguments alone.  Needs neither parameters nor a span.  Raises ScanFoldHipError on
+        a bad argument and on a library without the entry point (there is no fallback)."""
+        self._need(*_MEA_PAIRS)
+        L = int(L)
+        pr = np.ascontiguousarray(pairs, dtype=PAIR_PROB_DTYPE)
+        unp = np.ascontiguousarray(unpaired, dtype=np.float64)
+        if unp.shape != (max(L, 0),):
+            raise ValueError("one unpaired probability per nucleotide")
+        db = np.zeros(max(L, 0) + 1, dtype=np.uint8)
+        score = ctypes.c_double(0.0)
+        self._check(self.lib.sf_mea_pairs(L, pr.ctypes.data if len(pr) else None, len(pr), unp.ctypes.data, float(gamma),
+                                          db.ctypes.data, ctypes.addressof(score)))
+        return bytes(db[:L]).decode(), score.value
+
+    def has_pf_banded_mea(self):
+        return getattr(self.lib, "sf_pf_banded_mea", None) is not None
+
+    def pf_banded_mea(self, seq, cons=None, mfe_hint=None, cutoff=0.01, gamma=1.0):
+        """pf_banded_probs, then the maximum-expected-accuracy structure of its list and unpaired vector, formed on the device
+        while they are there (sf_pf_banded_mea) -> pf_banded_probs's dict, every value bit for bit pf_banded_probs's, plus
+          mea        the dot-bracket structure
+          mea_score  its score: the sum of unpaired over its unpaired positions plus 2 gamma p over its pairs.
+        gamma > 0 weighs pairs against unpaired positions: larger values give more pairs (RNAfold --MEA's gamma).
+        mea_pairs on the returned pairs and unpaired gives the same structure and score.  Raises ScanFoldHipError where no
+        span is set or cutoff or gamma is out of range, and on a library without the entry point (there is no fallback)."""
+        self._need(*_PF_BANDED_MEA)
+        arr, L, c = _record(seq, cons)
+        hint = None if mfe_hint is None else np.array([int(mfe_hint)], dtype=np.int32)
+        out = np.zeros(4)
+        cen = np.zeros(L + 1, dtype=np.uint8)
+        mea = np.zeros(L + 1, dtype=np.uint8)
+        unp, ent = np.zeros(L), np.zeros(L)
+        n = ctypes.c_size_t(0)
+        self._check(self.lib.sf_pf_banded_mea(arr.ctypes.data, L, c, None if hint is None else hint.ctypes.data,
+                                              float(cutoff), float(gamma), out[0:].ctypes.data, out[1:].ctypes.data,
+                                              cen.ctypes.data, out[2:].ctypes.data, unp.ctypes.data, ent.ctypes.data,
+                                              ctypes.byref(n), mea.ctypes.data, out[3:].ctypes.data))
+        pairs = np.zeros(n.value, dtype=PAIR_PROB_DTYPE)
+        self._check(self.lib.sf_pf_probs_pairs(pairs.ctypes.data, n.value, ctypes.byref(n)))
+        return dict(dG=float(out[0]), mean_bp_dist=float(out[1]), centroid=bytes(cen[:L]).decode(),
+                    centroid_dist=float(out[2]), unpaired=unp, entropy=ent, pairs=pairs, mea=bytes(mea[:L]).decode(),
+                    mea_score=float(out[3]))
+
+    def mea_times(self):
+        """-> dict(fill_ms, ext_ms, trace_ms, band, fill_launches, extra_bytes) of the last mea_pairs or pf_banded_mea: device
+        events of the three phases, the band of the list, and the device bytes the MEA allocated on top of what the call had
+        anyway."""
+        self._need("sf_mea_times", _MEA_PAIRS[1])
+        vals = [_D(), _D(), _D(), _I(), _I(), _Z()]
+        self._check(self.lib.sf_mea_times(*(ctypes.byref(v) for v in vals)))
+        return {k: v.value for k, v in zip(("fill_ms", "ext_ms", "trace_ms", "band", "fill_launches", "extra_bytes"), vals)}
 
     def has_pf_long_batch(self):
         return getattr(self.lib, "sf_pf_long_batch", None) is not None

@@ -30,6 +30,7 @@
 #include "sf_pf_long_batch.hip.h"
 #include "sf_pf_banded.hip.h"
 #include "sf_pf_probs.hip.h"
+#include "sf_mea.hip.h"
 #include "sf_pf_fast.hip.h"
 #include "sf_pf_lds.hip.h"
 #include "sf_shuffle.hip.h"
@@ -1993,8 +1994,89 @@ double g_pfb_lns = 0.0;
 // e^+-300 of its neighbours' weights, which leaves the outside pass (products of two such cells) inside FP64
 const double kPfBandEpsB = 300.0;
 
+// What sf_mea_pairs and sf_pf_banded_mea ask of mea_run, and where it is staged: the structure (L + 1 bytes), the score, the
+// device-event times of fill, exterior pass and traceback, the band of the list, the fill launches, the device bytes.
+struct MeaRun {
+  double gamma;
+  std::vector<char> db;
+  double score = 0;
+  double ms[3] = {0, 0, 0};
+  int band = 0, launches = 0;
+  size_t bytes = 0;
+};
+// of the last successful sf_mea_pairs or sf_pf_banded_mea
+double g_mea_ms[3] = {0, 0, 0};
+int g_mea_band = 0, g_mea_launches = 0;
+size_t g_mea_bytes = 0;
+
+void mea_keep(const MeaRun &R) {
+  for (int k = 0; k < 3; k++) g_mea_ms[k] = R.ms[k];
+  g_mea_band = R.band;
+  g_mea_launches = R.launches;
+  g_mea_bytes = R.bytes;
+}
+
+// B of the model: 1 + the largest j - i of the list
+int mea_band(const sf_pair_prob *pairs, size_t n) {
+  int B = 1;
+  for (size_t t = 0; t < n; t++) B = std::max(B, 1 + (int)(pairs[t].j - pairs[t].i));
+  return B;
+}
+
+// The one device path of the MEA structure (sf_mea.hip.h): weights, fill, exterior pass and traceback over a list, its
+// rows' offsets and an unpaired vector that are in device memory already; Bf's four events are free.  d_M: L * B doubles
+// the caller has to spare (sf_pf_banded_mea: a dead band table), or NULL: allocated here.  R.bytes counts what is
+// allocated here: SF_MEA_BYTES(L, n), and 8 L B with the table.
+int mea_run(CallBufs &Bf, int L, int B, const SfPairProb *d_list, const unsigned long long *d_off, size_t n, const double *d_unp,
+            double *d_M, MeaRun &R) {
+  int rc;
+  const size_t nL = (size_t)L;
+  SfMea F;
+  F.L = L;
+  F.B = B;
+  F.n = (unsigned long long)n;
+  F.list = d_list;
+  F.off = d_off;
+  F.u = d_unp;
+  F.M = d_M;
+  F.status = (int *)g.status.p;
+  R.bytes = SF_MEA_BYTES(L, n);
+  if (!d_M) {
+    if ((rc = Bf.alloc(&F.M, nL * (size_t)B, "MEA table"))) return rc;
+    R.bytes += nL * (size_t)B * sizeof(double);
+  }
+  if ((rc = Bf.alloc(&F.wa, n, "MEA weights"))) return rc;
+  if ((rc = Bf.alloc(&F.E, nL + 2, "MEA exterior values"))) return rc;
+  if ((rc = Bf.alloc(&F.stk, SF_MEA_STACK_INTS(L), "MEA traceback stack"))) return rc;
+  if ((rc = Bf.alloc(&F.db, nL + 1, "MEA structure"))) return rc;
+  R.db.resize(nL + 1);
+  HIPCHK(hipEventRecord(Bf.ev[0], g.stream));
+  if (n) SF_LAUNCH(sf_mea_weights_kernel, (int)std::min((n + 255) / 256, (size_t)4096), 256, 0, g.stream, F, 2.0 * R.gamma);
+  for (int d = 0; d < B; d++) SF_LAUNCH(sf_mea_fill_kernel, (int)((nL - (size_t)d + 255) / 256), 256, 0, g.stream, F, d);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(Bf.ev[1], g.stream));
+  SF_LAUNCH(sf_mea_exterior_kernel, 1, 64, 0, g.stream, F);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(Bf.ev[2], g.stream));
+  SF_LAUNCH(sf_mea_trace_kernel, 1, 64, 0, g.stream, F);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(Bf.ev[3], g.stream));
+  HIPCHK(hipMemcpyAsync(R.db.data(), F.db, nL + 1, hipMemcpyDeviceToHost, g.stream));
+  HIPCHK(hipMemcpyAsync(&R.score, F.E + 1, sizeof(double), hipMemcpyDeviceToHost, g.stream));
+  if ((rc = read_status(g.stream, false))) return rc;
+  for (int k = 0; k < 3; k++) {
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, Bf.ev[k], Bf.ev[k + 1]));
+    R.ms[k] = ms;
+  }
+  R.band = B;
+  R.launches = B;  // (the fill's, one per diagonal; the weights' launch before them is not counted)
+  return SF_OK;
+}
+
 // What sf_pf_banded_probs asks of the shared host path on top of sf_pf_banded's outputs, and where it is staged: unp / ent
-// hold L doubles, pairs the list; ms, bytes: the extraction's device-event time and its device allocations.
+// hold L doubles, pairs the list; ms, bytes: the extraction's device-event time and its device allocations.  mea: NULL, or
+// sf_pf_banded_mea's request, run on the extraction's device buffers (d_unp, d_off, d_list) while they are alive.
 struct PfbProbs {
   double cutoff;
   std::vector<double> unp, ent;
@@ -2003,6 +2085,10 @@ struct PfbProbs {
   std::vector<unsigned long long> off;  // destructor drains the copies on an early return)
   double ms = 0;
   size_t bytes = 0;
+  MeaRun *mea = nullptr;
+  const double *d_unp = nullptr;
+  const unsigned long long *d_off = nullptr;
+  const SfPairProb *d_list = nullptr;
 };
 static_assert(sizeof(sf_pair_prob) == 16 && sizeof(SfPairProb) == 16 && offsetof(sf_pair_prob, p) == offsetof(SfPairProb, p),
               "the device's pair record is the header's");
@@ -2063,6 +2149,12 @@ int pfb_extract(CallBufs &Bf, const SfPfBand &F, int waves, PfbProbs &P) {
   }
   HIPCHK(hipEventElapsedTime(&ms0, Bf.ev[0], Bf.ev[1]));
   P.ms = (double)ms0 + (double)ms1;
+  if (P.mea) {  // (an empty list never had its offsets copied up)
+    if (!total) HIPCHK(hipMemsetAsync(d_off, 0, nL * sizeof(unsigned long long), g.stream));
+    P.d_unp = d_unp;
+    P.d_off = d_off;
+    P.d_list = total ? d_list : nullptr;
+  }
   return SF_OK;
 }
 
@@ -2186,6 +2278,13 @@ int pf_banded_run(const char *who, const uint8_t *seq, int L, const char *cons, 
     lns += eps;
   }
   if (probs && (rc = pfb_extract(Bf, F, prob_waves, *probs))) return rc;
+  // The MEA structure of that list, from the device buffers of the extraction.  All seven band tables are dead once the
+  // extraction has read ob and qb; M (L doubles a diagonal of the list's band, which is at most B) lives in the second,
+  // "qb by columns / A0".
+  if (probs && probs->mea &&
+      (rc = mea_run(Bf, L, mea_band(probs->pairs.data(), probs->pairs.size()), probs->d_list, probs->d_off, probs->pairs.size(),
+                    probs->d_unp, d_tab[1], *probs->mea)))
+    return rc;
   if ((rc = leave(SF_OK))) return rc;
   // staged until here: nothing reaches the caller unless the call succeeds
   hcen[nL] = 0;
@@ -2213,18 +2312,22 @@ int sf_pf_banded(const uint8_t *seq, int L, const char *cons, const int32_t *mfe
   return pf_banded_run("sf_pf_banded", seq, L, cons, mfe_dcal_hint, ens_dG, mean_bp_dist, centroid_out, centroid_dist, nullptr);
 }
 
-int sf_pf_banded_probs(const uint8_t *seq, int L, const char *cons, const int32_t *mfe_dcal_hint, double cutoff, double *ens_dG,
-                       double *mean_bp_dist, char *centroid_out, double *centroid_dist, double *unpaired_out,
-                       double *entropy_out, size_t *n_pairs) {
-  int rc = check_ready();
-  if (rc) return rc;
+}  // extern "C"
+
+namespace {
+// sf_pf_banded_probs (mea == NULL) and sf_pf_banded_mea after check_ready: one body, so the ten outputs they share are the
+// same bytes.  *mea comes back staged; its caller hands it on.
+int pf_banded_probs_call(const char *who, const uint8_t *seq, int L, const char *cons, const int32_t *mfe_dcal_hint, double cutoff,
+                         double *ens_dG, double *mean_bp_dist, char *centroid_out, double *centroid_dist, double *unpaired_out,
+                         double *entropy_out, size_t *n_pairs, MeaRun *mea) {
   if (!(cutoff > 0.0 && cutoff <= 1.0)) return SF_ERR_BAD_ARG;  // (a NaN fails both comparisons)
   // the vectors and the list are staged like the four classic outputs, which wait in locals until the extraction is in
   PfbProbs P;
   P.cutoff = cutoff;
+  P.mea = mea;
   double dG = 0, mbd = 0, cd = 0;
   std::vector<char> cen(centroid_out ? (size_t)std::max(L, 0) + 1 : 0);
-  rc = pf_banded_run("sf_pf_banded_probs", seq, L, cons, mfe_dcal_hint, &dG, &mbd, centroid_out ? cen.data() : nullptr, &cd, &P);
+  const int rc = pf_banded_run(who, seq, L, cons, mfe_dcal_hint, &dG, &mbd, centroid_out ? cen.data() : nullptr, &cd, &P);
   if (rc) return rc;  // (the list of the last successful call stays as it is)
   g_pfbp_pairs.swap(P.pairs);
   g_pfbp_ms = P.ms;
@@ -2236,6 +2339,84 @@ int sf_pf_banded_probs(const uint8_t *seq, int L, const char *cons, const int32_
   if (unpaired_out) memcpy(unpaired_out, P.unp.data(), (size_t)L * sizeof(double));
   if (entropy_out) memcpy(entropy_out, P.ent.data(), (size_t)L * sizeof(double));
   if (n_pairs) *n_pairs = g_pfbp_pairs.size();
+  return SF_OK;
+}
+
+bool mea_gamma_ok(double gamma) { return isfinite(gamma) && gamma > 0.0; }
+}  // namespace
+
+extern "C" {
+
+int sf_pf_banded_probs(const uint8_t *seq, int L, const char *cons, const int32_t *mfe_dcal_hint, double cutoff, double *ens_dG,
+                       double *mean_bp_dist, char *centroid_out, double *centroid_dist, double *unpaired_out,
+                       double *entropy_out, size_t *n_pairs) {
+  const int rc = check_ready();
+  if (rc) return rc;
+  return pf_banded_probs_call("sf_pf_banded_probs", seq, L, cons, mfe_dcal_hint, cutoff, ens_dG, mean_bp_dist, centroid_out,
+                              centroid_dist, unpaired_out, entropy_out, n_pairs, nullptr);
+}
+
+int sf_pf_banded_mea(const uint8_t *seq, int L, const char *cons, const int32_t *mfe_dcal_hint, double cutoff, double gamma,
+                     double *ens_dG, double *mean_bp_dist, char *centroid_out, double *centroid_dist, double *unpaired_out,
+                     double *entropy_out, size_t *n_pairs, char *mea_out, double *mea_score) {
+  int rc = check_ready();
+  if (rc) return rc;
+  if (!mea_gamma_ok(gamma)) return SF_ERR_BAD_ARG;
+  MeaRun R;
+  R.gamma = gamma;
+  rc = pf_banded_probs_call("sf_pf_banded_mea", seq, L, cons, mfe_dcal_hint, cutoff, ens_dG, mean_bp_dist, centroid_out,
+                            centroid_dist, unpaired_out, entropy_out, n_pairs, &R);
+  if (rc) return rc;
+  mea_keep(R);
+  if (mea_out) memcpy(mea_out, R.db.data(), (size_t)L + 1);
+  if (mea_score) *mea_score = R.score;
+  return SF_OK;
+}
+
+int sf_mea_pairs(int L, const sf_pair_prob *pairs, size_t n, const double *unpaired, double gamma, char *mea_out,
+                 double *mea_score) {
+  SF_ENTER();
+  if (L < 1 || L > SF_MAX_BANDED || (!pairs && n) || !unpaired || !mea_gamma_ok(gamma)) return SF_ERR_BAD_ARG;
+  for (int k = 0; k < L; k++)
+    if (!(unpaired[k] >= 0.0 && unpaired[k] <= 1.0)) return SF_ERR_BAD_ARG;  // (a NaN fails both comparisons)
+  // the rows' offsets, on the host as sf_pf_banded_probs scans its counts
+  std::vector<unsigned long long> off((size_t)L, 0);
+  for (size_t t = 0; t < n; t++) {
+    const sf_pair_prob &r = pairs[t];
+    if (r.i < 1 || r.i >= r.j || r.j > L || !(r.p >= 0.0 && r.p <= 1.0)) return SF_ERR_BAD_ARG;
+    if (t && (r.i < pairs[t - 1].i || (r.i == pairs[t - 1].i && r.j <= pairs[t - 1].j))) return SF_ERR_BAD_ARG;
+    if (r.i < L) off[(size_t)r.i]++;  // (counted at the next row: the running sum below makes it that row's start)
+  }
+  for (int k = 1; k < L; k++) off[(size_t)k] += off[(size_t)k - 1];
+  int rc;
+  MeaRun R;
+  R.gamma = gamma;
+  {
+    CallBufs Bf("sf_mea_pairs");
+    SfPairProb *d_list;
+    unsigned long long *d_off;
+    double *d_unp;
+    if ((rc = Bf.upload(&d_list, (const SfPairProb *)pairs, n, "pair list"))) return rc;
+    if ((rc = Bf.upload(&d_off, (const unsigned long long *)off.data(), (size_t)L, "offsets of the rows in the pair list"))) return rc;
+    if ((rc = Bf.upload(&d_unp, unpaired, (size_t)L, "unpaired probabilities"))) return rc;
+    for (auto &e : Bf.ev) HIPCHK(hipEventCreate(&e));
+    if ((rc = mea_run(Bf, L, mea_band(pairs, n), d_list, d_off, n, d_unp, nullptr, R))) return rc;
+  }
+  R.bytes += n * sizeof(SfPairProb) + 2 * (size_t)L * sizeof(double);
+  mea_keep(R);
+  if (mea_out) memcpy(mea_out, R.db.data(), (size_t)L + 1);
+  if (mea_score) *mea_score = R.score;
+  return SF_OK;
+}
+
+int sf_mea_times(double *fill_ms, double *ext_ms, double *trace_ms, int *band, int *fill_launches, size_t *extra_bytes) {
+  SF_ENTER();
+  if (fill_ms) *fill_ms = g_mea_ms[0];
+  if (ext_ms) *ext_ms = g_mea_ms[1];
+  if (trace_ms) *trace_ms = g_mea_ms[2];
+  if (band) *band = g_mea_band;
+  if (fill_launches) *fill_launches = g_mea_launches;
+  if (extra_bytes) *extra_bytes = g_mea_bytes;
   return SF_OK;
 }
 

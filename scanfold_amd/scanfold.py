@@ -16,7 +16,8 @@ as the RNA facade routes them), into `<that>.<--dbn_file_path>` and `<that>.AllD
 directories and IGV wig exports are not reproduced.
 --global_span N (not upstream) runs those three folds under max bp span N in banded tables (sf_fold_banded), and
 --global_ensemble_banded adds their ensembles from the banded partition function (sf_pf_banded), at any record length, and
---global_bpp CUTOFF with it their base pairs with probability >= CUTOFF and positional entropy tracks (sf_pf_banded_probs).
+--global_bpp CUTOFF with it their base pairs with probability >= CUTOFF and positional entropy tracks (sf_pf_banded_probs),
+and --global_mea GAMMA with that their maximum-expected-accuracy structures (sf_pf_banded_mea; RNAfold -p --MEA GAMMA).
 --global_zscore (not upstream) z-scores the whole record against shuffles of itself (one batched whole-record fold,
 sf_fold_long_batch) into `<that>.global_zscore.txt`; --global_zscore_span N (not upstream) does so under max bp span N in
 banded tables (one sf_fold_banded_batch: linear in the record's length, records past 32767 nt).
@@ -157,7 +158,7 @@ def read_reactivities(path):
 
 
 def global_refold(seq, name, outname, temperature, dbn_file_path="AllDBN-global_refold.txt", ensemble=False, span=0,
-                  ensemble_banded=False, bpp=None):
+                  ensemble_banded=False, bpp=None, mea=None):
     """ScanFold.py:1509-1547 (--global_refold): a fresh RNA.md() at md.temperature = int(-t) — no --span, exactly as
     upstream — folds the whole record unconstrained and with line 3 of `<outname>.ScanFold.-1.dbn` / `.-2.dbn` as
     hc_add_from_db constraint, and writes the three records to `<outname>.<dbn_file_path>`; `<outname>.AllDBN.txt` is the
@@ -182,7 +183,11 @@ def global_refold(seq, name, outname, temperature, dbn_file_path="AllDBN-global_
     whose four classic values are pf_banded's bit for bit, so the ensemble file is the same bytes; for each fold (tags
     full, -1, -2) two more files: `<outname>.global_refold.<tag>.bpp.txt`, a header line "i\tj\tp span=N" and one
     "%d\t%d\t%.6g" line per pair with p >= CUTOFF, ascending in (i, j) and 1-based, and
-    `<outname>.global_refold.<tag>.entropy.wig`, the positional entropy in bits, one value per nucleotide."""
+    `<outname>.global_refold.<tag>.entropy.wig`, the positional entropy in bits, one value per nucleotide.
+    mea (--global_mea GAMMA, not upstream; needs bpp): the three ensembles go through Engine.pf_banded_mea, whose other
+    values are pf_banded_probs's bit for bit, so every file above is the same bytes; each fold gains
+    `<outname>.global_refold.<tag>.mea.dbn`: a header ">NAME TAG MEA gamma=%g cutoff=%g span=%d score=%.2f", the sequence,
+    and the maximum-expected-accuracy structure of the listed pairs (RNAfold -p --MEA GAMMA)."""
     from . import RNA
     span = int(span or 0)
     tail = " span=%d" % span if span > 0 else ""
@@ -200,7 +205,9 @@ def global_refold(seq, name, outname, temperature, dbn_file_path="AllDBN-global_
             whole.fold(eng, seq, c, whole.ALWAYS if span > 0 else whole.AUTO) for c in (cons[0], cons[1], None)))
         ens = []
         hints = [int(round(e * 100)) for e in (e0, e1, e2)]
-        if ensemble_banded and bpp is not None:
+        if ensemble_banded and bpp is not None and mea is not None:
+            ens = [whole.pf_mea(eng, seq, c, h, bpp, mea) for c, h in zip([None, cons[0], cons[1]], hints)]
+        elif ensemble_banded and bpp is not None:
             ens = [whole.pf_probs(eng, seq, c, h, bpp) for c, h in zip([None, cons[0], cons[1]], hints)]
         elif ensemble or ensemble_banded:
             ens = whole.pf_rows(eng, seq, [None, cons[0], cons[1]], hints, whole.ALWAYS if ensemble_banded else whole.NEVER)
@@ -221,6 +228,10 @@ def global_refold(seq, name, outname, temperature, dbn_file_path="AllDBN-global_
                 w.write("i\tj\tp" + tail + "\n")
                 w.write("".join("%d\t%d\t%.6g\n" % (i, j, p) for i, j, p in r["pairs"].tolist()))
             writers.write_wig(r["entropy"].tolist(), 1, name, outname + ".global_refold." + tag + ".entropy.wig")
+            if mea is not None:
+                with open(outname + ".global_refold." + tag + ".mea.dbn", "w") as w:
+                    w.write(">%s %s MEA gamma=%g cutoff=%g span=%d score=%.2f\n%s\n%s\n"
+                            % (name, tag, mea, bpp, span, r["mea_score"], seq, r["mea"]))
     with open(outname + ".AllDBN.txt", "w") as w:
         for tag in ("no_filter", "-1", "-2"):
             with open(outname + ".ScanFold." + tag + ".dbn") as f:
@@ -307,6 +318,9 @@ def build_parser():
     p.add_argument('--global_bpp', type=float, default=None, metavar='CUTOFF',
                    help='not in upstream ScanFold: with --global_ensemble_banded, also write the base pairs with probability '
                         '>= CUTOFF (0 < CUTOFF <= 1) and the positional entropy track of each of the three ensembles')
+    p.add_argument('--global_mea', type=float, default=None, metavar='GAMMA',
+                   help='not in upstream ScanFold: with --global_bpp, also write the maximum-expected-accuracy structure of each '
+                        'of the three ensembles (RNAfold -p --MEA GAMMA; GAMMA > 0, larger values give more pairs)')
     p.add_argument('--global_zscore', action='store_true',
                    help='not in upstream ScanFold: z-score of the whole record (its MFE at -t, no --span, against -r shuffles of '
                         '--type seeded with --seed) into <output prefix>.global_zscore.txt; costs r + 1 whole-record folds')
@@ -344,6 +358,13 @@ def main(argv=None):
                          "give all three")
     if args.global_ensemble_banded and args.global_ensemble:
         raise ValueError("--global_ensemble and --global_ensemble_banded write the same file: give one of them")
+    if args.global_mea is not None:
+        if args.global_bpp is None:
+            raise ValueError("--global_mea GAMMA folds the base-pair probabilities of --global_bpp into a structure: give both")
+        if not (np.isfinite(args.global_mea) and args.global_mea > 0.0):
+            raise ValueError("--global_mea GAMMA: a finite weight, GAMMA > 0")
+        if args.lri:
+            raise ValueError("--global_mea folds the record of a window scan: not with --lri")
     if args.global_bpp is not None:
         if not args.global_ensemble_banded:
             raise ValueError("--global_bpp CUTOFF lists the base-pair probabilities of the ensembles of "
@@ -461,7 +482,8 @@ def main(argv=None):
             if args.global_refold:
                 print("Refolding full sequence using ScanFold results as constraints...")
                 global_refold(seq, args.name, outname, args.t, args.dbn_file_path, ensemble=args.global_ensemble,
-                              span=args.global_span or 0, ensemble_banded=args.global_ensemble_banded, bpp=args.global_bpp)
+                              span=args.global_span or 0, ensemble_banded=args.global_ensemble_banded, bpp=args.global_bpp,
+                              mea=args.global_mea)
             if args.c == 1 and not args.dont_extract:
                 with open(outname + ".ScanFold.-2.dbn") as f:
                     line = f.readlines()[2]

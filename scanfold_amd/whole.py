@@ -5,7 +5,7 @@ points: full tables (fold_long, pf_long; up to SF_MAX_LONG), banded tables under
 pf_banded; up to SF_MAX_BANDED), and their batches.  mfe_route and pf_route choose among them ("Routes of the
 whole-record folds"; tests/test_whole_routes.py pins the table); fold, fold_rows, pf and pf_rows run what they chose; pf_probs
 runs the banded partition function with its base-pair probabilities brought out (pf_banded_probs: pf_banded's route, no
-route of its own).  No other module of the package calls one of them on an engine.
+route of its own), and pf_mea adds the maximum-expected-accuracy structure of that list (pf_banded_mea, likewise).  No other module of the package calls one of them on an engine.
 
 A caller states its banded policy:
   AUTO    the RNA facade's rule: banded tables when the record is past SF_MAX_LONG, or when a span is resident, the record is
@@ -138,3 +138,14 @@ def pf_probs(eng, seq, cons=None, mfe_hint=None, cutoff=0.01):
         raise _lib.ScanFoldHipError("base-pair probabilities of a whole record need sf_%s, which this library (%s) does not "
                                     "export" % (call, getattr(eng.lib, "_name", "?")))
     return getattr(eng, call)(seq, cons, mfe_hint=mfe_hint, cutoff=cutoff)
+
+
+def pf_mea(eng, seq, cons=None, mfe_hint=None, cutoff=0.01, gamma=1.0):
+    """pf_probs with the maximum-expected-accuracy structure of its list (Engine.pf_banded_mea's dict: pf_banded_probs's plus
+    mea and mea_score), on the same route: pf_route's banded one, the policy ALWAYS.  A library without sf_pf_banded_mea is a
+    ScanFoldHipError."""
+    call = _routed(pf_route, eng, len(seq), False, ALWAYS) + "_mea"
+    if not getattr(eng, "has_" + call)():
+        raise _lib.ScanFoldHipError("the maximum-expected-accuracy structure of a whole record needs sf_%s, which this library "
+                                    "(%s) does not export" % (call, getattr(eng.lib, "_name", "?")))
+    return getattr(eng, call)(seq, cons, mfe_hint=mfe_hint, cutoff=cutoff, gamma=gamma)
